@@ -5,7 +5,7 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Both forms run N ranks, one per GPU: started plainly with --gpus N > 1 (no WORLD_SIZE in the environment) this script
-becomes the launcher and re-executes itself under torch.distributed.run; it refuses to start when fewer than N HIP
+becomes the launcher and runs itself under torch.distributed.run as a child process; it refuses to start when fewer than N HIP
 devices are visible, and when the launcher's WORLD_SIZE disagrees with --gpus.  `n_gpus` in the line is the number of
 ranks of the RCCL communicator the statistics were reduced over, not an argument or an environment variable.
 
@@ -21,6 +21,10 @@ Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (the backwar
 events recorded on the kernel's own stream inside this process; `cpu_baseline` is the CPU oracle
 (single thread, the reference has no threads) on a bounded sample of the same workload.
 PyTorch is used for torch.distributed (RCCL) and device synchronisation only.
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last one (--dump-outputs DIR) and prints the
+line.  Everything else the line can carry -- CPU baselines, live PMC traffic passes, the single-problem seam, the repeat
+block, solver statistics, the iLQR solves, the other configs -- runs only with --full.
 """
 import argparse
 import json
@@ -59,14 +63,14 @@ def parse():
                          "(pendulum n=2 m=1 N=100 batch=8192), c3 = configs[3] (bicycle n=4 m=2 N=50 batch=65536 "
                          "per node, with the steering bound), c4 = configs[4] (random LTV n=12 m=4 N=512 "
                          "batch=16384, fp32 storage)")
-    ap.add_argument("--live-traffic", action="store_true", help="(the default at one GPU; kept for older command lines)")
+    ap.add_argument("--live-traffic", action="store_true", help="(the default of --full at one GPU; kept for older command lines)")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not measure roofline.traffic in this run.  By default (one GPU, rocprofv3 present) the C1 line's traffic "
+                    help="do not measure roofline.traffic in this run.  With --full (one GPU, rocprofv3 present) the C1 line's traffic "
                          "comes from two short rocprofv3 passes of this same command (--kernel-trace --pmc FETCH_SIZE, then WRITE_SIZE; "
                          "each counter in its own pass, nothing else traced) run as child processes before the timed region, ~1 minute; "
-                         "with this flag, or when a pass fails, the tracked figure of profiles/pmc_traffic.json is used and labelled")
+                         "without --full, with this flag, or when a pass fails, the tracked figure of profiles/pmc_traffic.json is used and labelled")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="config c1 at one GPU also runs short timed regions of configs[2], [3] (8192 and 65536 problems) and [4] "
+                    help="with --full, config c1 at one GPU also runs short timed regions of configs[2], [3] (8192 and 65536 problems) and [4] "
                          "after its own and reports them under config.other_configs; this flag leaves them out")
     ap.add_argument("--other-steps", type=int, default=10, help="timed sweeps per entry of config.other_configs")
     ap.add_argument("--sweeps-only", action="store_true",
@@ -77,6 +81,13 @@ def parse():
     ap.add_argument("--c4-mixed", action="store_true",
                     help="config c4: fp32 storage with fp64 tile arithmetic (the ALTRO_HIP_F32 default of the C ABI) instead of "
                          "the pure-fp32 backward sweep (ALTRO_HIP_F32_PURE: v_mfma_f32_16x16x4_f32, four problems per wave)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the timed steps: CPU baselines, live traffic, the single-problem seam, "
+                         "the repeat block, statistics, the iLQR solves and the other configs (the options above that shape "
+                         "those legs apply only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (K, d, P, p, x, u, y of a fixed seeded sample "
+                         "of problems, delta_V and status of the whole batch) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -102,8 +113,11 @@ def relaunch_if_needed(args):
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    print("[bench] --gpus %d: re-executing as %s" % (args.gpus, " ".join(cmd)), file=sys.stderr, flush=True)
-    os.execv(sys.executable, cmd)
+    print("[bench] --gpus %d: launching %s" % (args.gpus, " ".join(cmd)), file=sys.stderr, flush=True)
+    # a child process, not exec: the device count above has initialised HIP in this process, and replacing a process that
+    # holds the GPU open is unsafe
+    import subprocess
+    sys.exit(subprocess.run(cmd).returncode)
 
 
 def resolve_batch(args, default_per_gpu, rank, world, default_global=None):
@@ -780,24 +794,33 @@ def lane_config(args, rank, local_rank, world, dist, torch, chan):
     bt, set_guess = make_lane_batch(args.config, batch, first, N, local_rank, args.lane_fused)
 
     elapsed, kern = timed_region(bt, args, world, dist, torch, shard)
-    rep = repeat_block(bt, torch, elapsed / args.steps * 1e3, args.repeat_seconds)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(bt, torch, args.dump_outputs, first, False)
+    rep = repeat_block(bt, torch, elapsed / args.steps * 1e3, args.repeat_seconds if args.full else 0)
     ms_b, nb, name_b = kern[0]["avg_ms"], 1, kern[0]["name"]
     ms_f, nf, name_f = kern[1]["avg_ms"], 1, kern[1]["name"]
-    # one full batched solve (all problems to convergence), timed on the host clock; one untimed solve first (the first
-    # launch of each kernel loads its code object), duals and penalties reset in between so that both start alike
-    t_solves = []
-    for timed in (False, True, True, True):     # (median of three timed solves)
-        if c3:
-            bt.reset_duals(1.0)
-        set_guess()
-        torch.cuda.synchronize()
-        t1 = time.perf_counter()
-        res = bt.ilqr_solve(iterations_max=80, use_backtracking=c3)
-        torch.cuda.synchronize()
-        if timed:
-            t_solves.append(time.perf_counter() - t1)
-    t_solve = sorted(t_solves)[1]
-    stats = chan.reduce(bt)     # after the solve: the quantities Solve reports
+    full_solve, stats = None, None
+    if args.full:
+        # one full batched solve (all problems to convergence), timed on the host clock; one untimed solve first (the first
+        # launch of each kernel loads its code object), duals and penalties reset in between so that both start alike
+        t_solves = []
+        for timed in (False, True, True, True):     # (median of three timed solves)
+            if c3:
+                bt.reset_duals(1.0)
+            set_guess()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            res = bt.ilqr_solve(iterations_max=80, use_backtracking=c3)
+            torch.cuda.synchronize()
+            if timed:
+                t_solves.append(time.perf_counter() - t1)
+        t_solve = sorted(t_solves)[1]
+        full_solve = {"seconds": t_solve, "seconds_min_max": [min(t_solves), max(t_solves)], "sweeps": int(res["sweeps"]),
+                      "merit_launches": int(res["merit_launches"]),
+                      "converged": int((res["status"] == 0).sum()),
+                      "mean_iterations": float(res["iterations"].mean()),
+                      "problems_per_s": batch / t_solve}
+        stats = chan.reduce(bt)     # after the solve: the quantities Solve reports
     if rank == 0:
         bytes_b, bytes_f = bt.algorithmic_bytes(0), bt.algorithmic_bytes(1)
         dur_b = ms_b / nb * 1e-3
@@ -815,12 +838,7 @@ def lane_config(args, rank, local_rank, world, dist, torch, chan):
                        "plan": "LANE (lane-per-problem SoA)",
                        "kernels": {name_b: dict(kern[0], GBps=bytes_b / dur_b / 1e9),
                                    name_f: dict(kern[1], GBps=bytes_f / (ms_f / nf * 1e-3) / 1e9)},
-                       "repeat": rep, "stats": stats,
-                       "full_solve": {"seconds": t_solve, "seconds_min_max": [min(t_solves), max(t_solves)], "sweeps": int(res["sweeps"]),
-                                      "merit_launches": int(res["merit_launches"]),
-                                      "converged": int((res["status"] == 0).sum()),
-                                      "mean_iterations": float(res["iterations"].mean()),
-                                      "problems_per_s": batch / t_solve}},
+                       "repeat": rep, "stats": stats, "full_solve": full_solve},
             "roofline": roofline_block("c3" if c3 else "c2", batch, N, name_b, bytes_b, dur_b),
             "roofline_forward": roofline_block("c3" if c3 else "c2", batch, N, name_f, bytes_f, ms_f / nf * 1e-3, slot=1),
         }))
@@ -853,6 +871,42 @@ def ilqr_sweep_time(bt, torch, reps=5):
                     "the trajectory: 0.12-0.14 ms)" % reps}
 
 
+DUMP_BYTES = 64 << 20    # --dump-outputs writes at most this much
+
+
+def dump_outputs(bt, torch, out_dir, first, f32):
+    """--dump-outputs DIR: what the last timed step (altro_hip_sweep) hands its caller -- delta_V and status of the whole batch,
+    K, d, P, p, x, u, y of a fixed seeded sample of problems (their global indices: problems.npy) sized to keep all files under
+    DUMP_BYTES.  The per-problem arrays are fetched in device-pointer mode and sampled on the device (P of the whole C1 batch alone
+    is 1.2 GB).  float32 for an fp32 handle (the values it stores), float64 otherwise."""
+    import ctypes
+    N, n, m, B = bt.N, bt.n, bt.m, bt.batch
+    dt = np.float32 if f32 else np.float64
+    shapes = {"K": (N, m * n), "d": (N, m), "P": (N + 1, n * n), "p": (N + 1, n), "x": (N + 1, n), "u": (N, m), "y": (N + 1, n)}
+    out = {"delta_V": bt.get("delta_V").astype(dt), "status": bt.get("status").astype(dt)}
+    per_problem = sum(int(np.prod(s)) for s in shapes.values()) * np.dtype(dt).itemsize + 8
+    count = max(1, min(B, 64, (DUMP_BYTES - sum(a.nbytes for a in out.values())) // per_problem))
+    idx = np.sort(np.random.default_rng(20261016).choice(B, count, replace=False))
+    out["problems"] = (first + idx).astype(np.float64)
+    sel = torch.as_tensor(idx, device="cuda")
+    bt.set_pointer_mode(True)
+    try:
+        for name, shp in shapes.items():
+            buf = torch.empty((B,) + shp, dtype=torch.float64, device="cuda")
+            torch.cuda.synchronize()
+            rc = getattr(bt.L, "altro_hip_get_" + name)(bt.h, ctypes.c_void_p(buf.data_ptr()))
+            if rc != 0:
+                raise RuntimeError("altro_hip_get_%s failed (%d): %s" % (name, rc, bt.L.altro_hip_last_error().decode()))
+            out[name] = buf.index_select(0, sel).cpu().numpy().astype(dt)
+            del buf
+    finally:
+        bt.set_pointer_mode(False)
+        torch.cuda.empty_cache()
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 _JSON_OUT = None
 
 
@@ -880,14 +934,14 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     # The CPU legs run first, before any HIP state exists in this process (the all-cores leg forks workers).
     cpu_leg = None
-    if world == 1 and not args.no_cpu_baseline and args.config == "c1":
+    if args.full and world == 1 and not args.no_cpu_baseline and args.config == "c1":
         cpu_leg = cpu_baseline(args.horizon, args.cpu_seconds)
         cpu_leg["all_cores"] = cpu_all_cores(args.horizon)
         cpu_leg["eigen"] = eigen_probe()
     # roofline.traffic of THIS run: two short PMC passes of the same command as child processes, before this process touches the
     # GPU (one GPU only: the driver's multi-GPU runs keep the tracked figure)
     global _LIVE_TRAFFIC, _LIVE_TRAFFIC_NOTE
-    if not args.no_live_traffic and rank == 0 and world == 1:
+    if args.full and not args.no_live_traffic and rank == 0 and world == 1:
         t_live = time.perf_counter()
         try:
             _LIVE_TRAFFIC = live_traffic(args)
@@ -897,17 +951,19 @@ def main():
             print("[bench] live traffic failed: %s" % e, file=sys.stderr)
             _LIVE_TRAFFIC_NOTE = "the live PMC passes failed (%s): tracked figure" % e
     else:
-        _LIVE_TRAFFIC_NOTE = "--no-live-traffic" if args.no_live_traffic else "more than one rank: tracked figure"
+        _LIVE_TRAFFIC_NOTE = ("without --full: tracked figure" if not args.full else "--no-live-traffic" if args.no_live_traffic
+                              else "more than one rank: tracked figure")
     # ... and of the other single-GPU configs the line carries (C2, C3 at 8192 and 65536, C4): the same two passes each
     live_other = {}
-    if (not args.no_live_traffic and rank == 0 and world == 1 and args.config == "c1" and not args.no_other_configs and not args.sweeps_only):
+    if (args.full and not args.no_live_traffic and rank == 0 and world == 1 and args.config == "c1" and not args.no_other_configs
+            and not args.sweeps_only):
         for key, (cfg_o, batch_o) in {"c2": ("c2", 8192), "c3_8192": ("c3", 8192), "c3_65536": ("c3", 65536), "c4": ("c4", 16384)}.items():
             try:
                 live_other[key] = live_traffic(args, config=cfg_o, batch=batch_o)
             except Exception as e:   # noqa: BLE001
                 print("[bench] live traffic of %s failed: %s" % (key, e), file=sys.stderr)
     seam = None
-    if rank == 0 and world == 1 and args.config == "c1" and not args.sweeps_only and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and args.config == "c1" and not args.sweeps_only and not args.no_cpu_baseline:
         seam = single_problem_seam()
     import torch
     import torch.distributed as dist
@@ -947,16 +1003,18 @@ def main():
     bt = make_mfma_batch(c4, args.c4_pure, batch, first, N, local_rank)
 
     elapsed, kern = timed_region(bt, args, world, dist, torch, shard)
-    rep = repeat_block(bt, torch, elapsed / args.steps * 1e3, args.repeat_seconds)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(bt, torch, args.dump_outputs, first, c4)
+    rep = repeat_block(bt, torch, elapsed / args.steps * 1e3, args.repeat_seconds if args.full else 0)
     ms_b, nb, name_b = kern[0]["avg_ms"], 1, kern[0]["name"]
     ms_f, nf, name_f = kern[1]["avg_ms"], 1, kern[1]["name"]
 
     # the same batch as a full iLQR solve (rollout, expansion, backward sweep, merit-function line search,
     # convergence test; an LQ problem, so <= 3 sweeps), outside the timed region
     # who ran what: one row per rank (device, PCI bus id, its own K-step time) so that a straggler or a mis-bound rank shows
-    ranks = rank_table(elapsed_local(), args.steps, local_rank, rank, world, dist, torch)
+    ranks = rank_table(elapsed_local(), args.steps, local_rank, rank, world, dist, torch) if args.full else None
     full_solve, ilqr_sweep = None, None
-    if not c4 and not args.sweeps_only:
+    if args.full and not c4 and not args.sweeps_only:
         Qd2 = np.stack([np.ones(n), 100.0 * np.ones(n)])
         bt.set_tracking_cost(Qd2, np.full((1, m), 1e-2), np.zeros((2, n)), np.zeros((1, m)), k_stride_zero=True,
                              batch_stride_zero=True)
@@ -973,13 +1031,13 @@ def main():
 
     # solver statistics -- the only thing that ever crosses GPUs (RCCL over xGMI, latency-bound) -- after the solve,
     # so that the quantities SolverImpl::Solve reports are all populated (for c4: the sweep's quantities only)
-    stats = chan.reduce(bt)
+    stats = chan.reduce(bt) if args.full else None
 
     # ... and, after the statistics (they describe the unconstrained solve), the same batch with input bounds |u| <= 2 as a whole
     # AL-iLQR solve: constraint rows, dual and penalty updates, line searches past the first step -- the AL half of the path
     # (SURVEY section 8 row f2), outside the timed region like the solve above
     constrained = None
-    if not c4 and not args.sweeps_only:
+    if args.full and not c4 and not args.sweeps_only:
         import altro_amd
         Gb = np.zeros((2 * m, n + m)); Gb[:m, n:] = np.eye(m); Gb[m:, n:] = -np.eye(m)
         bt.add_linear_constraint(0, N - 1, altro_amd.CONE_INEQUALITY, Gb, np.full(2 * m, 2.0))
@@ -1000,7 +1058,7 @@ def main():
     # the other single-GPU configs of BASELINE.json, each a short timed region of its own on this GPU (one-GPU runs of the
     # default config only; the C1 handle is released first: C4 alone holds 18 GB)
     others = None
-    if not c4 and world == 1 and not args.no_other_configs and not args.sweeps_only:
+    if args.full and not c4 and world == 1 and not args.no_other_configs and not args.sweeps_only:
         bytes_keep = (bt.algorithmic_bytes(0), bt.algorithmic_bytes(1))
         bt.close()
         bt = None

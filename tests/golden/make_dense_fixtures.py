@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Generates tests/golden/dense_fixtures.npz: dense outputs of the CPU oracle (oracle/, itself pinned to the
+"""Generates tests/golden/dense_fixtures_*.npz: dense outputs of the CPU oracle (oracle/, itself pinned to the
 reference's constants by tests/test_oracle_kat.py) for every BASELINE.json config at reduced batch (SURVEY.md section 7
 step 1).  The inputs are NOT stored: tests/problems.py regenerates them from its counter-based PRNG; a checksum of the
 inputs is, so that a drifting generator is caught.  With these the GPU parity evidence can be replayed on a box that
 has neither gcc nor the oracle's .so (tests/test_gpu_golden.py), and the oracle itself is regression-pinned
 (tests/test_oracle_golden.py).
 
-    python tests/golden/make_dense_fixtures.py          # rewrites the .npz (run in the build container)
+    python tests/golden/make_dense_fixtures.py          # rewrites the .npz parts (run in the build container)
 """
 import os
 import sys
@@ -18,9 +18,9 @@ sys.path.insert(0, ROOT)
 from oracle import oracle          # noqa: E402
 from tests import problems         # noqa: E402
 
-OUT = os.path.join(ROOT, "tests", "golden", "dense_fixtures.npz")
 from tests.golden_cases import (AL_KINDS, MERIT_ALPHAS, P_KNOTS, REG_CASE, SOLVES, TVLQR, al_case, checksum, load_kats,   # noqa: E402,F401
-                                lq12_case, merit_case, mpc_case, mpc_linear_costs, quad12_case, quad4_case, solve_case, tvlqr_problem)
+                                lq12_case, merit_case, mpc_case, mpc_linear_costs, quad12_case, quad4_case, save_dense, solve_case,
+                                tvlqr_problem)
 
 OKIND = {"double_integrator": oracle.MODEL_DI, "pendulum": oracle.MODEL_PENDULUM, "bicycle": oracle.MODEL_BICYCLE}
 
@@ -301,5 +301,4 @@ def generate():
 if __name__ == "__main__":
     oracle.build()
     d = generate()
-    np.savez_compressed(OUT, **d)
-    print("wrote %s: %d arrays, %.1f KB" % (OUT, len(d), os.path.getsize(OUT) / 1e3))
+    print("wrote %d arrays in %d tests/golden/dense_fixtures_*.npz" % (len(d), save_dense(d)))

@@ -1,13 +1,54 @@
-"""Problem definitions of the dense golden fixtures (tests/golden/dense_fixtures.npz): shared by the generator
+"""Problem definitions of the dense golden fixtures (tests/golden/dense_fixtures_*.npz): shared by the generator
 (tests/golden/make_dense_fixtures.py, which runs the oracle) and by the tests that replay the fixtures -- the GPU one
 (tests/test_gpu_golden.py) must not need the oracle, so nothing here imports it."""
 import hashlib
+import io
+import os
 
 import numpy as np
 
 from tests import problems
 
 P_KNOTS = {}      # (round 2 kept P of c1 / c4 at three knot points only; every knot point is stored now)
+
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+PART_BYTES = 900_000     # each dense_fixtures_<i>.npz stays below the 1 MiB a committed file may have
+
+
+def save_dense(arrays):
+    """Writes the dense fixtures as dense_fixtures_<i>.npz, arrays packed in key order into parts of at most PART_BYTES
+    (compressed), and removes parts a larger earlier set left behind."""
+    def size(k):
+        b = io.BytesIO()
+        np.savez_compressed(b, **{k: arrays[k]})
+        return b.tell()
+    parts, cur, used = [], {}, 0
+    for k in sorted(arrays):
+        s = size(k)
+        if cur and used + s > PART_BYTES:
+            parts.append(cur)
+            cur, used = {}, 0
+        cur[k] = arrays[k]
+        used += s
+    parts.append(cur)
+    for f in os.listdir(GOLDEN):
+        if f.startswith("dense_fixtures_") and f.endswith(".npz"):
+            os.remove(os.path.join(GOLDEN, f))
+    for i, p in enumerate(parts):
+        np.savez_compressed(os.path.join(GOLDEN, "dense_fixtures_%d.npz" % i), **p)
+    return len(parts)
+
+
+def load_dense():
+    """The dense fixtures as one mapping {name: array}, from all dense_fixtures_<i>.npz."""
+    out = {}
+    names = sorted(f for f in os.listdir(GOLDEN) if f.startswith("dense_fixtures_") and f.endswith(".npz"))
+    assert names, "no tests/golden/dense_fixtures_*.npz"
+    for f in names:
+        with np.load(os.path.join(GOLDEN, f)) as z:
+            out.update({k: z[k] for k in z.files})
+    return out
 
 
 def checksum(pr):

@@ -1,15 +1,11 @@
 """The HIP path (through the C ABI) against the committed dense golden fixtures -- no oracle, no gcc on the box:
-tests/golden/dense_fixtures.npz holds the CPU oracle's outputs for every BASELINE.json config at reduced batch
+tests/golden/dense_fixtures_*.npz hold the CPU oracle's outputs for every BASELINE.json config at reduced batch
 (tests/golden/make_dense_fixtures.py; the inputs are regenerated from tests/problems.py's seeded streams).
 Tolerances are the ones DESIGN.md section 2 states per plan.  Needs an MI355X."""
-import os
-
 import numpy as np
 import pytest
 
 import altro_amd
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 pytestmark = pytest.mark.gpu
 
@@ -22,7 +18,8 @@ def mk():
 
 @pytest.fixture(scope="module")
 def dense():
-    return np.load(os.path.join(ROOT, "tests", "golden", "dense_fixtures.npz"))
+    from tests.golden_cases import load_dense
+    return load_dense()
 
 
 def relerr(a, b):

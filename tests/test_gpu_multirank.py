@@ -52,7 +52,7 @@ def _bench(args):
 @pytest.mark.timeout(600)
 def test_bench_honours_gpus_2_weak_c1():
     """`python bench.py --gpus 2` (no launcher around it) runs two ranks and says so."""
-    out = _bench(["--gpus", "2", "--batch", "256", "--horizon", "32", "--steps", "3", "--warmup", "1",
+    out = _bench(["--gpus", "2", "--batch", "256", "--horizon", "32", "--steps", "3", "--warmup", "1", "--full",
                   "--repeat-seconds", "0", "--no-cpu-baseline"])
     assert out["n_gpus"] == 2 and out["scaling"] == "weak"
     assert out["config"]["global_batch"] == 512 and out["config"]["batch_per_gpu"] == 256
@@ -64,7 +64,7 @@ def test_bench_honours_gpus_2_weak_c1():
 @pytest.mark.timeout(600)
 def test_bench_c3_shards_the_global_batch():
     """configs[3] names a node-wide batch: --config c3 splits --global-batch over the ranks (ragged here)."""
-    out = _bench(["--gpus", "2", "--config", "c3", "--global-batch", "1001", "--steps", "3", "--warmup", "1",
+    out = _bench(["--gpus", "2", "--config", "c3", "--global-batch", "1001", "--steps", "3", "--warmup", "1", "--full",
                   "--repeat-seconds", "0"])
     assert out["n_gpus"] == 2 and out["scaling"] == "strong"
     assert out["config"]["global_batch"] == 1001 and out["config"]["batch_per_gpu"] == 501

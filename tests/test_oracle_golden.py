@@ -1,4 +1,4 @@
-"""The dense golden fixtures (tests/golden/dense_fixtures.npz, made by tests/golden/make_dense_fixtures.py) against the
+"""The dense golden fixtures (tests/golden/dense_fixtures_*.npz, made by tests/golden/make_dense_fixtures.py) against the
 oracle as it is built today: the checker is regression-pinned, and the seeded generators the fixtures depend on have not
 drifted.  CPU only."""
 import os
@@ -14,7 +14,8 @@ import make_dense_fixtures as mk   # noqa: E402
 
 @pytest.fixture(scope="module")
 def dense():
-    return np.load(os.path.join(ROOT, "tests", "golden", "dense_fixtures.npz"))
+    from tests.golden_cases import load_dense
+    return load_dense()
 
 
 @pytest.mark.parametrize("name", mk.TVLQR)

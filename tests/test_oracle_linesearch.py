@@ -1,12 +1,20 @@
 """Pins oracle/linesearch_oracle.c against (a) the constants in the reference's line-search tests
-(src/linesearch/test/linesearch_tests.cpp:134-270) and (b) the REAL reference code, compiled from
-/root/reference/src/linesearch into oracle/_ref/liblinesearch_ref.so (`make -C oracle ref`).  CPU."""
+(src/linesearch/test/linesearch_tests.cpp:134-270) and (b) the REAL reference code: its results on 1600 seeded cases, recorded
+in tests/golden/reference_linesearch.npz by tests/golden/make_linesearch_fixtures.py, and the library itself
+(oracle/_ref/liblinesearch_ref.so, `make -C oracle ref`) where the reference tree was there to build it.  CPU."""
 import ctypes as C
+import os
+import sys
 
 import numpy as np
 import pytest
 
 from oracle import oracle
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+sys.path.insert(0, GOLDEN)
+import make_linesearch_fixtures as mk   # noqa: E402
+from make_linesearch_fixtures import cubic, quad   # noqa: E402
 
 
 def run_oracle(fn, c1=1e-4, c2=0.9, try_cubic_first=0, backtracking=0):
@@ -26,14 +34,6 @@ def run_oracle(fn, c1=1e-4, c2=0.9, try_cubic_first=0, backtracking=0):
     phi0, dphi0 = fn(0.0)
     alpha = L.oracle_ls_run(C.byref(ls), oracle.MERIT_FN(cb), None, 1.0, phi0, dphi0)
     return alpha, ls, evals
-
-
-def quad(a, c):
-    return lambda x: (a * (x - c) ** 2, 2 * a * (x - c))
-
-
-def cubic(c):
-    return lambda x: ((x - c) ** 2 - (x - c) ** 3, 2 * (x - c) - 3 * (x - c) ** 2)
 
 
 def test_reference_quadratic_cases():
@@ -58,45 +58,22 @@ def test_reference_cubic_cases(c, c2, iters):
 
 
 def test_against_real_reference_linesearch():
-    R = oracle.ref_linesearch()
-    if R is None:
-        pytest.skip("oracle/_ref not built (reference tree absent)")
-    rng = np.random.default_rng(7)
+    rec = np.load(os.path.join(GOLDEN, "reference_linesearch.npz"))
+    first = np.concatenate([[0], np.cumsum(rec["n_evals"])])
+    R = oracle.ref_linesearch()      # the library as well, where it was built
     n_checked = 0
-    for trial in range(400):
-        kind = trial % 4
-        if kind == 0:
-            a, c = rng.uniform(0.1, 5), rng.uniform(-0.5, 3)
-            fn = quad(a, c)
-        elif kind == 1:
-            fn = cubic(rng.uniform(0.01, 2.5))
-        elif kind == 2:
-            w, s = rng.uniform(0.5, 6), rng.uniform(0.1, 3)
-            fn = lambda x, w=w, s=s: (-s * np.sin(w * x) + 0.3 * x * x, -s * w * np.cos(w * x) + 0.6 * x)
-        else:
-            k, c = rng.uniform(1, 30), rng.uniform(0.001, 0.5)
-            fn = lambda x, k=k, c=c: (np.cosh(k * (x - c)), k * np.sinh(k * (x - c)))
-        phi0, dphi0 = fn(0.0)
-        for tcf in (0, 1):
-            for bt in (0, 1):
-                alpha, ls, evals = run_oracle(fn, try_cubic_first=tcf, backtracking=bt)
-                revals = []
-
-                def cb(a, phi, dphi, ctx):
-                    p, dp = fn(a)
-                    revals.append(a)
-                    phi[0] = p
-                    if dphi:
-                        dphi[0] = dp
-
-                st, it, ph, dph = C.c_int(), C.c_int(), C.c_double(), C.c_double()
-                ralpha = R.ref_ls_run(oracle.MERIT_FN(cb), None, 1.0, phi0, dphi0, tcf, bt,
-                                      C.byref(st), C.byref(it), C.byref(ph), C.byref(dph))
-                assert st.value == ls.status
-                assert it.value == ls.n_iters
-                assert revals == evals          # identical sequence of trial steps, bit for bit
-                assert (np.isnan(ralpha) and np.isnan(alpha)) or ralpha == alpha
-                if st.value != 3:
-                    assert ph.value == ls.phi
-                n_checked += 1
+    for i, (fn, phi0, dphi0, tcf, bt) in enumerate(mk.cases()):
+        alpha, ls, evals = run_oracle(fn, try_cubic_first=tcf, backtracking=bt)
+        refs = [(int(rec["status"][i]), int(rec["iters"][i]), float(rec["alpha"][i]), float(rec["phi"][i]),
+                 rec["evals"][first[i]:first[i + 1]].tolist())]
+        if R is not None:
+            refs.append(mk.run_reference(R, fn, phi0, dphi0, tcf, bt))
+        for st, it, ralpha, ph, revals in refs:
+            assert st == ls.status
+            assert it == ls.n_iters
+            assert revals == evals          # identical sequence of trial steps, bit for bit
+            assert (np.isnan(ralpha) and np.isnan(alpha)) or ralpha == alpha
+            if st != 3:
+                assert ph == ls.phi
+        n_checked += 1
     assert n_checked == 1600

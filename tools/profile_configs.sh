@@ -13,7 +13,7 @@ for cfg in $CFGS; do
     c4mixed) ARGS="--config c4 --c4-mixed" ;;
     *) ARGS="--config $cfg" ;;
   esac
-  CMD="python bench.py $ARGS --steps 5 --warmup 1 --no-cpu-baseline --repeat-seconds 0"
+  CMD="python bench.py $ARGS --steps 5 --warmup 1 --full --no-cpu-baseline --repeat-seconds 0"
   OUT=gpurun_out/prof_${TAG}_$cfg
   rm -rf $OUT; mkdir -p $OUT
   SUM=gpurun_out/${TAG}_$cfg.txt

@@ -1,9 +1,9 @@
 #!/bin/bash
-# tools/profile_default.sh <tag> -- the DEFAULT bench command under rocprofv3: kernel-trace stats, then FETCH_SIZE and
+# tools/profile_default.sh <tag> -- the full bench command (--full) under rocprofv3: kernel-trace stats, then FETCH_SIZE and
 # WRITE_SIZE in their own passes (kernel-trace only, each pass bounded); summary in gpurun_out/<tag>_default_rocprofv3.txt
 TAG=${1:-r02z}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-CMD="python bench.py --no-cpu-baseline --no-live-traffic"
+CMD="python bench.py --full --no-cpu-baseline --no-live-traffic"
 OUT=gpurun_out/prof_${TAG}_default; rm -rf $OUT; mkdir -p $OUT
 SUM=gpurun_out/${TAG}_default_rocprofv3.txt
 echo "# $CMD  (= the default bench command without its CPU leg; rocprofv3, MI355X; one pass per counter set, --kernel-trace only)" > $SUM

@@ -1,5 +1,5 @@
 """tools/profile_index.py -- regenerate profiles/INDEX.md: ONE table, kernel -> latest evidence file -> duration -> bytes -> fraction
-of the 8 TB/s HBM roof, from (a) the JSON line of a default `python bench.py` run (per-kernel hipEvent durations, algorithmic bytes,
+of the 8 TB/s HBM roof, from (a) the JSON line of a `python bench.py --full` run (per-kernel hipEvent durations, algorithmic bytes,
 live PMC traffic) and (b) the rocprofv3 summary of the same command (tools/profile_default.sh: --kernel-trace --stats, then
 FETCH_SIZE and WRITE_SIZE in their own passes).  Usage: python tools/profile_index.py [tag]     (tag defaults to the newest
 profiles/r*_bench_default.json that has a rocprofv3 summary next to it)."""
@@ -97,8 +97,8 @@ def main():
 
     out = [f"# profiles/INDEX.md — the current number for every kernel of the hot path, and the file it comes from",
            "",
-           f"Regenerated by `python tools/profile_index.py {tag}` from `profiles/{tag}_bench_default.json` (the JSON line of a default",
-           f"`python bench.py` run: hipEvent durations inside the timed region, SURVEY §8(d) algorithmic bytes, live PMC traffic) and",
+           f"Regenerated by `python tools/profile_index.py {tag}` from `profiles/{tag}_bench_default.json` (the JSON line of a",
+           f"`python bench.py --full` run: hipEvent durations inside the timed region, SURVEY §8(d) algorithmic bytes, live PMC traffic) and",
            f"`profiles/{summ}` (rocprofv3 `--kernel-trace --stats` + FETCH_SIZE / WRITE_SIZE passes of the same command, one box).",
            "`frac` = algorithmic bytes ÷ duration ÷ 8 TB/s; `frac_traffic` = PMC bytes (2·1024·FETCH_SIZE + 1024·WRITE_SIZE, gfx950",
            "correction of MI355X_MICROARCH.md) ÷ duration ÷ 8 TB/s. rocprofv3's average mixes the bench's full sweeps with the masked",

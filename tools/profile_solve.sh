@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out
 for cfg in $CFGS; do
   for mode in sequenced policy; do
-    CMD="python bench.py --config $cfg --steps 2 --warmup 1 --no-cpu-baseline --repeat-seconds 0"
+    CMD="python bench.py --config $cfg --steps 2 --warmup 1 --full --no-cpu-baseline --repeat-seconds 0"
     OUT=gpurun_out/prof_${TAG}_${cfg}_$mode
     rm -rf $OUT; mkdir -p $OUT
     SUM=gpurun_out/${TAG}_${cfg}_solve_$mode.txt

@@ -4,7 +4,7 @@ TAG=${1:-r01}
 export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
-CMD="python bench.py --steps 10 --warmup 2 --no-cpu-baseline"
+CMD="python bench.py --steps 10 --warmup 2 --full --no-cpu-baseline"
 cd $GRAFT_REPO_ROOT
 rocprofv3 --kernel-trace --stats -d $OUT/trace -o bench -- $CMD > $OUT/trace_stdout.log 2>&1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/pmc_fetch -o bench -- $CMD > $OUT/pmc_fetch.log 2>&1
