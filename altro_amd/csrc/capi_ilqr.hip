@@ -17,7 +17,7 @@ template <typename T>
 int al_upload_typed(altro_hip_batch* h) {
   const int64_t B = h->batch;
   h->al_Gpad_count = 0;
-  for (void** p : {(void**)&h->al_d_knots, (void**)&h->al_d_big, (void**)&h->al_d_gsel, &h->al_d_G, &h->al_d_Gpad, &h->al_d_g, &h->al_d_z})
+  for (void** p : {(void**)&h->al_d_knots, (void**)&h->al_d_big, (void**)&h->al_d_gsel, (void**)&h->al_d_guser, &h->al_d_G, &h->al_d_Gpad, &h->al_d_g, &h->al_d_z})
     if (*p) { (void)hipFree(*p); *p = nullptr; }
   if (h->al_defs.empty()) { h->al_rows = 0; return 0; }
   // G on the device: p x (n + m) column-major as given on plan LANE; on plan MFMA16 p x 16 in the tile's own column order
@@ -151,6 +151,16 @@ int al_upload_typed(altro_hip_batch* h) {
       int rcg = dmalloc(h, (void**)&h->al_d_gsel, gsel.size() * sizeof(int));
       if (rcg) return rcg;
       HIP_TRY(hipMemcpy(h->al_d_gsel, gsel.data(), gsel.size() * sizeof(int), hipMemcpyHostToDevice));
+    }
+    // blocks from the caller's source (AlTable::guser): only the run-time compiled kernels read the table, and only a handle with
+    // such a block has one
+    std::vector<int> guser(defs.size(), 0);
+    bool any_user = false;
+    for (size_t i = 0; i < defs.size(); ++i) { guser[i] = defs[i].user; any_user = any_user || defs[i].user != 0; }
+    if (any_user) {
+      int rcu = dmalloc(h, (void**)&h->al_d_guser, guser.size() * sizeof(int));
+      if (rcu) return rcu;
+      HIP_TRY(hipMemcpy(h->al_d_guser, guser.data(), guser.size() * sizeof(int), hipMemcpyHostToDevice));
     }
   }
   h->al_row32_ok = true;   // (kernels/ilqr_row32.hip: a lane position per row, the row-wise cones)
@@ -381,7 +391,7 @@ int gen_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int 
   a.al.enabled = h->al_defs.empty() ? 0 : 1;
   a.al.uniform = h->al_uniform; a.al.rows_per_knot = h->al_rows_per_knot; a.al.N = h->N; a.al.G_count = h->al_G_count;
   a.al.has_soc = h->al_has_soc; a.al.all_sel = h->al_all_sel; a.al.Gpad = nullptr; a.al.Gpad_count = 0;
-  a.al.big = h->al_d_big; a.al.gsel = h->al_d_gsel;
+  a.al.big = h->al_d_big; a.al.gsel = h->al_d_gsel; a.al.guser = h->al_d_guser;
   // MeritFunction in the row layout of kernels/ilqr_row32.hip: plan MFMA32's shapes (also on a handle created as plan GENERIC), fp64,
   // dynamics as data, every constraint block in a row-wise cone with at most 32 rows
   a.row32 = (sizeof(T) == 8 && row32_eligible(h)) ? 1 : 0;
@@ -401,12 +411,21 @@ int gen_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int 
   }
   if constexpr (sizeof(T) == 8) {
     if (h->model_set && h->model.kind == MODEL_USER) {   // the caller's own model, compiled at run time (capi_rtc.hip)
+      // a block from the caller's source: every kernel that evaluates constraint rows comes from the run-time module (the merit kernel
+      // there carries them too)
+      const bool user_al = a.al.enabled && a.al.guser;
       if (which == IK_ROLLOUT || which == IK_MERIT || (which == IK_MERIT2 && a.row32m)) return rtc_gen_launch(h, which, a);
+      if (user_al && (which == IK_STATIONARITY || which == IK_DUAL)) return rtc_gen_al_launch(h, which, a);
       if (which == IK_EXPAND) {   // the cost's expansion from the library's kernel (the model kind it sees is not one it steps), then A_k, B_k
-        IlqrGenArgs<T> ac = a;
+        IlqrGenArgs<T> ac = a;    // (with user blocks the AL expansion -- cost and constraint terms, one kernel -- from the run-time module)
         ac.mp.kind = MODEL_LINEAR;
-        const int rc0 = ilqr_generic_launch<T>(h->stream, which, ac);
-        if (rc0) return fail(ALTRO_HIP_ERR_HIP, "iLQR kernel launch failed");
+        if (user_al) {
+          const int rc0 = rtc_gen_al_launch(h, which, ac);
+          if (rc0) return rc0;
+        } else {
+          const int rc0 = ilqr_generic_launch<T>(h->stream, which, ac);
+          if (rc0) return fail(ALTRO_HIP_ERR_HIP, "iLQR kernel launch failed");
+        }
         return (a.mode & EXPAND_DYN) ? rtc_gen_launch(h, which, a) : 0;
       }
     }
@@ -1180,10 +1199,26 @@ int altro_hip_add_user_constraint(altro_hip_batch* h, int k_first, int k_last, i
   // from the source given to altro_hip_set_model_source (altro_user_constraint / altro_user_constraint_jacobian)
   int rc = loop_entry(h);
   if (rc) return rc;
-  if (h->plan != ALTRO_HIP_PLAN_LANE || h->model.kind != MODEL_USER || !h->rtc_has_constraints)
+  const bool gen = h->plan == ALTRO_HIP_PLAN_GENERIC;
+  if ((h->plan != ALTRO_HIP_PLAN_LANE && !gen) || h->model.kind != MODEL_USER || !h->rtc_has_constraints)
     return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_set_model_source must come first, with a source that defines "
-                                       "altro_user_constraint and altro_user_constraint_jacobian (plan LANE)");
+                                       "altro_user_constraint and altro_user_constraint_jacobian (plans LANE and GENERIC / MFMA32)");
   if (id < 0) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "constraint id %d", id);
+  if (gen) {   // plan GENERIC stages the user blocks' values and Jacobians of a knot point in LDS (kernels/ilqr_generic.hip: GEN_USER_MAXROWS)
+    if (p < 1 || p > GEN_USER_MAXROWS)
+      return fail(ALTRO_HIP_ERR_UNSUPPORTED, "a constraint block from source has 1 .. %d rows on plan GENERIC (GEN_USER_MAXROWS; got %d)",
+                  GEN_USER_MAXROWS, p);
+    for (int k = std::max(k_first, 0); k <= std::min(k_last, h->N); ++k) {
+      int rows = p;
+      for (int j = 0; j < h->al_knots[k].ncon; ++j) {
+        const AlDef& d0 = h->al_defs[h->al_knots[k].def[j]];
+        if (d0.user) rows += d0.p;
+      }
+      if (rows > GEN_USER_MAXROWS)
+        return fail(ALTRO_HIP_ERR_UNSUPPORTED, "at most %d rows of constraint blocks from source per knot point on plan GENERIC "
+                                               "(GEN_USER_MAXROWS; k = %d would have %d)", GEN_USER_MAXROWS, k, rows);
+    }
+  }
   std::vector<double> G((size_t)std::max(p, 0) * (h->n + h->m), 0.0), g((size_t)std::max(p, 0), 0.0);   // placeholders: never read
   rc = altro_hip_add_linear_constraint(h, k_first, k_last, cone, p, G.data(), g.data(), 0);
   if (rc < 0) return rc;

@@ -144,6 +144,7 @@ struct altro_hip_batch {
   bool al_all_gsel = false;              // plan GENERIC: every block is bound-type (the Hessian blocks change on their diagonals only)
   double* g_stat_part = nullptr; size_t g_stat_part_bytes = 0;   // row32_stationarity_kernel's per-chunk maxima (capi_ilqr.hip: gen_run)
   int* al_d_gsel = nullptr;              // plan GENERIC: AlTable::gsel (bound-type blocks)
+  int* al_d_guser = nullptr;             // plan GENERIC: AlTable::guser (blocks from the caller's source), null without such a block
   bool al_row32_ok = false;              // every block fits kernels/ilqr_row32.hip (row-wise cone, <= 32 rows)
   int al_max_ncon = 0;                   // most blocks (plan MFMA16: slots, al_types.h) any knot point has
   int al_G_count = 0;                        // elements of the device G pool
@@ -493,6 +494,7 @@ template <typename T>
 int rtc_launch(altro_hip_batch* h, int which, const IlqrArgs<T>& a);
 int rtc_tile_launch(altro_hip_batch* h, int which, const IlqrWaveArgs<double>& a);   // plan MFMA16: the model kernels of a caller's source
 int rtc_gen_launch(altro_hip_batch* h, int which, const IlqrGenArgs<double>& a);     // plans GENERIC / MFMA32: likewise
+int rtc_gen_al_launch(altro_hip_batch* h, int which, const IlqrGenArgs<double>& a);  // ... and their constraint kernels (user blocks)
 
 // the sweep launchers (capi_tvlqr.hip), also used by the iLQR loop
 int replan_empty_handle(altro_hip_batch* h, int plan);   // capi_core.hip

@@ -339,11 +339,16 @@ static int rtc_tile_module_for(altro_hip_batch* h, int al, int dense, RtcTileMod
 // memory (row_ok): a Jacobian the compiler cannot keep in registers -- a dense one of many states, a loop it cannot unroll -- makes
 // that formulation spill, and a spilling wave of that kernel waits for its reloads behind the prefetch (3.4 x slower
 // than without); the wave-per-problem kernels above are the form for such models.
-enum RtcGenKernel { RTG_ROLLOUT = 0, RTG_EXPAND_DYN, RTG_MERIT, RTG_NUM, RTG_ROW_MERIT = RTG_NUM, RTG_ROW_MERIT2, RTG_ROW_EXPAND_DYN, RTG_NUM_ROW };
+// A source that defines altro_user_constraint / _jacobian also gets the kernels that evaluate constraint blocks (ALTRO_HIP_USER_CONSTRAINTS:
+// kernels/ilqr_generic.hip, GEN_USER_BLOCKS): the merit kernel above then carries them, and three more are instantiated -- the
+// stationarity / feasibility walk, the AL expansion (the cost's part included: it is one kernel) and the dual update.
+enum RtcGenKernel { RTG_ROLLOUT = 0, RTG_EXPAND_DYN, RTG_MERIT, RTG_NUM, RTG_ROW_MERIT = RTG_NUM, RTG_ROW_MERIT2, RTG_ROW_EXPAND_DYN, RTG_NUM_ROW,
+                    RTG_STATIONARITY = RTG_NUM_ROW, RTG_EXPAND_AL, RTG_DUAL, RTG_NUM_ALL };
 struct RtcGenModule {
   hipModule_t module = nullptr;
-  hipFunction_t fn[RTG_NUM_ROW] = {};
+  hipFunction_t fn[RTG_NUM_ALL] = {};
   bool row_ok = false;
+  bool al = false;   // the source's constraint blocks: RTG_STATIONARITY .. RTG_DUAL exist
 };
 constexpr int RTG_ROW_SCRATCH_MAX = 256;   // bytes of private segment per lane a row-layout kernel may use and still be chosen
 static int rtc_gen_module_for(altro_hip_batch* h, RtcGenModule** out) {
@@ -360,8 +365,14 @@ static int rtc_gen_module_for(altro_hip_batch* h, RtcGenModule** out) {
   if (rc) return rc;
   const std::string nm = std::to_string(h->n) + ", " + std::to_string(h->m);
   const bool row_shape = tile32_supported(h->n, h->m);
-  const int nk = row_shape ? (int)RTG_NUM_ROW : (int)RTG_NUM;
-  std::string exprs[RTG_NUM_ROW];
+  const bool al = source_has_constraints(user_src);
+  std::vector<int> ks = {RTG_ROLLOUT, RTG_EXPAND_DYN, RTG_MERIT};   // the kernels this module instantiates
+  if (row_shape) ks.insert(ks.end(), {RTG_ROW_MERIT, RTG_ROW_MERIT2, RTG_ROW_EXPAND_DYN});
+  if (al) ks.insert(ks.end(), {RTG_STATIONARITY, RTG_EXPAND_AL, RTG_DUAL});
+  std::string exprs[RTG_NUM_ALL];
+  exprs[RTG_STATIONARITY] = "altro_hip::generic_stationarity_kernel<double>";
+  exprs[RTG_EXPAND_AL] = "altro_hip::generic_expand_al_kernel<double>";
+  exprs[RTG_DUAL] = "altro_hip::generic_dual_update_kernel<double>";
   exprs[RTG_ROW_MERIT] = "altro_hip::row32_merit_kernel<double, " + nm + ", 1, false, altro_hip::MODEL_USER>";
   exprs[RTG_ROW_MERIT2] = "altro_hip::row32_merit_kernel<double, " + nm + ", 1, true, altro_hip::MODEL_USER>";
   exprs[RTG_ROW_EXPAND_DYN] = "altro_hip::row32_expand_dyn_kernel<double, " + nm + ", altro_hip::MODEL_USER>";
@@ -369,11 +380,12 @@ static int rtc_gen_module_for(altro_hip_batch* h, RtcGenModule** out) {
   exprs[RTG_EXPAND_DYN] = "altro_hip::generic_model_expand_dyn_kernel<double, altro_hip::MODEL_USER, " + nm + ">";
   exprs[RTG_MERIT] = "altro_hip::generic_merit_kernel<double, false, altro_hip::MODEL_USER, " + nm + ">";
   std::string src = "#define ALTRO_HIP_USER_MODEL 1\n";
+  if (al) src += "#define ALTRO_HIP_USER_CONSTRAINTS 1\n#define ALTRO_HIP_GEN_UN " + std::to_string(h->n) + "\n#define ALTRO_HIP_GEN_UM " + std::to_string(h->m) + "\n";
   src += "#include \"rtc_compat.h\"\n#include \"fp_contract.h\"\nALTRO_FP_REGION_ON\n";
   src += "#line 1 \"user_model\"\n" + user_src + "\nALTRO_FP_REGION_END\n#include \"kernels/ilqr_generic.hip\"\n";
   if (row_shape) src += "#include \"kernels/ilqr_row32.hip\"\n";
   src += "namespace altro_hip {\n";
-  for (int w = 0; w < nk; ++w) {
+  for (int w : ks) {
     std::string e = exprs[w];
     for (size_t p; (p = e.find("altro_hip::")) != std::string::npos;) e.erase(p, std::strlen("altro_hip::"));
     src += "template __global__ void " + e + "(IlqrGenArgs<double>);\n";
@@ -389,7 +401,7 @@ static int rtc_gen_module_for(altro_hip_batch* h, RtcGenModule** out) {
   hiprtcProgram prog = nullptr;
   hiprtcResult rr = R->CreateProgram(&prog, src.c_str(), "altro_user_generic_model.hip", 14, hdr_src, hdr_name);
   if (rr != HIPRTC_SUCCESS) return fail(ALTRO_HIP_ERR_HIP, "hiprtcCreateProgram: %s", R->GetErrorString(rr));
-  for (int w = 0; w < nk; ++w) R->AddNameExpression(prog, exprs[w].c_str());
+  for (int w : ks) R->AddNameExpression(prog, exprs[w].c_str());
   hipDeviceProp_t prop;
   std::string arch = "--offload-arch=gfx950";
   if (hipGetDeviceProperties(&prop, h->device) == hipSuccess) arch = std::string("--offload-arch=") + prop.gcnArchName;
@@ -412,12 +424,13 @@ static int rtc_gen_module_for(altro_hip_batch* h, RtcGenModule** out) {
   std::vector<char> code(cs);
   R->GetCode(prog, code.data());
   RtcGenModule* m = new RtcGenModule();
+  m->al = al;
   if (const hipError_t le = hipModuleLoadData(&m->module, code.data()); le != hipSuccess) {
     R->DestroyProgram(&prog);
     delete m;
     return fail(ALTRO_HIP_ERR_HIP, "hipModuleLoadData of the compiled model failed: %s", hipGetErrorString(le));
   }
-  for (int w = 0; w < nk; ++w) {
+  for (int w : ks) {
     const char* lowered = nullptr;
     if (R->GetLoweredName(prog, exprs[w].c_str(), &lowered) != HIPRTC_SUCCESS || !lowered ||
         hipModuleGetFunction(&m->fn[w], m->module, lowered) != hipSuccess) {
@@ -468,6 +481,29 @@ int rtc_gen_launch(altro_hip_batch* h, int which, const IlqrGenArgs<double>& a) 
       if (row) return go(RTG_ROW_MERIT, (unsigned)((a.batch + 1) / 2), 0);
       return go(RTG_MERIT, (unsigned)a.batch, a.al.enabled ? (unsigned)(GEN_AL_JV * sizeof(double)) : 0u);
     default: return fail(ALTRO_HIP_ERR_UNSUPPORTED, "operation %d has no run-time compiled kernel on this plan", which);
+  }
+}
+// The kernels of plan GENERIC's loop that evaluate constraint blocks, from the handle's run-time module: a handle with a block from the
+// source (altro_hip_add_user_constraint).  IK_EXPAND is the whole AL expansion (the cost's terms included); the caller adds the dynamics'.
+int rtc_gen_al_launch(altro_hip_batch* h, int which, const IlqrGenArgs<double>& a) {
+  if (h->rtc_source.empty()) return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_set_model_source has not been called");
+  RtcGenModule* mod = nullptr;
+  int rc = rtc_gen_module_for(h, &mod);
+  if (rc) return rc;
+  if (!mod->al) return fail(ALTRO_HIP_ERR_NOT_SET, "the model source defines no constraint blocks (altro_user_constraint / _jacobian)");
+  IlqrGenArgs<double> args = a;
+  void* params[] = {&args};
+  auto go = [&](int w, unsigned gx) -> int {   // (the grids of ilqr_launch_generic.hip; no dynamic LDS)
+    const hipError_t e = hipModuleLaunchKernel(mod->fn[w], gx, 1, 1, 64, 1, 1, 0, h->stream, params, nullptr);
+    if (e != hipSuccess) return fail(ALTRO_HIP_ERR_HIP, "launch of the run-time compiled constraint kernel %d of plan GENERIC's loop failed: %s", w, hipGetErrorString(e));
+    return 0;
+  };
+  const unsigned waves_k = (unsigned)((int64_t)a.batch * (a.N + 1));   // one wave per (problem, knot point)
+  switch (which) {
+    case IK_STATIONARITY: return go(RTG_STATIONARITY, (unsigned)a.batch);
+    case IK_EXPAND: return go(RTG_EXPAND_AL, waves_k);
+    case IK_DUAL: return go(RTG_DUAL, waves_k);
+    default: return fail(ALTRO_HIP_ERR_UNSUPPORTED, "operation %d has no run-time compiled constraint kernel on this plan", which);
   }
 }
 
@@ -556,20 +592,26 @@ int altro_hip_set_model_source(altro_hip_batch* h, const char* source, float tim
   if (!source) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "source == NULL");
   if (!(timestep > 0.0f)) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "time step must be positive (ErrorCodes::TimestepNotPositive)");
   HIP_TRY(hipSetDevice(h->device));
+  const std::string src(source);
+  const bool c_val = defines_function(src, "altro_user_constraint"), c_jac = defines_function(src, "altro_user_constraint_jacobian");
+  if (c_val != c_jac)
+    return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "the model source defines %s but not %s: constraint blocks need both",
+                c_val ? "altro_user_constraint" : "altro_user_constraint_jacobian", c_val ? "altro_user_constraint_jacobian" : "altro_user_constraint");
+  // nonlinear constraint blocks from source are plans LANE's and GENERIC's: an ALTRO_HIP_PLAN_AUTO handle that rides the padded tile only
+  // because of its shape / batch size moves to one of them while it is still empty -- LANE for n <= 6, else GENERIC
+  if (h->plan == ALTRO_HIP_PLAN_MFMA16 && h->auto_plan && c_val &&
+      (rc = replan_empty_handle(h, lane_supported(h->n, h->m) ? ALTRO_HIP_PLAN_LANE : ALTRO_HIP_PLAN_GENERIC))) return rc;
   if (h->plan == ALTRO_HIP_PLAN_GENERIC) {   // plans GENERIC / MFMA32: the caller's model inside that plan's loop kernels (any n, m <= 32)
     if (h->ragged) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "device models need uniform dimensions");
     if (h->dtype != ALTRO_HIP_F64) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "device models on plans GENERIC / MFMA32 run on fp64 handles");
     if (h->n > 32 || h->m > 32)
       return fail(ALTRO_HIP_ERR_UNSUPPORTED, "run-time compiled models on plan GENERIC take n, m <= 32 (got %d, %d)", h->n, h->m);
-    const std::string gsrc(source);
-    if (defines_function(gsrc, "altro_user_constraint") || defines_function(gsrc, "altro_user_constraint_jacobian"))
-      return fail(ALTRO_HIP_ERR_UNSUPPORTED, "nonlinear constraint blocks from source are a plan LANE feature; this plan takes the model's two "
-                                             "functions and linear blocks (altro_hip_add_linear_constraint)");
+    const std::string& gsrc = src;
     h->rtc_source = gsrc;
     h->model = ModelParams{MODEL_USER, timestep, 0, 2.7, 1.5};
     RtcGenModule* gm = nullptr;   // compile now: a source that does not build must fail HERE, with the compiler's log
     if ((rc = rtc_gen_module_for(h, &gm))) { h->rtc_source.clear(); h->model = ModelParams{MODEL_LINEAR, 0.0f, 0, 2.7, 1.5}; return rc; }
-    h->model_set = true; h->rtc_has_constraints = false;
+    h->model_set = true; h->rtc_has_constraints = c_val && c_jac;
     h->rtc_row32_ok = gm->row_ok;
     HIP_TRY(hipMemsetAsync(h->g_arr[G_f], 0, (size_t)h->batch * h->g_bstride[G_f] * h->esz, h->stream));
     HIP_TRY(hipMemsetAsync(h->g_arr[G_A], 0, (size_t)h->batch * h->g_bstride[G_A] * h->esz, h->stream));
@@ -579,20 +621,13 @@ int altro_hip_set_model_source(altro_hip_batch* h, const char* source, float tim
   }
   if (h->plan != ALTRO_HIP_PLAN_LANE && h->plan != ALTRO_HIP_PLAN_MFMA16)
     return fail(ALTRO_HIP_ERR_UNSUPPORTED, "unknown plan %d", h->plan);
-  if (h->plan == ALTRO_HIP_PLAN_MFMA16 && h->auto_plan && lane_supported(h->n, h->m)) {
-    // nonlinear constraint blocks from source are plan LANE's: an ALTRO_HIP_PLAN_AUTO handle that rides the padded tile only because
-    // of its batch size moves there while it is still empty
-    const std::string probe(source);
-    if ((defines_function(probe, "altro_user_constraint") || defines_function(probe, "altro_user_constraint_jacobian")) &&
-        (rc = replan_empty_handle(h, ALTRO_HIP_PLAN_LANE))) return rc;
-  }
   if (h->plan == ALTRO_HIP_PLAN_MFMA16) {   // the tile plan's row-layout kernels around the caller's model (kernels/ilqr_tile_model.hip)
     if (h->dtype != ALTRO_HIP_F64)
       return fail(ALTRO_HIP_ERR_UNSUPPORTED, "device models on plan MFMA16 run on fp64 records (create the handle with ALTRO_HIP_F64)");
-    const std::string tsrc(source);
-    if (defines_function(tsrc, "altro_user_constraint") || defines_function(tsrc, "altro_user_constraint_jacobian"))
-      return fail(ALTRO_HIP_ERR_UNSUPPORTED, "nonlinear constraint blocks from source are a plan LANE feature; plan MFMA16 takes the model's "
-                                             "two functions and linear blocks (altro_hip_add_linear_constraint)");
+    const std::string& tsrc = src;
+    if (c_val || c_jac)
+      return fail(ALTRO_HIP_ERR_UNSUPPORTED, "nonlinear constraint blocks from source run on plan GENERIC (ALTRO_HIP_PLAN_GENERIC, any n, m <= 32) "
+                                             "and plan LANE; plan MFMA16 takes the model's two functions and linear blocks (altro_hip_add_linear_constraint)");
     h->rtc_source = tsrc;
     h->model = ModelParams{MODEL_USER, timestep, 0, 2.7, 1.5};
     RtcTileModule* tm = nullptr;   // compile now: a source that does not build must fail HERE, with the compiler's log
@@ -603,11 +638,6 @@ int altro_hip_set_model_source(altro_hip_batch* h, const char* source, float tim
     return 0;
   }
   RtcModule* m = nullptr;
-  const std::string src(source);
-  const bool c_val = defines_function(src, "altro_user_constraint"), c_jac = defines_function(src, "altro_user_constraint_jacobian");
-  if (c_val != c_jac)
-    return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "the model source defines %s but not %s: constraint blocks need both",
-                c_val ? "altro_user_constraint" : "altro_user_constraint_jacobian", c_val ? "altro_user_constraint_jacobian" : "altro_user_constraint");
   const int ck = h->cost_dense ? 1 : 0;
   if ((rc = rtc_module_for(h, src, ck, &m))) return rc;   // (altro_hip_last_error has the compiler's log)
   h->rtc = m; h->rtc_ck = ck; h->rtc_source = src;

@@ -111,6 +111,9 @@ int SolveRun::configure(const altro_hip_solve_options* opts) {
   if (opts) o = *opts;
   else altro_hip_default_solve_options(&o);
   h->forms = forms0 | o.forms;
+  // the constraint tables (and the flags derived from them: al_row32_ok, al_all_gsel, read below) describe the blocks as they are NOW:
+  // a block added since the last solve must not leave this one choosing kernels for the old set
+  if (int rc = al_upload(h)) return rc;
   la.prob = h->i_prob; la.alpha = h->i_alpha; la.active = h->i_active; la.phi = h->i_phi; la.dphi = h->i_dphi;
   la.counters = h->i_counters; la.batch = h->batch; la.iter = 0; la.iterations_max = o.iterations_max;
   la.tol_stationarity = o.tol_stationarity; la.tol_meritfun_gradient = o.tol_meritfun_gradient;

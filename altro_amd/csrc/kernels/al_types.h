@@ -27,6 +27,10 @@ constexpr int GEN_MAXC = 8;     // constraint blocks per knot point on plan GENE
 constexpr int GEN_MAXSOC = 32;  // rows per second-order-cone block on plan GENERIC (one lane per row; cones.cpp:13-123 takes any dimension)
 constexpr int GEN_MAXP = 64;    // rows per zero / identity / orthant block on plan GENERIC: one lane each, so up to n + m = 64
 constexpr int GEN_MAXDEF = 64;  // distinct blocks per handle on plan GENERIC
+// Blocks from the caller's source on plan GENERIC (altro_hip_add_user_constraint; kernels/ilqr_generic.hip, GEN_USER_BLOCKS): their
+// values and Jacobians are staged in LDS once per knot point, GEN_USER_MAXROWS rows of them at most -- the cap of one block and of all
+// user blocks of a knot point together
+constexpr int GEN_USER_MAXROWS = 32;
 
 enum { CONE_EQUALITY = 0, CONE_IDENTITY = 1, CONE_INEQUALITY = 2, CONE_SOC = 3 };   // typedefs.hpp:29-34
 
@@ -81,6 +85,9 @@ struct AlTable {
   // term of such a block is diagonal), [1 + i] = +(idx + 1) / -(idx + 1) for row i = +e_idx / -e_idx (the caller's column order) -- or null
   const int* gsel = nullptr;
   int max_ncon = 0;      // most blocks / slots any knot point has (plan MFMA16: above AL_MAXC the merit kernel's wide instantiation runs)
+  // plan GENERIC: per block definition the caller's constraint id + 1 (AlDef::user), 0 for c = G [x;u] - g -- or null when the handle
+  // has no such block.  Read only by the kernels compiled around a source that defines them (kernels/ilqr_generic.hip: GEN_USER_BLOCKS).
+  const int* guser = nullptr;
 };
 #define ALTRO_CONST_AS __attribute__((address_space(4)))
 // table entry and dual-row shift for knot point k

@@ -144,6 +144,62 @@ __device__ __forceinline__ const AlKnotBig ALTRO_CONST_AS& gen_knot(const AlTabl
   zshift = u ? k * t.rows_per_knot : 0;
   return *(const AlKnotBig ALTRO_CONST_AS*)(t.big + (u ? 0 : k));
 }
+
+// ---- constraint blocks from the caller's source (altro_hip_add_user_constraint): only in the unit hiprtc compiles around a source that
+// defines altro_user_constraint / _jacobian (capi_rtc.hip: rtc_gen_module_for, which also defines the handle's ALTRO_HIP_GEN_UN / _UM).
+// Lane 0 evaluates the caller's two functions ONCE per knot point and user block (a 13 x 17 Jacobian in every lane's registers would
+// spill) into one LDS image per knot point:
+//   [x; u] (UN + UM, u = 0 at the terminal knot point) | c of every user block (GEN_USER_MAXROWS) | their Jacobians, block after block,
+//   each p x (UN + UM) column-major (GEN_USER_MAXROWS x (UN + UM) in all)
+// -- (UN + UM + 32 + 32 (UN + UM)) x 8 bytes: 4.7 KB at (13, 4), 17.2 KB at (32, 32).  Every block of the knot point keeps its image
+// until the next knot point is staged, so value(r), gen_al_col and the expansion's Gauss-Newton / SOC terms read a user block's image
+// where they read G for a linear one: the same arithmetic on the caller's c and dc/d[x;u] (knotpoint_data.cpp:489-567).
+#if defined(ALTRO_HIP_USER_MODEL) && defined(ALTRO_HIP_USER_CONSTRAINTS) && defined(ALTRO_HIP_GEN_UN) && defined(ALTRO_HIP_GEN_UM)
+#define GEN_USER_BLOCKS 1
+constexpr int GEN_UW = ALTRO_HIP_GEN_UN + ALTRO_HIP_GEN_UM;
+constexpr int GEN_UIMG_C = GEN_UW, GEN_UIMG_J = GEN_UW + GEN_USER_MAXROWS;   // offsets of c and of the Jacobians in the image
+template <typename T>
+__device__ __forceinline__ T* gen_uimg() {
+  __shared__ T img[GEN_UW + GEN_USER_MAXROWS + GEN_USER_MAXROWS * GEN_UW];
+  return img;
+}
+template <typename T>
+__device__ __forceinline__ int gen_uid(const AlTable<T>& t, int def) {   // the block definition's caller id + 1, or 0
+  return t.guser ? ((const int ALTRO_CONST_AS*)t.guser)[def] : 0;
+}
+// the knot point's image (all lanes; barriers inside when the knot point has a user block -- the table says so, wave-uniformly)
+template <typename T>
+__device__ __forceinline__ void gen_user_stage(const AlTable<T>& t, const AlKnotBig ALTRO_CONST_AS& kn, int n, int m, const double* xs,
+                                               const double* us, bool terminal, int lane) {
+  bool any = false;
+  for (int c = 0; c < kn.ncon; ++c) any = any || gen_uid<T>(t, kn.def[c]) != 0;
+  if (!any) return;
+  T* const img = gen_uimg<T>();
+  if (lane < ALTRO_HIP_GEN_UN) img[lane] = lane < n ? (T)xs[lane] : T(0);
+  if (lane < ALTRO_HIP_GEN_UM) img[ALTRO_HIP_GEN_UN + lane] = (!terminal && lane < m) ? (T)us[lane] : T(0);
+  __syncthreads();
+  if (lane == 0) {
+    int ro = 0;
+    for (int c = 0; c < kn.ncon; ++c) {
+      const int uid = gen_uid<T>(t, kn.def[c]);
+      if (!uid) continue;
+      altro_user_constraint<T>(uid - 1, img, img + ALTRO_HIP_GEN_UN, img + GEN_UIMG_C + ro);
+      altro_user_constraint_jacobian<T>(uid - 1, img, img + ALTRO_HIP_GEN_UN, img + GEN_UIMG_J + ro * GEN_UW);
+      ro += kn.p[c];
+    }
+  }
+  __syncthreads();
+}
+// block c's Jacobian: its image for a user block (ro: the user rows of the blocks before it, advanced past this one), else G
+template <typename T>
+__device__ __forceinline__ const T* gen_block_G(const AlTable<T>& t, const AlKnotBig ALTRO_CONST_AS& kn, int c, int& ro) {
+  if (!gen_uid<T>(t, kn.def[c])) return t.G + kn.G_off[c];
+  const T* J = gen_uimg<T>() + GEN_UIMG_J + ro * GEN_UW;
+  ro += kn.p[c];
+  return J;
+}
+#endif
+
 template <typename T>
 __device__ __forceinline__ void gen_al_rows(const AlTable<T>& t, int k, int b, int64_t B, int n, int m, const double* xs, const double* us,
                                             bool terminal, double rho_est, int lane, double* jv, double* jd, double* Jm, double* Hm,
@@ -152,9 +208,18 @@ __device__ __forceinline__ void gen_al_rows(const AlTable<T>& t, int k, int b, i
   const AlKnotBig ALTRO_CONST_AS& kn = gen_knot<T>(t, k, zshift);
   const int i = lane;
   const int ncon = kn.ncon;
+#ifdef GEN_USER_BLOCKS
+  gen_user_stage<T>(t, kn, n, m, xs, us, terminal, lane);
+  int ro = 0;
+#endif
   for (int c = 0; c < ncon; ++c) {
     const int p = kn.p[c], cone = kn.cone[c];
+#ifdef GEN_USER_BLOCKS
+    const T* uc = gen_uid<T>(t, kn.def[c]) ? gen_uimg<T>() + GEN_UIMG_C + ro : nullptr;   // a user block's values (before ro moves on)
+    const T* G = gen_block_G<T>(t, kn, c, ro);
+#else
     const T* G = t.G + kn.G_off[c];
+#endif
     jv[c * GEN_MAXP + i] = 0.0;
     if (jd) jd[c * GEN_MAXP + i] = 0.0;
     if (Jm && i < AL_MAXSOC * AL_MAXSOC) { Jm[c * 16 + i] = 0.0; Hm[c * 16 + i] = 0.0; }
@@ -163,6 +228,10 @@ __device__ __forceinline__ void gen_al_rows(const AlTable<T>& t, int k, int b, i
     const bool bsel = sd && sd[0];
     auto value = [&](int r) -> double {
       double s = 0.0;
+#ifdef GEN_USER_BLOCKS
+      if (uc) s = (double)uc[r];   // (g is zero for such a block)
+      else
+#endif
       if (bsel) {
         const int se = sd[1 + r], e = (se < 0 ? -se : se) - 1;
         if (e < n) s += (double)G[r + e * p] * xs[e];
@@ -274,9 +343,16 @@ __device__ __forceinline__ double gen_al_col(const AlTable<T>& t, int k, int e, 
   const AlKnotBig ALTRO_CONST_AS& kn = gen_knot<T>(t, k, zshift);
   double s = 0.0;
   const int ncon = kn.ncon;
+#ifdef GEN_USER_BLOCKS
+  int ro = 0;
+#endif
   for (int c = 0; c < ncon; ++c) {
     const int p = kn.p[c];
+#ifdef GEN_USER_BLOCKS
+    const T* G = gen_block_G<T>(t, kn, c, ro);
+#else
     const T* G = t.G + kn.G_off[c];
+#endif
     const int* sd = t.gsel ? t.gsel + (int64_t)kn.def[c] * (1 + GEN_MAXP) : nullptr;
     if (sd && sd[0]) {   // bound-type: the rows that select column e (the others would add exact zeros)
       for (int i = 0; i < p; ++i)
@@ -677,9 +753,16 @@ __global__ __launch_bounds__(64) void generic_expand_al_kernel(IlqrGenArgs<T> a)
       if (r < n && cc >= n) continue;             // the lux^T block is not stored
       double v = r < n ? (double)Qk[r + cc * n] : (cc < n ? (double)Hk[(r - n) + cc * m] : (double)Rk[(r - n) + (cc - n) * m]);
       double s = 0.0;
+#ifdef GEN_USER_BLOCKS
+      int ro = 0;
+#endif
       for (int cidx = 0; cidx < kn.ncon; ++cidx) {
         const int p = kn.p[cidx];
+#ifdef GEN_USER_BLOCKS
+        const T* G = gen_block_G<T>(a.al, kn, cidx, ro);
+#else
         const T* G = a.al.G + kn.G_off[cidx];
+#endif
         const double* Jc = Jm + cidx * 16;
         const int* sd = a.al.gsel ? a.al.gsel + (int64_t)kn.def[cidx] * (1 + GEN_MAXP) : nullptr;
         if (sd && sd[0]) {

@@ -244,7 +244,10 @@ int altro_hip_set_model(altro_hip_batch* h, int model, float timestep, int bicyc
  * A, B), as in the reference's own test models (test/test_utils.cpp:84-132).  No system headers: the HIP device API and
  * the math functions (sin, cos, sincos, sqrt, ...) are built in.  A source that does not compile gives
  * ALTRO_HIP_ERR_BAD_ARGUMENT with the compiler's log in altro_hip_last_error().  Whole solves of such a handle run on the
- * launch-sequenced loop.                                                                                              */
+ * launch-sequenced loop.  Plans GENERIC / MFMA32 (fp64, uniform n, m <= 32) and MFMA16 take the model the same way.  A source that
+ * also defines the constraint pair of altro_hip_add_user_constraint is taken by plans LANE and GENERIC / MFMA32 (an empty
+ * ALTRO_HIP_PLAN_AUTO handle of the tile moves to LANE for n <= 6, else to GENERIC); plan MFMA16 refuses it
+ * (ALTRO_HIP_ERR_UNSUPPORTED), and a source that defines only one of the pair is ALTRO_HIP_ERR_BAD_ARGUMENT.               */
 int altro_hip_set_model_source(altro_hip_batch* h, const char* source, float timestep);
 /* Plans GENERIC / MFMA32: 1 when the handle's device model (compiled in, or the caller's source) runs the loop's ROW-LAYOUT model kernels
  * (kernels/ilqr_row32.hip: two problems per wave, every lane evaluates the model -- plan MFMA32's shapes), 0 when it runs the
@@ -258,7 +261,10 @@ int altro_hip_model_row_layout(const altro_hip_batch* h);
  *     template <typename T> __device__ void altro_user_constraint_jacobian(int id, const T* x, const T* u, T* J);   // p x (n+m)
  * (J column-major; u is zero at the terminal knot point), this registers block `id` of them -- p rows in `cone` at knot
  * points k_first..k_last -- next to the linear blocks; the AL terms treat it as the reference treats any constraint
- * (knotpoint_data.cpp:489-613: projected duals, Gauss-Newton in the Jacobian).  Returns the block id or a negative error. */
+ * (knotpoint_data.cpp:489-613: projected duals, Gauss-Newton in the Jacobian).  Plans LANE (p <= 8, SOC p <= 4, two blocks per
+ * knot point) and GENERIC / MFMA32 (p <= 32 in any cone, 32 such rows per knot point; the handle then runs the wave-per-problem
+ * loop kernels).  ALTRO_HIP_ERR_NOT_SET when the handle's model is not a source that defines the pair.  Returns the block id or a
+ * negative error. */
 int altro_hip_add_user_constraint(altro_hip_batch* h, int k_first, int k_last, int cone, int p, int id);
 /* ALTROSolver::SetLQRCost (altro_solver.cpp:138-172): Qd, xref [batch][N+1][n]; Rd, uref [batch][N][m];
  * with k_stride_zero Qd/xref hold {running, terminal} and Rd/uref one knot point.                   */
@@ -303,7 +309,8 @@ int altro_hip_get_expansion(altro_hip_batch* h, double* A, double* B, double* lx
  * names it, never a truncation):
  *   plan GENERIC       (and plan MFMA32, which shares its loop) 8 blocks per knot point, p <= 64 rows per block, a second-order cone
  *                      p <= 32 (one lane per row; the projection's Jacobian and curvature applied from their closed forms), 64 blocks
- *                      per handle;
+ *                      per handle; blocks from source (altro_hip_add_user_constraint) count among these and have p <= 32 rows each,
+ *                      32 rows per knot point in all (GEN_USER_MAXROWS: their values and Jacobians are staged in LDS);
  *   plan MFMA16        (the (12, 4) tile, fp64) 6 SLOTS of 8 rows per knot point -- a block in the zero / identity / orthant cones
  *                      takes ceil(p / 8) consecutive slots (p <= 48: those cones project row by row, so the host lays the rows out;
  *                      duals stay [p] per block), a second-order cone (p <= 4) one -- and 32 slots per handle: e.g. an input box

@@ -98,6 +98,13 @@ class BatchSolver {
     if (id < 0) Check(id);
     return id;
   }
+  // ALTROSolver::SetConstraint with a general callback pair: block `id` of the altro_user_constraint / _jacobian pair in the source
+  // given to SetModelSource, p rows in `cone` at knot points k_start .. k_stop (plans LANE and GENERIC / MFMA32); returns the block id
+  int SetUserConstraint(int k_start, int k_stop, Cone cone, int p, int id) {
+    const int bid = altro_hip_add_user_constraint(h_, k_start, k_stop, static_cast<int>(cone), p, id);
+    if (bid < 0) Check(bid);
+    return bid;
+  }
   void ClearConstraints() { Check(altro_hip_clear_constraints(h_)); }
   void ResetDuals(double penalty = 1.0) { Check(altro_hip_reset_duals(h_, penalty)); }
 
