@@ -12,6 +12,17 @@ namespace altro_hip {
 namespace capi {   // (external linkage: capi_solve.hip drives these)
 
 // ---- iLQR loop (plan LANE) ---------------------------------------------------------------------------
+// Is row r of block d's G (as the caller gave it: p x w, column-major) +e_idx or -e_idx?  idx and sign are those of the row's only
+// nonzero, whatever its size (the tables record them for a multiple of e_idx too, which is no bound row); idx < 0: not exactly one.
+static bool al_bound_row(const altro_hip_batch* h, const AlDef& d, int r, int w, int& idx, int& sign) {
+  int nz = 0; bool unit = true;
+  for (int e = 0; e < w; ++e) {
+    const double v = h->al_G[(size_t)d.G_off + r + (size_t)e * d.p];
+    if (v != 0.0) { ++nz; idx = e; sign = v > 0 ? 1 : -1; unit = unit && (v == 1.0 || v == -1.0); }
+  }
+  if (nz != 1) idx = -1;
+  return unit && nz == 1;
+}
 // (re)build the device tables of the constraint blocks; duals restart from zero when the structure changes
 template <typename T>
 int al_upload_typed(altro_hip_batch* h) {
@@ -110,16 +121,10 @@ int al_upload_typed(altro_hip_batch* h) {
         kn.user[ns] = d.user;
         kn.Gp_off[ns] = tile ? (slot_base[bk.def[j]] + sl) * AL_GP_DEF : 0;
         // bound-type slot: every row of G is +-e_idx
-        const int w = h->n + h->m;
         bool sel = d.cone != CONE_SOC;
-        for (int r = 0; r < ps && sel; ++r) {
-          int nz = 0, at = -1;
-          for (int e = 0; e < w; ++e) {
-            const double v = h->al_G[(size_t)d.G_off + (r0 + r) + (size_t)e * d.p];
-            if (v != 0.0) { ++nz; at = e; if (v != 1.0 && v != -1.0) sel = false; }
-          }
-          if (nz != 1) sel = false;
-          else kn.sidx[ns][r] = h->al_G[(size_t)d.G_off + (r0 + r) + (size_t)at * d.p] > 0 ? dev_col(at) + 1 : -(dev_col(at) + 1);
+        for (int r = 0, at, sg; r < ps && sel; ++r) {
+          sel = al_bound_row(h, d, r0 + r, w_log, at, sg);
+          if (at >= 0) kn.sidx[ns][r] = sg * (dev_col(at) + 1);
         }
         kn.sel[ns] = sel ? 1 : 0;
       }
@@ -128,40 +133,32 @@ int al_upload_typed(altro_hip_batch* h) {
     max_ncon = std::max(max_ncon, gen ? bk.ncon : ns);
   }
   h->al_max_ncon = max_ncon;
+  auto upload = [&](void** dst, const void* src, size_t bytes) -> int {   // a host table's copy on the device
+    if (const int rcu = dmalloc(h, dst, bytes)) return rcu;
+    HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+    return 0;
+  };
+  int rc = 0;
   h->al_all_gsel = gen && !h->ragged && !defs.empty();
   if (gen && !h->ragged) {   // plan GENERIC: which blocks are bound-type (AlTable::gsel; the expansion's Gauss-Newton term is then diagonal)
     std::vector<int> gsel(defs.size() * (size_t)(1 + GEN_MAXP), 0);
-    const int wn = h->n + h->m;
     for (size_t i = 0; i < defs.size(); ++i) {
       const AlDef& d = defs[i];
       bool sel = d.cone != CONE_SOC && !d.user && d.p <= GEN_MAXP;
-      for (int r = 0; r < d.p && sel; ++r) {
-        int nz = 0, at = -1;
-        for (int e = 0; e < wn; ++e) {
-          const double v = h->al_G[(size_t)d.G_off + r + (size_t)e * d.p];
-          if (v != 0.0) { ++nz; at = e; if (v != 1.0 && v != -1.0) sel = false; }
-        }
-        if (nz != 1) sel = false;
-        else gsel[i * (size_t)(1 + GEN_MAXP) + 1 + r] = h->al_G[(size_t)d.G_off + r + (size_t)at * d.p] > 0 ? at + 1 : -(at + 1);
+      for (int r = 0, at, sg; r < d.p && sel; ++r) {
+        sel = al_bound_row(h, d, r, w_log, at, sg);
+        if (at >= 0) gsel[i * (size_t)(1 + GEN_MAXP) + 1 + r] = sg * (at + 1);
       }
       gsel[i * (size_t)(1 + GEN_MAXP)] = sel ? 1 : 0;
       if (!sel) h->al_all_gsel = false;
     }
-    if (!gsel.empty()) {
-      int rcg = dmalloc(h, (void**)&h->al_d_gsel, gsel.size() * sizeof(int));
-      if (rcg) return rcg;
-      HIP_TRY(hipMemcpy(h->al_d_gsel, gsel.data(), gsel.size() * sizeof(int), hipMemcpyHostToDevice));
-    }
+    if (!gsel.empty() && (rc = upload((void**)&h->al_d_gsel, gsel.data(), gsel.size() * sizeof(int)))) return rc;
     // blocks from the caller's source (AlTable::guser): only the run-time compiled kernels read the table, and only a handle with
     // such a block has one
     std::vector<int> guser(defs.size(), 0);
     bool any_user = false;
     for (size_t i = 0; i < defs.size(); ++i) { guser[i] = defs[i].user; any_user = any_user || defs[i].user != 0; }
-    if (any_user) {
-      int rcu = dmalloc(h, (void**)&h->al_d_guser, guser.size() * sizeof(int));
-      if (rcu) return rcu;
-      HIP_TRY(hipMemcpy(h->al_d_guser, guser.data(), guser.size() * sizeof(int), hipMemcpyHostToDevice));
-    }
+    if (any_user && (rc = upload((void**)&h->al_d_guser, guser.data(), guser.size() * sizeof(int)))) return rc;
   }
   h->al_row32_ok = true;   // (kernels/ilqr_row32.hip: a lane position per row, the row-wise cones)
   for (const AlDef& d : defs) if (d.cone == CONE_SOC || d.p > 32 || d.user) h->al_row32_ok = false;
@@ -180,23 +177,16 @@ int al_upload_typed(altro_hip_batch* h) {
     h->al_uniform = uni ? 1 : 0;
     h->al_rows_per_knot = r0;
   }
-  int rc = 0;
-  if (gen) {
-    if ((rc = dmalloc(h, (void**)&h->al_d_big, big.size() * sizeof(AlKnotBig)))) return rc;
-    HIP_TRY(hipMemcpy(h->al_d_big, big.data(), big.size() * sizeof(AlKnotBig), hipMemcpyHostToDevice));
-  }
-  if ((rc = dmalloc(h, (void**)&h->al_d_knots, std::max<size_t>(knots.size(), 1) * sizeof(AlKnot)))) return rc;
-  if ((rc = dmalloc(h, &h->al_d_G, G.size() * sizeof(T)))) return rc;
-  if ((rc = dmalloc(h, &h->al_d_g, g.size() * sizeof(T)))) return rc;
-  if ((rc = dmalloc(h, &h->al_d_z, (size_t)rows * B * sizeof(T)))) return rc;
+  if (gen && (rc = upload((void**)&h->al_d_big, big.data(), big.size() * sizeof(AlKnotBig)))) return rc;
+  if ((rc = dmalloc(h, (void**)&h->al_d_knots, std::max<size_t>(knots.size(), 1) * sizeof(AlKnot)))) return rc;   // (plan GENERIC: no entries)
   if (!knots.empty()) HIP_TRY(hipMemcpy(h->al_d_knots, knots.data(), knots.size() * sizeof(AlKnot), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(h->al_d_G, G.data(), G.size() * sizeof(T), hipMemcpyHostToDevice));
+  if ((rc = upload(&h->al_d_G, G.data(), G.size() * sizeof(T)))) return rc;
+  if ((rc = upload(&h->al_d_g, g.data(), g.size() * sizeof(T)))) return rc;
   if (!Gpad.empty()) {
-    if ((rc = dmalloc(h, &h->al_d_Gpad, Gpad.size() * sizeof(T)))) return rc;
-    HIP_TRY(hipMemcpy(h->al_d_Gpad, Gpad.data(), Gpad.size() * sizeof(T), hipMemcpyHostToDevice));
+    if ((rc = upload(&h->al_d_Gpad, Gpad.data(), Gpad.size() * sizeof(T)))) return rc;
     h->al_Gpad_count = (int)Gpad.size();
   }
-  HIP_TRY(hipMemcpy(h->al_d_g, g.data(), g.size() * sizeof(T), hipMemcpyHostToDevice));
+  if ((rc = dmalloc(h, &h->al_d_z, (size_t)rows * B * sizeof(T)))) return rc;
   // (memsets go on the handle's own stream: it is non-blocking, so a null-stream memset would race the kernels)
   HIP_TRY(hipMemsetAsync(h->al_d_z, 0, (size_t)rows * B * sizeof(T), h->stream));
   h->al_knots = big;
@@ -215,12 +205,21 @@ int al_upload(altro_hip_batch* h) {
   return rc;
 }
 
+// The kernels' view of the handle's constraint tables, on every plan: what a plan does not have is null / zero on the handle (al_upload_typed:
+// Gpad is plan MFMA16's; big, gsel and guser are plan GENERIC's), and max_ncon is read by plan MFMA16's launcher alone.
+template <typename T>
+AlTable<T> al_table(const altro_hip_batch* h) {
+  AlTable<T> t;
+  t.knots = h->al_d_knots; t.big = h->al_d_big; t.G = (const T*)h->al_d_G; t.g = (const T*)h->al_d_g; t.z = (T*)h->al_d_z; t.enabled = h->al_defs.empty() ? 0 : 1;
+  t.uniform = h->al_uniform; t.rows_per_knot = h->al_rows_per_knot; t.N = h->N; t.G_count = h->al_G_count; t.Gpad = (const T*)h->al_d_Gpad; t.Gpad_count = h->al_Gpad_count;
+  t.all_sel = h->al_all_sel; t.has_soc = h->al_has_soc; t.gsel = h->al_d_gsel; t.max_ncon = h->al_max_ncon; t.guser = h->al_d_guser;
+  return t;
+}
+
 template <typename T>
 IlqrArgs<T> ilqr_args(altro_hip_batch* h, bool use_alpha, bool use_active, int want_deriv, double alpha_const) {
   IlqrArgs<T> a;
-  a.al.knots = h->al_d_knots; a.al.G = (const T*)h->al_d_G; a.al.g = (const T*)h->al_d_g;
-  a.al.z = (T*)h->al_d_z; a.al.enabled = h->al_defs.empty() ? 0 : 1;
-  a.al.uniform = h->al_uniform; a.al.rows_per_knot = h->al_rows_per_knot; a.al.N = h->N; a.al.G_count = h->al_G_count; a.al.has_soc = h->al_has_soc; a.al.all_sel = h->al_all_sel; a.al.Gpad = (decltype(a.al.Gpad))h->al_d_Gpad; a.al.Gpad_count = h->al_Gpad_count; a.al.max_ncon = h->al_max_ncon;
+  a.al = al_table<T>(h);
   a.mode = EXPAND_GRADIENT | EXPAND_HESSIAN;
   a.in = (T*)h->l_in; a.term = (T*)h->l_term; a.out = (const T*)h->l_out; a.outn = (const T*)h->l_outn;
   a.nom = (T*)h->l_nom; a.cand = (T*)h->l_xuy; a.x0 = (const T*)h->l_x0;
@@ -286,9 +285,7 @@ int ilqr_launch(altro_hip_batch* h, int which, IlqrArgs<T> a) {
 template <typename S>
 int wave_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int want_deriv, double alpha_const, int mode) {
   IlqrWaveArgs<S> a;
-  a.al.knots = h->al_d_knots; a.al.G = (const S*)h->al_d_G; a.al.g = (const S*)h->al_d_g; a.al.z = (S*)h->al_d_z;
-  a.al.enabled = h->al_defs.empty() ? 0 : 1;
-  a.al.uniform = h->al_uniform; a.al.rows_per_knot = h->al_rows_per_knot; a.al.N = h->N; a.al.G_count = h->al_G_count; a.al.has_soc = h->al_has_soc; a.al.all_sel = h->al_all_sel; a.al.Gpad = (decltype(a.al.Gpad))h->al_d_Gpad; a.al.Gpad_count = h->al_Gpad_count; a.al.max_ncon = h->al_max_ncon;
+  a.al = al_table<S>(h);
   a.mode = mode;
   a.penalty_scaling = h->expand_penalty_scaling; a.penalty_max = h->expand_penalty_max;
   if (which == IK_STATIONARITY || which == IK_DUAL)   // constraint rows in the DPP form unless ALTRO_HIP_FORM_ALROWS_LDS
@@ -387,11 +384,7 @@ int gen_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int 
   a.off = h->g_off; a.nx = h->g_nx; a.nu = h->g_nu;
   const GenSizes gs = gen_sizes(h);
   a.sx = gs.sx; a.su = gs.su; a.sQ = gs.sQ; a.sR = gs.sR; a.sH = gs.sH;
-  a.al.knots = h->al_d_knots; a.al.G = (const T*)h->al_d_G; a.al.g = (const T*)h->al_d_g; a.al.z = (T*)h->al_d_z;
-  a.al.enabled = h->al_defs.empty() ? 0 : 1;
-  a.al.uniform = h->al_uniform; a.al.rows_per_knot = h->al_rows_per_knot; a.al.N = h->N; a.al.G_count = h->al_G_count;
-  a.al.has_soc = h->al_has_soc; a.al.all_sel = h->al_all_sel; a.al.Gpad = nullptr; a.al.Gpad_count = 0;
-  a.al.big = h->al_d_big; a.al.gsel = h->al_d_gsel; a.al.guser = h->al_d_guser;
+  a.al = al_table<T>(h);
   // MeritFunction in the row layout of kernels/ilqr_row32.hip: plan MFMA32's shapes (also on a handle created as plan GENERIC), fp64,
   // dynamics as data, every constraint block in a row-wise cone with at most 32 rows
   a.row32 = (sizeof(T) == 8 && row32_eligible(h)) ? 1 : 0;
@@ -546,6 +539,15 @@ int ilqr_check(altro_hip_batch* h, bool need_guess) {
   return 0;
 }
 
+// A device model on plan GENERIC or MFMA16: A_k, B_k (plan MFMA16: the DYN records, Z = [A B]) are the EXPANSION's from now on, written
+// by the expansion / merit kernels, and f = 0.  (memsets on the handle's own stream: see al_upload_typed)
+int model_takes_dynamics(altro_hip_batch* h) {
+  if (h->plan == ALTRO_HIP_PLAN_GENERIC) for (int a : {G_f, G_A, G_B}) HIP_TRY(hipMemsetAsync(h->g_arr[a], 0, (size_t)h->batch * h->g_bstride[a] * h->esz, h->stream));
+  if (h->plan == ALTRO_HIP_PLAN_MFMA16) HIP_TRY(hipMemsetAsync(h->m_in, 0, (size_t)h->batch * h->N * MF_DYN * h->esz, h->stream));
+  h->dyn_set = true; h->has_f = 0;
+  return 0;
+}
+
 template IlqrArgs<double> ilqr_args<double>(altro_hip_batch*, bool, bool, int, double);
 template IlqrArgs<float> ilqr_args<float>(altro_hip_batch*, bool, bool, int, double);
 }  // namespace capi
@@ -574,12 +576,7 @@ int altro_hip_set_model(altro_hip_batch* h, int model, float timestep, int bicyc
     if (h->dtype != ALTRO_HIP_F64) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "device models on plans GENERIC / MFMA32 run on fp64 handles");
     h->model = ModelParams{model, timestep, 0, 2.7, 1.5};
     h->model_set = true;
-    // A_k, B_k are the EXPANSION's from now on (written by the expansion / merit kernels), f = 0
-    HIP_TRY(hipMemsetAsync(h->g_arr[G_f], 0, (size_t)h->batch * h->g_bstride[G_f] * h->esz, h->stream));
-    HIP_TRY(hipMemsetAsync(h->g_arr[G_A], 0, (size_t)h->batch * h->g_bstride[G_A] * h->esz, h->stream));
-    HIP_TRY(hipMemsetAsync(h->g_arr[G_B], 0, (size_t)h->batch * h->g_bstride[G_B] * h->esz, h->stream));
-    h->dyn_set = true; h->has_f = 0;
-    return 0;
+    return model_takes_dynamics(h);
   }
   const bool tile = h->plan == ALTRO_HIP_PLAN_MFMA16 && ilqr_tile_model_supported(model, h->n, h->m);   // kernels/ilqr_tile_model.hip
   if (tile && h->dtype != ALTRO_HIP_F64)
@@ -589,11 +586,7 @@ int altro_hip_set_model(altro_hip_batch* h, int model, float timestep, int bicyc
   h->model = ModelParams{model, timestep, bicycle_frame, bicycle_length > 0 ? bicycle_length : 2.7,
                          bicycle_lr > 0 ? bicycle_lr : 1.5};
   h->model_set = true;
-  if (tile) {   // the DYN records are the EXPANSION's from now on (Z = [A B] written by the expansion / merit kernels, f = 0)
-    HIP_TRY(hipMemsetAsync(h->m_in, 0, (size_t)h->batch * h->N * MF_DYN * h->esz, h->stream));
-    h->dyn_set = true; h->has_f = 0;
-  }
-  return 0;
+  return tile ? model_takes_dynamics(h) : 0;
 }
 
 int altro_hip_set_tracking_cost(altro_hip_batch* h, const double* Qd, const double* Rd, const double* xref,

@@ -23,6 +23,7 @@
 #include "kernels/ilqr_generic.hip"
 #include "kernels/mfma16_layout.h"
 #include "linesearch_sm.h"
+#include "rtc_unit.h"
 
 namespace altro_hip {
 namespace capi {
@@ -99,7 +100,7 @@ struct altro_hip_batch {
   bool rtc_has_constraints = false;   // ... whose source also defines altro_user_constraint / _jacobian
   void* rtc = nullptr;            // run-time compiled model (capi_rtc.hip: RtcModule, shared through a per-process cache)
   std::string rtc_source;         // ... its source, and the cost kind (IlqrArgs::cost_kind) its cost-reading kernels were instantiated for
-  int rtc_ck = 0;
+  int rtc_ck = 0;                 // (plan MFMA16: constraint blocks | dense cost << 1, rtc_tile_launch)
   int x0_stride = 0;              // elements between two problems' x0 on the device (12 on plan MFMA16, else n)
   int spare_count = 0;            // spare candidate trajectories i_cand_spec holds (sized to the path in use, see spec_trials_cap)
   int spare_failed = 0;           // > 0: an allocation of this many spares failed on this handle (no retry at this size or above)
@@ -487,9 +488,7 @@ inline int lane_get(altro_hip_batch* h, double* host, const void* src, const voi
 constexpr int kCounterSlots = 2048;   // counter slots of one handle (altro_hip_batch::i_counters)
 constexpr int kStatsBlocks = 1024, kStatsStride = 16;   // capi_stats.hip: partials [kStatsBlocks][kStatsStride]
 
-// run-time compiled user models (capi_rtc.hip): the kernels of the launch-sequenced loop, in this order in RtcModule::fn
-enum RtcKernel { RTC_ROLLOUT = 0, RTC_ACCEPT, RTC_EXPAND, RTC_MERIT, RTC_MERIT_ROLL, RTC_MERIT_POINT, RTC_MERIT_SUM, RTC_SPEC_SELECT,
-                 RTC_ZERO_RESIDUALS, RTC_STATIONARITY, RTC_DUAL, RTC_SHIFT, RTC_NUM };
+// run-time compiled user models (capi_rtc.hip; RtcKernel and the other kinds' slots: rtc_unit.h)
 template <typename T>
 int rtc_launch(altro_hip_batch* h, int which, const IlqrArgs<T>& a);
 int rtc_tile_launch(altro_hip_batch* h, int which, const IlqrWaveArgs<double>& a);   // plan MFMA16: the model kernels of a caller's source
@@ -500,6 +499,7 @@ int rtc_gen_al_launch(altro_hip_batch* h, int which, const IlqrGenArgs<double>& 
 int replan_empty_handle(altro_hip_batch* h, int plan);   // capi_core.hip
 // capi_ilqr.hip, for the solve loop in capi_solve.hip
 int al_upload(altro_hip_batch* h);
+int model_takes_dynamics(altro_hip_batch* h);   // a device model (compiled in or from source) owns the dynamics arrays from now on
 int ilqr_check(altro_hip_batch* h, bool need_guess);
 int ilqr_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int want_deriv, double alpha_const,
              int mode = EXPAND_GRADIENT | EXPAND_HESSIAN);
