@@ -100,7 +100,7 @@ struct altro_hip_batch {
   bool rtc_has_constraints = false;   // ... whose source also defines altro_user_constraint / _jacobian
   void* rtc = nullptr;            // run-time compiled model (capi_rtc.hip: RtcModule, shared through a per-process cache)
   std::string rtc_source;         // ... its source, and the cost kind (IlqrArgs::cost_kind) its cost-reading kernels were instantiated for
-  int rtc_ck = 0;                 // (plan MFMA16: constraint blocks | dense cost << 1, rtc_tile_launch)
+  int rtc_ck = 0;                 // (plan MFMA16: constraint blocks | dense cost << 1 | more than AL_MAXC slots << 2, rtc_tile_launch)
   int x0_stride = 0;              // elements between two problems' x0 on the device (12 on plan MFMA16, else n)
   int spare_count = 0;            // spare candidate trajectories i_cand_spec holds (sized to the path in use, see spec_trials_cap)
   int spare_failed = 0;           // > 0: an allocation of this many spares failed on this handle (no retry at this size or above)

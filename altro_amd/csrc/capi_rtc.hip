@@ -189,7 +189,10 @@ static int rtc_build(altro_hip_batch* h, const RtcUnit& unit, const std::string&
 static int rtc_lane_module(altro_hip_batch* h, const std::string& source, int ck, RtcModule** out) {
   return rtc_build(h, rtc_unit_lane(h->n, h->m, h->dtype == ALTRO_HIP_F64 ? "double" : "float", ck, source), source, out);
 }
-static int rtc_tile_module(altro_hip_batch* h, int al, int dense, RtcModule** out) { return rtc_build(h, rtc_unit_tile(h->n, h->m, al, dense, h->rtc_source), h->rtc_source, out); }
+// (ck: constraint blocks | dense cost << 1 | more than AL_MAXC slots at some knot point << 2 -- altro_hip_batch::rtc_ck)
+static int rtc_tile_module(altro_hip_batch* h, int ck, RtcModule** out) {
+  return rtc_build(h, rtc_unit_tile(h->n, h->m, ck & 1, (ck >> 1) & 1, h->rtc_source, (ck >> 2) & 1), h->rtc_source, out);
+}
 // One launch from a run-time module.  `a`: the kernel's one parameter (only read); fmt, p...: the message of a failed launch, the error's text last.
 template <typename A, typename... P>
 static int rtc_go(altro_hip_batch* h, hipFunction_t f, unsigned gx, unsigned gy, unsigned bx, unsigned lds, const A& a, const char* fmt, P... p) {
@@ -242,10 +245,10 @@ int rtc_gen_al_launch(altro_hip_batch* h, int which, const IlqrGenArgs<double>& 
 // A model kernel of plan MFMA16's loop from the handle's run-time module: the grids of ilqr_launch_mfma16_model.hip.
 int rtc_tile_launch(altro_hip_batch* h, int which, const IlqrWaveArgs<double>& a) {
   if (h->rtc_source.empty()) return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_set_model_source has not been called");
-  const int ck = (a.al.enabled ? 1 : 0) | (a.cost_dense ? 2 : 0);
-  if (!h->rtc || h->rtc_ck != ck) {   // blocks or a dense cost came or went since the handle's module was built: the instantiations for this combination
+  const int ck = (a.al.enabled ? 1 : 0) | (a.cost_dense ? 2 : 0) | ((a.al.enabled && a.al.max_ncon > AL_MAXC) ? 4 : 0);
+  if (!h->rtc || h->rtc_ck != ck) {   // blocks, a dense cost or a third slot came or went since the handle's module was built: the instantiations for this combination
     RtcModule* m2 = nullptr;
-    if (const int rc = rtc_tile_module(h, ck & 1, ck >> 1, &m2)) return rc;
+    if (const int rc = rtc_tile_module(h, ck, &m2)) return rc;
     h->rtc = m2; h->rtc_ck = ck;
   }
   const RtcModule* mod = (const RtcModule*)h->rtc;
@@ -350,8 +353,9 @@ int altro_hip_set_model_source(altro_hip_batch* h, const char* source, float tim
     h->rtc_source = src;
     h->model = ModelParams{MODEL_USER, timestep, 0, 2.7, 1.5};
     RtcModule* tm = nullptr;   // compile now: a source that does not build must fail HERE, with the compiler's log
-    const int ck = (h->al_defs.empty() ? 0 : 1) | (h->cost_dense ? 2 : 0);
-    if ((rc = rtc_tile_module(h, ck & 1, ck >> 1, &tm))) { h->rtc_source.clear(); return rc; }
+    if (!h->al_defs.empty() && (rc = al_upload(h))) { h->rtc_source.clear(); h->model = ModelParams{MODEL_LINEAR, 0.0f, 0, 2.7, 1.5}; return rc; }   // (al_max_ncon: the slots of the blocks so far)
+    const int ck = (h->al_defs.empty() ? 0 : 1) | (h->cost_dense ? 2 : 0) | ((!h->al_defs.empty() && h->al_max_ncon > AL_MAXC) ? 4 : 0);
+    if ((rc = rtc_tile_module(h, ck, &tm))) { h->rtc_source.clear(); return rc; }
     h->rtc = tm; h->rtc_ck = ck; h->model_set = true; h->rtc_has_constraints = false;
     return model_takes_dynamics(h);
   }

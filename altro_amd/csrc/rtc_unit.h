@@ -17,7 +17,7 @@ namespace capi {
 enum RtcKernel { RTC_ROLLOUT = 0, RTC_ACCEPT, RTC_EXPAND, RTC_MERIT, RTC_MERIT_ROLL, RTC_MERIT_POINT, RTC_MERIT_SUM, RTC_SPEC_SELECT,
                  RTC_ZERO_RESIDUALS, RTC_STATIONARITY, RTC_DUAL, RTC_SHIFT, RTC_NUM };
 // tile: the rollout, the dynamics expansion and the two merit kernels (line-search round / two-trial pass) of one (source, n, m,
-// constraint blocks?, dense cost?) -- four kernels instead of ten, the merit kernels being the library's heaviest compiles
+// constraint blocks?, dense cost?, more than AL_MAXC slots?) -- four kernels instead of ten, the merit kernels being the library's heaviest compiles
 enum RtcTileKernel { RTT_ROLLOUT = 0, RTT_EXPAND_DYN, RTT_MERIT, RTT_MERIT2, RTT_NUM };
 // generic: three kernels per (source, n, m): the open-loop rollout, the dynamics expansion and the merit evaluation.
 // On plan MFMA32's shapes three more: the merit kernel, its two-trial pass and the dynamics expansion in the row layout
@@ -107,19 +107,24 @@ inline RtcUnit rtc_unit_lane(int n, int m, const char* T, int ck, const std::str
   u.args = std::string("IlqrArgs<") + T + ">"; u.options = kRtcOptions;
   return u;
 }
-// plan MFMA16: the caller's model inside the tile plan's row-layout kernels (kernels/ilqr_tile_model.hip), fp64 records
-inline RtcUnit rtc_unit_tile(int n, int m, int al, int dense, const std::string& source) {
+// plan MFMA16: the caller's model inside the tile plan's row-layout kernels (kernels/ilqr_tile_model.hip), fp64 records.
+// wide: some knot point of the handle has more than AL_MAXC constraint slots -- the merit kernels are then the AL_TILE_MAXC-slot
+// instantiations (the ones ilqr_launch_mfma16_wide.hip holds for the compiled-in models); a two-slot kernel would skip the slots past
+// the second while the expansion, the dual update and the feasibility walk honour them.
+inline RtcUnit rtc_unit_tile(int n, int m, int al, int dense, const std::string& source, int wide = 0) {
   RtcUnit u;
   u.kind = RtcKind::tile; u.program = "altro_user_tile_model.hip"; u.where = " for the tile plan"; u.noun = "tile model";
-  u.key = std::string(1, (char)u.kind) + "|" + std::to_string(n) + "|" + std::to_string(m) + "|" + std::to_string(al) + "|" + std::to_string(dense) + "|" + source;
+  u.key = std::string(1, (char)u.kind) + "|" + std::to_string(n) + "|" + std::to_string(m) + "|" + std::to_string(al) + "|" + std::to_string(dense) + "|" +
+          std::to_string(wide) + "|" + source;
   u.defines = "#define ALTRO_HIP_TILE_N " + std::to_string(n) + "\n#define ALTRO_HIP_TILE_M " + std::to_string(m) + "\n";
   u.includes = "#include \"kernels/ilqr_mfma16.hip\"\n#include \"kernels/ilqr_merit2_dpp.hip\"\n";
   const char* B_[2] = {"false", "true"};
   u.exprs.resize(RTT_NUM);
   u.exprs[RTT_ROLLOUT] = "altro_hip::wave_rollout_model_kernel<double, altro_hip::MODEL_USER>";
   u.exprs[RTT_EXPAND_DYN] = "altro_hip::wave_expand_dyn_kernel<double, altro_hip::MODEL_USER>";
-  u.exprs[RTT_MERIT] = std::string("altro_hip::wave_merit_dpp_kernel<double, ") + B_[al] + ", false, " + B_[dense] + ", altro_hip::MODEL_USER>";
-  u.exprs[RTT_MERIT2] = std::string("altro_hip::wave_merit_dpp_kernel<double, ") + B_[al] + ", true, " + B_[dense] + ", altro_hip::MODEL_USER>";
+  const char* tail = wide ? ", altro_hip::MODEL_USER, true, false, altro_hip::AL_TILE_MAXC>" : ", altro_hip::MODEL_USER>";
+  u.exprs[RTT_MERIT] = std::string("altro_hip::wave_merit_dpp_kernel<double, ") + B_[al] + ", false, " + B_[dense] + tail;
+  u.exprs[RTT_MERIT2] = std::string("altro_hip::wave_merit_dpp_kernel<double, ") + B_[al] + ", true, " + B_[dense] + tail;
   u.args = "IlqrWaveArgs<double>"; u.options = kRtcRowOptions;
   return u;
 }

@@ -316,7 +316,10 @@ int altro_hip_get_expansion(altro_hip_batch* h, double* A, double* B, double* lx
  *                      duals stay [p] per block), a second-order cone (p <= 4) one -- and 32 slots per handle: e.g. an input box
  *                      (8 rows) and a state box (24 rows) at every knot point with two slots to spare.  Knot points with up to 2 / 4 /
  *                      6 slots run the merit kernel's 2- / 4- / 6-slot instantiation (the last at one wave per SIMD: C1 with both
- *                      boxes solves in 1.27 x the time of the input box alone).  fp32 records: 2 slots;
+ *                      boxes solves in 1.27 x the time of the input box alone).  fp32 records: 2 slots.  The capacity
+ *                      is the same for handles with a device model (altro_hip_set_model) and with a model from source
+ *                      (altro_hip_set_model_source): the run-time compiled merit kernels are built for the table's width, and
+ *                      built again when blocks added or cleared later move it across two slots;
  *   plan LANE          2 blocks per knot point, p <= 8 (SOC: p <= 4), 16 blocks per handle (the blocks ride registers of the
  *                      lane-per-problem kernels); rows of one cone can be stacked into one block.
  * Returns the block id (>= 0) or a negative error.  Duals and penalties live on the device per problem and,

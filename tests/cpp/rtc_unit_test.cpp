@@ -326,6 +326,38 @@ altro_hip::generic_dual_update_kernel<double>
 -mllvm
 -unroll-threshold=5000
 )X"},
+      // (more than AL_MAXC constraint slots at a knot point: the merit kernels' AL_TILE_MAXC-slot instantiations)
+      {"tile_11w", rtc_unit_tile(12, 4, 1, 1, kPlain, 1), &kPlain, "altro_user_tile_model.hip",
+       R"X(#define ALTRO_HIP_USER_MODEL 1
+#define ALTRO_HIP_TILE_N 12
+#define ALTRO_HIP_TILE_M 4
+#include "rtc_compat.h"
+#include "fp_contract.h"
+ALTRO_FP_REGION_ON
+#line 1 "user_model"
+template <typename T> __device__ void altro_user_dynamics(const T* x, const T* u, T* xdot) {}
+template <typename T> __device__ void altro_user_jacobian(const T* x, const T* u, T* J) {}
+
+ALTRO_FP_REGION_END
+#include "kernels/ilqr_mfma16.hip"
+#include "kernels/ilqr_merit2_dpp.hip"
+namespace altro_hip {
+template __global__ void wave_rollout_model_kernel<double, MODEL_USER>(IlqrWaveArgs<double>);
+template __global__ void wave_expand_dyn_kernel<double, MODEL_USER>(IlqrWaveArgs<double>);
+template __global__ void wave_merit_dpp_kernel<double, true, false, true, MODEL_USER, true, false, AL_TILE_MAXC>(IlqrWaveArgs<double>);
+template __global__ void wave_merit_dpp_kernel<double, true, true, true, MODEL_USER, true, false, AL_TILE_MAXC>(IlqrWaveArgs<double>);
+}
+)X",
+       R"X(altro_hip::wave_rollout_model_kernel<double, altro_hip::MODEL_USER>
+altro_hip::wave_expand_dyn_kernel<double, altro_hip::MODEL_USER>
+altro_hip::wave_merit_dpp_kernel<double, true, false, true, altro_hip::MODEL_USER, true, false, altro_hip::AL_TILE_MAXC>
+altro_hip::wave_merit_dpp_kernel<double, true, true, true, altro_hip::MODEL_USER, true, false, altro_hip::AL_TILE_MAXC>
+)X",
+       R"X(-O3
+-std=c++17
+-mllvm
+-unroll-threshold=5000
+)X"},
   };
   for (const Case& c : cases) {
     const std::string text = rtc_unit_text(c.unit, *c.source), names = lines(c.unit.exprs);
@@ -338,7 +370,7 @@ altro_hip::generic_dual_update_kernel<double>
   }
   // the slots: a lane unit fills RtcKernel's, a tile unit RtcTileKernel's, a generic unit leaves empty what it does not instantiate
   auto filled = [](const RtcUnit& u) { std::string s; for (const std::string& e : u.exprs) s += e.empty() ? '-' : 'x'; return s; };
-  const char* want_slots[] = {"xxxxxxxxxxxx", "xxxxxxxxxxxx", "xxxx", "xxxx", "xxx------", "xxx---xxx", "xxxxxx---", "xxxxxxxxx"};
+  const char* want_slots[] = {"xxxxxxxxxxxx", "xxxxxxxxxxxx", "xxxx", "xxxx", "xxx------", "xxx---xxx", "xxxxxx---", "xxxxxxxxx", "xxxx"};
   for (size_t i = 0; i < sizeof(cases) / sizeof(cases[0]); ++i) check(filled(cases[i].unit) == want_slots[i], cases[i].name, "slots", filled(cases[i].unit), want_slots[i]);
   check(cases[7].unit.exprs[RTG_ROW_MERIT2].find("row32_merit_kernel<double, 13, 4, 1, true") != std::string::npos, "gen_13_4_con", "RTG_ROW_MERIT2", cases[7].unit.exprs[RTG_ROW_MERIT2], "");
   check(cases[5].unit.exprs[RTG_DUAL] == "altro_hip::generic_dual_update_kernel<double>", "gen_4_2_con", "RTG_DUAL", cases[5].unit.exprs[RTG_DUAL], "");
@@ -347,6 +379,7 @@ altro_hip::generic_dual_update_kernel<double>
   check(kl != kt && kl != kg && kt != kg, "keys", "the kinds' keys differ", kl.substr(0, 24) + " / " + kt.substr(0, 24) + " / " + kg.substr(0, 24), "");
   check(cases[0].unit.key != cases[1].unit.key && cases[2].unit.key != cases[3].unit.key && cases[4].unit.key != cases[5].unit.key &&
         cases[4].unit.key != cases[6].unit.key && kt != rtc_unit_tile(12, 4, 1, 0, kPlain).key && kt != rtc_unit_tile(12, 4, 0, 1, kPlain).key &&
+        cases[3].unit.key != cases[8].unit.key && rtc_unit_tile(12, 4, 1, 0, kPlain).key != rtc_unit_tile(12, 4, 1, 0, kPlain, 1).key &&
         kl != rtc_unit_lane(12, 4, "float", 0, kPlain).key && kl != rtc_unit_lane(12, 4, "double", 1, kPlain).key, "keys", "arguments", "", "");
   // defines_function: a name that appears only inside a // comment, and one that is the tail of a longer identifier, define nothing
   check(!defines_function("// altro_user_constraint(int id) is not defined here\nint f(int);\n", "altro_user_constraint"), "defines_function", "comment", "true", "false");
