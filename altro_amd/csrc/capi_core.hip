@@ -39,8 +39,7 @@ int lane_get_any(altro_hip_batch* h, int what, double* dst) {
     case MGET_y: src = h->l_xuy; E = z.e_xuy; off = n; len = n; nk = nk_main = N + 1; break;
     default: src = h->l_xuy; E = z.e_xuy; off = 2 * n; len = m; nk = nk_main = N; break;
   }
-  return h->dtype == ALTRO_HIP_F64 ? lane_get<double>(h, dst, src, term, E, off, off_t, len, nk, nk_main)
-                                   : lane_get<float>(h, dst, src, term, E, off, off_t, len, nk, nk_main);
+  return lane_get(h, dst, src, 0, term, E, off, off_t, len, nk, nk_main);
 }
 
 }  // namespace
@@ -157,17 +156,17 @@ static int batch_create_impl(altro_hip_batch** out, int N, int n, int m, int bat
     {
       // knot-point-major slabs [k][b][record] (problem-major [b][k] measured the same)
       const int64_t Bq = batch;
-      h->m_st = Mfma16Strides{MF_DYN, Bq * MF_DYN, MF_OUT, Bq * MF_OUT, 28, Bq * 28, MF_COST, Bq * MF_COST};
+      h->m_st = Mfma16Strides{MF_DYN, Bq * MF_DYN, MF_OUT, Bq * MF_OUT, MF_XUY, Bq * MF_XUY, MF_COST, Bq * MF_COST};
     }
     ALLOC(h->m_term, B * MF_TERM * E);
     ALLOC(h->m_out, B * N * MF_OUT * E);
     ALLOC(h->m_outn, B * MF_TERM * E);
-    ALLOC(h->m_xuy, B * (N + 1) * 28 * E);
+    ALLOC(h->m_xuy, B * (N + 1) * MF_XUY * E);
     ALLOC(h->m_trash, B * MF_OUT * E);
     if (flags & ALTRO_HIP_STORE_QBLOCKS) ALLOC(h->m_qblk, B * N * MF_QB * E);
     if (!rc && (n < MF_N || m < MF_M)) {   // padded shape: whatever no setter writes must read as zero
       (void)hipMemsetAsync(h->x0, 0, B * MF_N * E, h->stream);
-      (void)hipMemsetAsync(h->m_xuy, 0, B * (N + 1) * 28 * E, h->stream);
+      (void)hipMemsetAsync(h->m_xuy, 0, B * (N + 1) * MF_XUY * E, h->stream);
       (void)hipMemsetAsync(h->m_in, 0, B * N * MF_DYN * E, h->stream);
       (void)hipMemsetAsync(h->m_cin, 0, B * N * MF_COST * E, h->stream);
       (void)hipMemsetAsync(h->m_term, 0, B * MF_TERM * E, h->stream);
@@ -365,37 +364,20 @@ int altro_hip_set_dynamics(altro_hip_batch* h, const double* A, const double* B,
   } else if (h->plan == ALTRO_HIP_PLAN_LANE) {
     const LaneSizes z = lane_sizes(n, m);
     const int nkh = kz ? 1 : N;
-    auto pk = [&](const double* src, int len, int off) -> int {
-      return h->dtype == ALTRO_HIP_F64
-                 ? lane_pack<double>(h, (double*)h->l_in, z.e_in, src, len, off, 0, N, 0, nkh, kz, bz)
-                 : lane_pack<float>(h, (float*)h->l_in, z.e_in, src, len, off, 0, N, 0, nkh, kz, bz);
-    };
+    auto pk = [&](const double* src, int len, int off) -> int { return lane_pack(h, h->l_in, 0, z.e_in, src, len, off, 0, N, 0, nkh, kz, bz); };
     rc = pk(A, n * n, 0);
     if (!rc) rc = pk(B, n * m, n * n);
     if (!rc) rc = pk(f, n, n * n + n * m);
-  } else if (h->ragged) {   // per-knot-point dimensions: the caller's packed [b][k][block_k] IS the device layout, one block per problem
-    if (kz) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "k_stride_zero needs uniform dimensions");
-    auto whole = [&](int arr, const double* src) -> int {
-      if (!src) { HIP_TRY(hipMemsetAsync(h->g_arr[arr], 0, (size_t)h->batch * h->g_bstride[arr] * h->esz, h->stream)); return 0; }
-      return h->dtype == ALTRO_HIP_F64 ? generic_set<double>(h, arr, src, (int)h->g_bstride[arr], 1, 0, bz)
-                                       : generic_set<float>(h, arr, src, (int)h->g_bstride[arr], 1, 0, bz);
+  } else {   // plan GENERIC; per-knot-point dimensions: the caller's packed [b][k][block_k] IS the device layout, one block per problem
+    if (h->ragged && kz) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "k_stride_zero needs uniform dimensions");
+    auto set = [&](int arr, const double* src, int blk) -> int {
+      return h->ragged ? generic_set(h, arr, src, (int)h->g_bstride[arr], 1, 0, bz) : generic_set(h, arr, src, blk, N, kz, bz);
     };
-    rc = whole(G_A, A);
-    if (!rc) rc = whole(G_B, B);
-    if (!rc) rc = whole(G_f, f);
-  } else if (h->dtype == ALTRO_HIP_F64) {
-    rc = generic_set<double>(h, G_A, A, n * n, N, kz, bz);
-    if (!rc) rc = generic_set<double>(h, G_B, B, n * m, N, kz, bz);
+    rc = set(G_A, A, n * n);
+    if (!rc) rc = set(G_B, B, n * m);
     if (!rc) {
-      if (f) rc = generic_set<double>(h, G_f, f, n, N, kz, bz);
-      else HIP_TRY(hipMemsetAsync(h->g_arr[G_f], 0, (size_t)h->batch * N * n * h->esz, h->stream));
-    }
-  } else {
-    rc = generic_set<float>(h, G_A, A, n * n, N, kz, bz);
-    if (!rc) rc = generic_set<float>(h, G_B, B, n * m, N, kz, bz);
-    if (!rc) {
-      if (f) rc = generic_set<float>(h, G_f, f, n, N, kz, bz);
-      else HIP_TRY(hipMemsetAsync(h->g_arr[G_f], 0, (size_t)h->batch * N * n * h->esz, h->stream));
+      if (f) rc = set(G_f, f, n);
+      else HIP_TRY(hipMemsetAsync(h->g_arr[G_f], 0, (size_t)h->batch * h->g_bstride[G_f] * h->esz, h->stream));
     }
   }
   if (!rc) { HIP_TRY(hipStreamSynchronize(h->stream)); h->dyn_set = true; }
@@ -438,9 +420,7 @@ int altro_hip_set_cost(altro_hip_batch* h, const double* Q, const double* R, con
     const int oQ = n * n + n * m + n, oR = oQ + n * n, oH = oR + m * m, oq = oH + m * n, or_ = oq + n;
     auto pk = [&](void* dst, int E, const double* src, int len, int off, int diag, int nk, int k_src0,
                   int nk_host, int src_off = 0) -> int {
-      return h->dtype == ALTRO_HIP_F64
-                 ? lane_pack<double>(h, (double*)dst, E, src, len, off, diag, nk, k_src0, nk_host, kz, bz, src_off)
-                 : lane_pack<float>(h, (float*)dst, E, src, len, off, diag, nk, k_src0, nk_host, kz, bz, src_off);
+      return lane_pack(h, dst, 0, E, src, len, off, diag, nk, k_src0, nk_host, kz, bz, src_off);
     };
     // terminal source knot point: index N, or block 1 of the broadcast pair (ks == 0 there, so the
     // device source pointer is shifted by one block instead)
@@ -471,8 +451,7 @@ int altro_hip_set_cost(altro_hip_batch* h, const double* Q, const double* R, con
     }
     auto whole = [&](int arr, const double* src) -> int {
       if (!src) { HIP_TRY(hipMemsetAsync(h->g_arr[arr], 0, (size_t)h->batch * h->g_bstride[arr] * h->esz, h->stream)); return 0; }
-      return h->dtype == ALTRO_HIP_F64 ? generic_set<double>(h, arr, src, (int)h->g_bstride[arr], 1, 0, bz)
-                                       : generic_set<float>(h, arr, src, (int)h->g_bstride[arr], 1, 0, bz);
+      return generic_set(h, arr, src, (int)h->g_bstride[arr], 1, 0, bz);
     };
     rc = whole(G_Q, Q);
     if (!rc) rc = whole(G_q, q);
@@ -485,8 +464,7 @@ int altro_hip_set_cost(altro_hip_batch* h, const double* Q, const double* R, con
         HIP_TRY(hipMemsetAsync(h->g_arr[arr], 0, (size_t)h->batch * nk * blk * h->esz, h->stream));
         return 0;
       }
-      return h->dtype == ALTRO_HIP_F64 ? generic_set<double>(h, arr, src, blk, nk, kz, bz, k0, nk_host, src_off)
-                                       : generic_set<float>(h, arr, src, blk, nk, kz, bz, k0, nk_host, src_off);
+      return generic_set(h, arr, src, blk, nk, kz, bz, k0, nk_host, src_off);
     };
     // NOTE: the device block of Q / R is always dense-sized (n*n / m*m); a diagonal cost keeps its
     // diagonal in the head of the block, like the reference does (knotpoint_data.cpp:92-95).
@@ -531,22 +509,8 @@ int altro_hip_set_initial_state(altro_hip_batch* h, const double* x0, int bz) {
   h->expansion_current = false;
   if (!x0) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "x0 == NULL");
   const int n0 = h->ragged ? h->nxv[0] : h->n;   // (per-knot-point dimensions: x0 has nx[0] entries per problem)
-  auto consume = [&](SrcArr s, int b0, int nb) -> int {
-    const int64_t total = (int64_t)nb * n0;
-    if (h->dtype == ALTRO_HIP_F64)
-      hipLaunchKernelGGL(expand_copy_kernel<double>, dim3(grid_for(total)), dim3(256), 0, h->stream,
-                         (double*)h->x0, (int64_t)h->x0_stride, (int64_t)h->x0_stride, s, n0, 1, b0, nb);
-    else
-      hipLaunchKernelGGL(expand_copy_kernel<float>, dim3(grid_for(total)), dim3(256), 0, h->stream,
-                         (float*)h->x0, (int64_t)h->x0_stride, (int64_t)h->x0_stride, s, n0, 1, b0, nb);
-    if (hipGetLastError() != hipSuccess) return fail(ALTRO_HIP_ERR_HIP, "x0 copy launch failed");
-    return 0;
-  };
-  rc = upload_chunks(h, x0, n0, 1, 1, bz, -1, 0, consume);
-  if (!rc && h->plan == ALTRO_HIP_PLAN_LANE)
-    rc = h->dtype == ALTRO_HIP_F64
-             ? lane_pack<double>(h, (double*)h->l_x0, h->n, x0, h->n, 0, 0, 1, 0, 1, 1, bz)
-             : lane_pack<float>(h, (float*)h->l_x0, h->n, x0, h->n, 0, 0, 1, 0, 1, 1, bz);
+  rc = aos_set(h, h->x0, 0, h->x0_stride, h->x0_stride, x0, n0, 1, 1, bz);
+  if (!rc && h->plan == ALTRO_HIP_PLAN_LANE) rc = lane_pack(h, h->l_x0, 0, h->n, x0, h->n, 0, 0, 1, 0, 1, 1, bz);
   if (!rc) {
     h->x0_set = true;
     // a handle that may still move to another plan (altro_hip_set_model on an ALTRO_HIP_PLAN_AUTO handle) keeps the initial state
@@ -585,10 +549,8 @@ int altro_hip_synchronize(altro_hip_batch* h) {
     if (h->plan == ALTRO_HIP_PLAN_MFMA16) return mfma16_get(h, MWHAT, dst, BLOCK, NK);          \
     if (h->plan == ALTRO_HIP_PLAN_LANE) return lane_get_any(h, MWHAT, dst);                     \
     if (h->ragged) /* per-knot-point dimensions: the packed array of a problem as one block */   \
-      return h->dtype == ALTRO_HIP_F64 ? generic_get<double>(h, GARR, dst, (int)h->g_bstride[GARR], 1)   \
-                                       : generic_get<float>(h, GARR, dst, (int)h->g_bstride[GARR], 1);   \
-    return h->dtype == ALTRO_HIP_F64 ? generic_get<double>(h, GARR, dst, BLOCK, NK)            \
-                                     : generic_get<float>(h, GARR, dst, BLOCK, NK);            \
+      return generic_get(h, GARR, dst, (int)h->g_bstride[GARR], 1);                             \
+    return generic_get(h, GARR, dst, BLOCK, NK);                                                \
   }
 GETTER(K, G_K, MGET_K, h->m * h->n, h->N, false)
 GETTER(d, G_d, MGET_d, h->m, h->N, false)
@@ -639,8 +601,7 @@ int altro_hip_get_qblocks(altro_hip_batch* h, double* dst) {
   const int blks[5] = {n * n, m * m, m * n, n, m};
   int offp = 0;
   for (int i = 0; i < 5; ++i) {
-    rc = h->dtype == ALTRO_HIP_F64 ? generic_get<double>(h, arrs[i], tmp.data(), blks[i], N)
-                                   : generic_get<float>(h, arrs[i], tmp.data(), blks[i], N);
+    rc = generic_get(h, arrs[i], tmp.data(), blks[i], N);
     if (rc) return rc;
     for (size_t bk = 0; bk < (size_t)h->batch * N; ++bk)
       memcpy(dst + bk * per + offp, tmp.data() + bk * blks[i], sizeof(double) * blks[i]);

@@ -308,7 +308,7 @@ int wave_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int
   a.want_derivative = want_deriv; a.alpha_const = alpha_const;
   a.cand_spec = (S*)h->i_cand_spec; a.spec_trials = h->i_cand_spec ? h->spec_trials : 1; a.spec_sel = h->i_spec_sel;
   a.spec_pre = h->i_cand_spec ? h->spec_pre : 0;
-  a.spec_stride = (int64_t)h->batch * (h->N + 1) * 28;
+  a.spec_stride = (int64_t)h->batch * (h->N + 1) * MF_XUY;
   a.ls_beta = h->spec_beta; a.ls_max_iters = h->spec_max_iters;
   a.skip = which == IK_STATIONARITY ? h->stat_skip : nullptr;
   if constexpr (sizeof(S) == 8) {   // affine line-search trials (capi_solve.hip switches them on for a solve): dynamics as data only
@@ -453,13 +453,31 @@ int ilqr_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int
   return ilqr_launch<float>(h, which, a);
 }
 
+struct CostUpload { int field; const double* src; int nk_host; };
+// Cost fields of knot points 0 .. N from host arrays of nk_host knot points per problem -- N + 1 or N, with kz the {running, terminal}
+// pair or the one running block: the running knot points of every field, then record N of those that have one (element N of a full
+// array, or the second entry of the pair).  `dense`: the cost form being set (the handle's flag changes once all of it is in place).
+int cost_fields_set(altro_hip_batch* h, bool dense, const CostUpload* up, int count, int kz, int bz) {
+  LoopShape s = loop_shape(h);
+  s.cost_dense = dense;
+  const int N = h->N;
+  int rc = 0;
+  for (int pass = 0; pass < 2; ++pass)
+    for (int i = 0; i < count && !rc; ++i) {
+      const FieldRef r0 = loop_field(s, up[i].field, 0), rN = loop_field(s, up[i].field, N);
+      const bool zero_array = !up[i].src && r0.kind == LK_AOS;   // plan GENERIC (one array per field): src == NULL zeroes it
+      if (pass == 0 && zero_array) HIP_TRY(hipMemsetAsync(loop_buffer(h, r0.buf), 0, (size_t)h->batch * r0.bs * h->esz, h->stream));
+      else if (pass == 0) rc = field_set(h, s, up[i].field, 0, s.ragged && rN.buf != LB_NONE ? N + 1 : N, up[i].src, kz, bz, up[i].nk_host);
+      else if (!zero_array && !s.ragged && rN.buf != LB_NONE) rc = field_set(h, s, up[i].field, N, 1, up[i].src, 1, bz, up[i].nk_host, (kz ? 1 : N) * rN.len);
+    }
+  return rc;
+}
 // plan GENERIC: the cost's own dense blocks (what the merit function and the expansion evaluate) next to the backward sweep's
 // inputs, which altro_hip_set_cost fills; nominal trajectory allocated on first use.  Host arrays: Q [nb][nkx][n n], R [nb][nku][m m],
 // H [nb][nku][m n], q [nb][nkx][n], r [nb][nku][m], c [nb][nkx] or NULL.
-template <typename T>
 int generic_cost_def(altro_hip_batch* h, const double* Q, const double* R, const double* H, const double* q, const double* r,
                      const double* c, int kz, int bz) {
-  const int n = h->n, m = h->m, N = h->N;
+  const int N = h->N;
   const int nkx = kz ? 2 : N + 1, nku = kz ? 1 : N;
   const size_t B = h->batch, E = h->esz;
   const GenSizes gs = gen_sizes(h);
@@ -478,40 +496,16 @@ int generic_cost_def(altro_hip_batch* h, const double* Q, const double* R, const
     // the candidate inputs (g_arr[G_u]) are NOT touched here: altro_hip_set_input_guess may come before the cost, like the reference's
     // SetInput may; they are zeroed once, when the handle is created
   }
-  auto put = [&](void* dst, int blk, int nk_total, const double* src, int nk_host, bool with_terminal) -> int {
-    if (!src) { HIP_TRY(hipMemsetAsync(dst, 0, B * nk_total * blk * E, h->stream)); return 0; }
-    int r_ = aos_set<T>(h, (T*)dst, (int64_t)nk_total * blk, (int64_t)blk, src, blk, N, kz, bz, nk_host, 0);
-    if (!r_ && with_terminal)   // knot point N: element N of a full host array, or the second entry of a {running, terminal} pair
-      r_ = aos_set<T>(h, (T*)dst + (size_t)N * blk, (int64_t)nk_total * blk, (int64_t)blk, src, blk, 1, 1, bz, nk_host, (kz ? 1 : N) * blk);
-    return r_;
-  };
-  if (h->ragged) {   // per-knot-point dimensions: the caller's packed [b][k][block_k] arrays are the device layout, one block per problem
-    if (kz) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "k_stride_zero needs uniform dimensions");
-    auto whole = [&](void* dst, int64_t len, const double* src) -> int {
-      if (!src) { HIP_TRY(hipMemsetAsync(dst, 0, B * len * E, h->stream)); return 0; }
-      return aos_set<T>(h, (T*)dst, len, len, src, (int)len, 1, 0, bz);
-    };
-    rc = whole(h->g_cQ, gs.sQ, Q);
-    if (!rc) rc = whole(h->g_cR, gs.sR, R);
-    if (!rc) rc = whole(h->g_cH, gs.sH, H);
-    if (!rc) rc = whole(h->g_cq, gs.sx, q);
-    if (!rc) rc = whole(h->g_cr, gs.su, r);
-    if (!rc) rc = whole(h->g_cc, N + 1, c);
-    return rc;
-  }
-  rc = put(h->g_cQ, n * n, N + 1, Q, nkx, true);
-  if (!rc) rc = put(h->g_cR, m * m, N, R, nku, false);
-  if (!rc) rc = put(h->g_cH, m * n, N, H, nku, false);
-  if (!rc) rc = put(h->g_cq, n, N + 1, q, nkx, true);
-  if (!rc) rc = put(h->g_cr, m, N, r, nku, false);
-  if (!rc) rc = put(h->g_cc, 1, N + 1, c, nkx, true);
-  return rc;
+  // (per-knot-point dimensions: the caller's packed [b][k][block_k] arrays are the device layout, one block per problem)
+  if (h->ragged && kz) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "k_stride_zero needs uniform dimensions");
+  const CostUpload up[] = {{LF_COST_Q, Q, nkx}, {LF_COST_R, R, nku}, {LF_COST_H, H, nku}, {LF_COST_q, q, nkx}, {LF_COST_r, r, nku}, {LF_COST_c, c, nkx}};
+  return cost_fields_set(h, true, up, 6, kz, bz);
 }
 int generic_cost(altro_hip_batch* h, const double* Q, const double* R, const double* H, const double* q, const double* r,
                  const double* c, int kz, int bz) {
   int rc = altro_hip_set_cost(h, Q, R, H, q, r, 0, kz, bz);   // the backward sweep's blocks: lxx = Q, luu = R, lux = H (lx, lu refreshed by the loop)
   if (rc) return rc;
-  rc = h->dtype == ALTRO_HIP_F64 ? generic_cost_def<double>(h, Q, R, H, q, r, c, kz, bz) : generic_cost_def<float>(h, Q, R, H, q, r, c, kz, bz);
+  rc = generic_cost_def(h, Q, R, H, q, r, c, kz, bz);
   if (!rc) { h->lqr_cost_set = true; h->ilqr_linear = true; h->cost_dense = true; h->spec_no_memory = true; /* one step per launch on this plan */ }
   return rc;
 }
@@ -638,7 +632,6 @@ int altro_hip_set_tracking_cost(altro_hip_batch* h, const double* Qd, const doub
   }
   const int n = h->n, m = h->m, N = h->N;
   const int nb = bz ? 1 : h->batch, nkx = kz ? 2 : N + 1, nku = kz ? 1 : N;
-  const int E = 2 * n + 2 * m + 1;
   // host-side arithmetic exactly as the reference's setter does it, then one upload per field
   std::vector<double> q((size_t)nb * nkx * n), r((size_t)nb * nku * m), c((size_t)nb * nkx);
   for (int b = 0; b < nb; ++b)
@@ -675,69 +668,30 @@ int altro_hip_set_tracking_cost(altro_hip_batch* h, const double* Qd, const doub
     // (a) the backward sweep's blocks: lxx = diag(Qd), luu = diag(Rd), lux = 0; lx, lu are refreshed by the loop
     rc = altro_hip_set_cost(h, Qd, Rd, nullptr, q.data(), r.data(), 1, kz, bz);
     if (rc) return rc;
-    // (b) the cost parameters the merit function needs: [k][b][36] = Qd | Rd | q | r | c
-    const size_t Ez = h->dtype == ALTRO_HIP_F64 ? 8 : 4;
+    // (b) the cost parameters the merit function needs: COSTP records [k][b][36] = Qd | Rd | q | r | c
     const int64_t B = h->batch;
     if (!h->m_costp) {
-      if ((rc = dmalloc(h, &h->m_costp, (size_t)B * (N + 1) * MF_COSTP * Ez))) return rc;
-      if ((rc = dmalloc(h, &h->m_nom, (size_t)B * (N + 1) * MF_NOM * Ez))) return rc;
-      HIP_TRY(hipMemsetAsync(h->m_costp, 0, (size_t)B * (N + 1) * MF_COSTP * Ez, h->stream));
-      HIP_TRY(hipMemsetAsync(h->m_nom, 0, (size_t)B * (N + 1) * MF_NOM * Ez, h->stream));
+      if ((rc = dmalloc(h, &h->m_costp, (size_t)B * (N + 1) * MF_COSTP * h->esz))) return rc;
+      if ((rc = dmalloc(h, &h->m_nom, (size_t)B * (N + 1) * MF_NOM * h->esz))) return rc;
+      HIP_TRY(hipMemsetAsync(h->m_costp, 0, (size_t)B * (N + 1) * MF_COSTP * h->esz, h->stream));
+      HIP_TRY(hipMemsetAsync(h->m_nom, 0, (size_t)B * (N + 1) * MF_NOM * h->esz, h->stream));
     }
-    auto put = [&](const double* src, int len, int off, int k0, int nk, int nk_host, int src_off) -> int {
-      // records k0..k0+nk-1; with kz the host holds {running, terminal} and src_off selects which
-      if (h->dtype == ALTRO_HIP_F64)
-        return aos_set<double>(h, (double*)h->m_costp + (size_t)k0 * B * MF_COSTP + off, MF_COSTP, B * MF_COSTP, src, len, nk,
-                               kz, bz, nk_host, src_off);
-      return aos_set<float>(h, (float*)h->m_costp + (size_t)k0 * B * MF_COSTP + off, MF_COSTP, B * MF_COSTP, src, len, nk, kz,
-                            bz, nk_host, src_off);
-    };
-    rc = put(Qd, n, 0, 0, N, nkx, 0);
-    if (!rc) rc = put(Rd, m, 12, 0, N, nku, 0);
-    if (!rc) rc = put(q.data(), n, 16, 0, N, nkx, 0);
-    if (!rc) rc = put(r.data(), m, 28, 0, N, nku, 0);
-    if (!rc) rc = put(c.data(), 1, 32, 0, N, nkx, 0);
-    if (!rc && m < MF_M) {   // padded inputs: Rd = 1 keeps their diagonal of Quu positive (they stay at exactly 0: K, d rows are 0)
-      const double ones[MF_M] = {1.0, 1.0, 1.0, 1.0};
-      rc = h->dtype == ALTRO_HIP_F64
-               ? aos_set<double>(h, (double*)h->m_costp + 12 + m, MF_COSTP, B * MF_COSTP, ones, MF_M - m, N, 1, 1, 1, 0)
-               : aos_set<float>(h, (float*)h->m_costp + 12 + m, MF_COSTP, B * MF_COSTP, ones, MF_M - m, N, 1, 1, 1, 0);
-    }
-    // terminal record N: element N of a full host array, or the second entry of a {running, terminal} pair
-    auto put_term = [&](const double* src, int len, int off) -> int {
-      const double* base = kz ? src : src;   // per problem the host holds nkx knot points
-      if (h->dtype == ALTRO_HIP_F64)
-        return aos_set<double>(h, (double*)h->m_costp + (size_t)N * B * MF_COSTP + off, MF_COSTP, B * MF_COSTP, base, len, 1, 1,
-                               bz, nkx, (kz ? 1 : N) * len);
-      return aos_set<float>(h, (float*)h->m_costp + (size_t)N * B * MF_COSTP + off, MF_COSTP, B * MF_COSTP, base, len, 1, 1, bz,
-                            nkx, (kz ? 1 : N) * len);
-    };
-    if (!rc) rc = put_term(Qd, n, 0);
-    if (!rc) rc = put_term(q.data(), n, 16);
-    if (!rc) rc = put_term(c.data(), 1, 32);
-    if (!rc) { h->lqr_cost_set = true; h->ilqr_linear = true; h->cost_dense = false; }
-    return rc;
   }
-  auto pk = [&](const double* src, int len, int off, int nk, int k_src0, int nk_host, int src_off) -> int {
-    return h->dtype == ALTRO_HIP_F64
-               ? lane_pack<double>(h, (double*)h->l_cost + (size_t)0, E, src, len, off, 0, nk, k_src0, nk_host, kz, bz, src_off)
-               : lane_pack<float>(h, (float*)h->l_cost + (size_t)0, E, src, len, off, 0, nk, k_src0, nk_host, kz, bz, src_off);
-  };
-  auto pk_term = [&](const double* src, int len, int off, int nk_host) -> int {   // record N of l_cost
-    const size_t base = (size_t)N * E * h->batch;
-    return h->dtype == ALTRO_HIP_F64
-               ? lane_pack<double>(h, (double*)h->l_cost + base, E, src, len, off, 0, 1, kz ? 0 : N, nk_host, kz, bz, kz ? len : 0)
-               : lane_pack<float>(h, (float*)h->l_cost + base, E, src, len, off, 0, 1, kz ? 0 : N, nk_host, kz, bz, kz ? len : 0);
-  };
-  rc = pk(Qd, n, 0, N, 0, nkx, 0);
-  if (!rc) rc = pk(Rd, m, n, N, 0, nku, 0);
-  if (!rc) rc = pk(q.data(), n, n + m, N, 0, nkx, 0);
-  if (!rc) rc = pk(r.data(), m, 2 * n + m, N, 0, nku, 0);
-  if (!rc) rc = pk(c.data(), 1, 2 * n + 2 * m, N, 0, nkx, 0);
-  if (!rc) rc = pk_term(Qd, n, 0, nkx);
-  if (!rc) rc = pk_term(q.data(), n, n + m, nkx);
-  if (!rc) rc = pk_term(c.data(), 1, 2 * n + 2 * m, nkx);
-  if (!rc) { h->lqr_cost_set = true; h->cost_set = true; h->dyn_set = true; h->is_diag = 0; h->has_f = 0; h->cost_dense = false; }
+  // plans MFMA16 and LANE: the diagonal cost's record Qd | Rd | q | r | c of every knot point (record N: Qd, q, c)
+  const CostUpload up[] = {{LF_COST_Qd, Qd, nkx}, {LF_COST_Rd, Rd, nku}, {LF_COST_q, q.data(), nkx}, {LF_COST_r, r.data(), nku}, {LF_COST_c, c.data(), nkx}};
+  rc = cost_fields_set(h, false, up, 5, kz, bz);
+  if (!rc && h->plan == ALTRO_HIP_PLAN_MFMA16 && m < MF_M) {   // padded inputs: Rd = 1 keeps their diagonal of Quu positive (they stay at exactly 0: K, d rows are 0)
+    const double ones[MF_M] = {1.0, 1.0, 1.0, 1.0};
+    LoopShape s = loop_shape(h);
+    s.cost_dense = false;
+    FieldRef pad = loop_field(s, LF_COST_Rd, 0);
+    pad.off += m; pad.len = MF_M - m;
+    rc = ref_set(h, pad, 0, N, ones, 1, 1, 1, 0);
+  }
+  if (rc) return rc;
+  h->lqr_cost_set = true; h->cost_dense = false;
+  if (h->plan == ALTRO_HIP_PLAN_MFMA16) h->ilqr_linear = true;
+  else { h->cost_set = true; h->dyn_set = true; h->is_diag = 0; h->has_f = 0; }
   return rc;
 }
 
@@ -789,57 +743,31 @@ int altro_hip_set_quadratic_cost(altro_hip_batch* h, const double* Q, const doub
       if (!rc) HIP_TRY(hipStreamSynchronize(h->stream));   // (the sources are freed on leaving this block)
     }
     if (!rc && c) {   // c_k into the record's spare slot, k = 0 .. N (record N holds nothing else)
-      auto putc = [&](int k0, int nk, int src_off) -> int {
-        if (h->dtype == ALTRO_HIP_F64)
-          return aos_set<double>(h, (double*)h->m_costd + (size_t)k0 * B * MF_COST + MF_COSTD_C, MF_COST, B * MF_COST, c, 1, nk, kz, bz, nkx, src_off);
-        return aos_set<float>(h, (float*)h->m_costd + (size_t)k0 * B * MF_COST + MF_COSTD_C, MF_COST, B * MF_COST, c, 1, nk, kz, bz, nkx, src_off);
-      };
-      rc = putc(0, N, 0);
-      if (!rc) {   // record N: element N of a full host array, or the second entry of a {running, terminal} pair
-        if (h->dtype == ALTRO_HIP_F64)
-          rc = aos_set<double>(h, (double*)h->m_costd + (size_t)N * B * MF_COST + MF_COSTD_C, MF_COST, B * MF_COST, c, 1, 1, 1, bz, nkx, kz ? 1 : N);
-        else
-          rc = aos_set<float>(h, (float*)h->m_costd + (size_t)N * B * MF_COST + MF_COSTD_C, MF_COST, B * MF_COST, c, 1, 1, 1, bz, nkx, kz ? 1 : N);
-      }
+      const CostUpload up[] = {{LF_COST_c, c, nkx}};
+      rc = cost_fields_set(h, true, up, 1, kz, bz);
     } else if (!rc) {   // c == NULL: zero (a handle that carried another cost before)
       const double zero = 0.0;
       struct HostPtrs { altro_hip_batch* h; bool keep; ~HostPtrs() { h->dev_ptrs = keep; } } host_ptrs{h, h->dev_ptrs};
       h->dev_ptrs = false;   // (`zero` lives on the host whatever the caller's pointer mode)
-      rc = h->dtype == ALTRO_HIP_F64
-               ? aos_set<double>(h, (double*)h->m_costd + MF_COSTD_C, MF_COST, B * MF_COST, &zero, 1, N + 1, 1, 1, 1, 0)
-               : aos_set<float>(h, (float*)h->m_costd + MF_COSTD_C, MF_COST, B * MF_COST, &zero, 1, N + 1, 1, 1, 1, 0);
+      LoopShape s = loop_shape(h);
+      s.cost_dense = true;
+      rc = field_set(h, s, LF_COST_c, 0, N + 1, &zero, 1, 1, 1, 0);
     }
     if (!rc) { h->lqr_cost_set = true; h->ilqr_linear = true; h->cost_dense = true; }
     return rc;
   }
   // plan LANE: [k][Q n n | R m m | H m n | q n | r m | c][batch], column-major blocks as given (IlqrDims<n, m, 1>)
-  const int E = n * n + m * m + m * n + n + m + 1;
-  const int oR = n * n, oH = oR + m * m, oq = oH + m * n, or_ = oq + n, oc = or_ + m;
+  LoopShape s = loop_shape(h);
+  s.cost_dense = true;
+  const int E = loop_field(s, LF_COST_c, 0).E;
   if ((uint64_t)B * (uint64_t)E * Ez >= (1ull << 31))
     return fail(ALTRO_HIP_ERR_UNSUPPORTED, "plan LANE: batch %d too large for one handle (dense cost rows exceed 2 GiB)", h->batch);
   if (!h->l_costq) {
     if ((rc = dmalloc(h, &h->l_costq, (size_t)B * (N + 1) * E * Ez))) return rc;
     HIP_TRY(hipMemsetAsync(h->l_costq, 0, (size_t)B * (N + 1) * E * Ez, h->stream));
   }
-  auto pk = [&](const double* src, int len, int off, int nk_host) -> int {   // knot points 0 .. N - 1  (src == NULL: zeros)
-    return h->dtype == ALTRO_HIP_F64 ? lane_pack<double>(h, (double*)h->l_costq, E, src, len, off, 0, N, 0, nk_host, kz, bz, 0)
-                                     : lane_pack<float>(h, (float*)h->l_costq, E, src, len, off, 0, N, 0, nk_host, kz, bz, 0);
-  };
-  auto pk_term = [&](const double* src, int len, int off) -> int {           // record N
-    const size_t base = (size_t)N * E * h->batch;
-    return h->dtype == ALTRO_HIP_F64
-               ? lane_pack<double>(h, (double*)h->l_costq + base, E, src, len, off, 0, 1, kz ? 0 : N, nkx, kz, bz, kz ? len : 0)
-               : lane_pack<float>(h, (float*)h->l_costq + base, E, src, len, off, 0, 1, kz ? 0 : N, nkx, kz, bz, kz ? len : 0);
-  };
-  rc = pk(Q, n * n, 0, nkx);
-  if (!rc) rc = pk(R, m * m, oR, nku);
-  if (!rc) rc = pk(H, m * n, oH, nku);
-  if (!rc) rc = pk(q, n, oq, nkx);
-  if (!rc) rc = pk(r, m, or_, nku);
-  if (!rc) rc = pk(c, 1, oc, nkx);
-  if (!rc) rc = pk_term(Q, n * n, 0);
-  if (!rc) rc = pk_term(q, n, oq);
-  if (!rc) rc = pk_term(c, 1, oc);
+  const CostUpload up[] = {{LF_COST_Q, Q, nkx}, {LF_COST_R, R, nku}, {LF_COST_H, H, nku}, {LF_COST_q, q, nkx}, {LF_COST_r, r, nku}, {LF_COST_c, c, nkx}};   // (c == NULL: zeros)
+  rc = cost_fields_set(h, true, up, 6, kz, bz);
   if (!rc) { h->lqr_cost_set = true; h->cost_set = true; h->dyn_set = true; h->is_diag = 0; h->has_f = 0; h->cost_dense = true; }
   return rc;
 }
@@ -850,27 +778,8 @@ int altro_hip_set_input_guess(altro_hip_batch* h, const double* u, int kz, int b
   if (rc) return rc;
   h->expansion_current = false;
   if (!u) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "u == NULL");
-  const int n = h->n, m = h->m, N = h->N;
-  if (h->plan == ALTRO_HIP_PLAN_GENERIC) {   // candidate inputs: the forward sweep's u array, reference layout
-    if (h->ragged) {   // one packed block per problem
-      if (kz) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "k_stride_zero needs uniform dimensions");
-      const int len = (int)h->g_bstride[G_u];
-      rc = h->dtype == ALTRO_HIP_F64 ? generic_set<double>(h, G_u, u, len, 1, 0, bz) : generic_set<float>(h, G_u, u, len, 1, 0, bz);
-    } else
-    rc = h->dtype == ALTRO_HIP_F64 ? generic_set<double>(h, G_u, u, m, N, kz, bz) : generic_set<float>(h, G_u, u, m, N, kz, bz);
-    if (!rc) h->guess_set = true;
-    return rc;
-  }
-  if (h->plan == ALTRO_HIP_PLAN_MFMA16) {   // candidate records [k][b][28] = x | y | u
-    rc = h->dtype == ALTRO_HIP_F64
-             ? aos_set<double>(h, (double*)h->m_xuy + 24, h->m_st.xuy_bs, h->m_st.xuy_ks, u, m, N, kz, bz)
-             : aos_set<float>(h, (float*)h->m_xuy + 24, h->m_st.xuy_bs, h->m_st.xuy_ks, u, m, N, kz, bz);
-    if (!rc) h->guess_set = true;
-    return rc;
-  }
-  rc = h->dtype == ALTRO_HIP_F64
-           ? lane_pack<double>(h, (double*)h->l_xuy, 2 * n + m, u, m, 2 * n, 0, N, 0, kz ? 1 : N, kz, bz)
-           : lane_pack<float>(h, (float*)h->l_xuy, 2 * n + m, u, m, 2 * n, 0, N, 0, kz ? 1 : N, kz, bz);
+  if (h->ragged && kz) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "k_stride_zero needs uniform dimensions");   // (one packed block per problem)
+  rc = field_set(h, loop_shape(h), LF_CAND_U, 0, h->N, u, kz, bz);
   if (!rc) h->guess_set = true;
   return rc;
 }
@@ -881,20 +790,8 @@ int altro_hip_set_state_guess(altro_hip_batch* h, const double* x, int kz, int b
   if (rc) return rc;
   h->expansion_current = false;
   if (!x) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "x == NULL");
-  const int n = h->n, m = h->m, N = h->N;
-  const bool f64 = h->dtype == ALTRO_HIP_F64;
-  if (h->plan == ALTRO_HIP_PLAN_GENERIC && h->ragged) {   // one packed block per problem
-    if (kz) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "k_stride_zero needs uniform dimensions");
-    const int len = (int)h->g_bstride[G_x];
-    return f64 ? generic_set<double>(h, G_x, x, len, 1, 0, bz) : generic_set<float>(h, G_x, x, len, 1, 0, bz);
-  }
-  if (h->plan == ALTRO_HIP_PLAN_GENERIC)
-    return f64 ? generic_set<double>(h, G_x, x, n, N + 1, kz, bz) : generic_set<float>(h, G_x, x, n, N + 1, kz, bz);
-  if (h->plan == ALTRO_HIP_PLAN_MFMA16)
-    return f64 ? aos_set<double>(h, (double*)h->m_xuy, h->m_st.xuy_bs, h->m_st.xuy_ks, x, n, N + 1, kz, bz)
-               : aos_set<float>(h, (float*)h->m_xuy, h->m_st.xuy_bs, h->m_st.xuy_ks, x, n, N + 1, kz, bz);
-  return f64 ? lane_pack<double>(h, (double*)h->l_xuy, 2 * n + m, x, n, 0, 0, N + 1, 0, kz ? 1 : N + 1, kz, bz)
-             : lane_pack<float>(h, (float*)h->l_xuy, 2 * n + m, x, n, 0, 0, N + 1, 0, kz ? 1 : N + 1, kz, bz);
+  if (h->ragged && kz) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "k_stride_zero needs uniform dimensions");   // (one packed block per problem)
+  return field_set(h, loop_shape(h), LF_CAND_X, 0, h->N + 1, x, kz, bz);
 }
 
 int altro_hip_open_loop_rollout(altro_hip_batch* h) {
@@ -975,89 +872,25 @@ int altro_hip_update_linear_costs(altro_hip_batch* h, const double* q, const dou
   if (rc) return rc;
   h->expansion_current = false;
   if (!h->lqr_cost_set) return fail(ALTRO_HIP_ERR_NOT_SET, "no quadratic cost to update (ErrorCodes::CostNotQuadratic)");
-  const int n = h->n, m = h->m, N = h->N;
+  const int N = h->N;
   if (k_first < 0 || k_last > N || k_first > k_last)
     return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "knot point range [%d, %d] outside [0, %d] (ErrorCodes::BadIndex)", k_first, k_last, N);
   if (r && k_last == N)
     return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "cannot update linear input costs at the terminal knot point "
                                             "(ErrorCodes::InvalidOptAtTerminalKnotPoint)");
   const int nk = k_last - k_first + 1;
-  if (h->plan == ALTRO_HIP_PLAN_GENERIC && h->ragged) {   // per-knot-point dimensions: q [b][sum over the range of nx[k]], r likewise, c [b][nk]
-    if (kz) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "k_stride_zero needs uniform dimensions");
-    const GenSizes gs = gen_sizes(h);
-    int64_t ox = 0, ou = 0, lx = 0, lu = 0;
-    for (int k = 0; k < k_first; ++k) { ox += h->nxv[k]; ou += h->nuv[k]; }
-    for (int k = k_first; k <= k_last; ++k) { lx += h->nxv[k]; if (k < N) lu += h->nuv[k]; }
-    auto put = [&](void* base, int64_t at, int64_t bs, const double* src, int64_t len) -> int {
-      if (!src || len <= 0) return 0;
-      char* dst = (char*)base + (size_t)at * h->esz;
-      return h->dtype == ALTRO_HIP_F64 ? aos_set<double>(h, (double*)dst, bs, bs, src, (int)len, 1, 0, bz)
-                                       : aos_set<float>(h, (float*)dst, bs, bs, src, (int)len, 1, 0, bz);
-    };
-    rc = put(h->g_cq, ox, gs.sx, q, lx);
-    if (!rc) rc = put(h->g_cr, ou, gs.su, r, lu);
-    if (!rc) rc = put(h->g_cc, k_first, N + 1, c, nk);
-    return rc;
+  // per-knot-point dimensions: q [b][sum over the range of nx[k]], r likewise, c [b][nk]
+  if (h->ragged && kz) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "k_stride_zero needs uniform dimensions");
+  const LoopShape s = loop_shape(h);
+  const struct { int field; const double* src; } up[] = {{LF_COST_q, q}, {LF_COST_r, r}, {LF_COST_c, c}};
+  for (const auto& f : up) {
+    if (!f.src) continue;
+    for (int k = k_first; k <= k_last && !rc;) {   // (a run ends where the field changes buffer: q_N of the tile plan's dense cost)
+      const int run = loop_field_run(s, f.field, k, k_last);
+      rc = field_set(h, s, f.field, k, run, f.src, kz, bz, kz ? 1 : nk, kz ? 0 : (k - k_first) * loop_field(s, f.field, k).len);
+      k += run;
+    }
   }
-  if (h->plan == ALTRO_HIP_PLAN_GENERIC) {   // the cost's own q, r, c blocks (dense [b][k][block])
-    auto put = [&](void* base, int blk, int nk_total, const double* src, int nkp) -> int {
-      if (!src || nkp <= 0) return 0;
-      char* dst = (char*)base + (size_t)k_first * blk * h->esz;
-      return h->dtype == ALTRO_HIP_F64
-                 ? aos_set<double>(h, (double*)dst, (int64_t)nk_total * blk, (int64_t)blk, src, blk, nkp, kz, bz, kz ? 1 : nk, 0)
-                 : aos_set<float>(h, (float*)dst, (int64_t)nk_total * blk, (int64_t)blk, src, blk, nkp, kz, bz, kz ? 1 : nk, 0);
-    };
-    rc = put(h->g_cq, n, N + 1, q, nk);
-    if (!rc) rc = put(h->g_cr, m, N, r, nk);
-    if (!rc) rc = put(h->g_cc, 1, N + 1, c, nk);
-    return rc;
-  }
-  if (h->plan == ALTRO_HIP_PLAN_MFMA16 && h->cost_dense) {
-    // the dense cost's record: [q r] at MF_OFF_QR, c in the spare slot; the terminal knot point's q_N lives in costd_term
-    const int64_t B = h->batch;
-    const int nkr = k_last == N ? nk - 1 : nk;    // running knot points in the range
-    auto put = [&](void* base, int64_t bs, int64_t ks, const double* src, int len, int nkp, int src_off) -> int {
-      if (!src || nkp <= 0) return 0;
-      if (h->dtype == ALTRO_HIP_F64) return aos_set<double>(h, (double*)base, bs, ks, src, len, nkp, kz, bz, kz ? 1 : nk, src_off);
-      return aos_set<float>(h, (float*)base, bs, ks, src, len, nkp, kz, bz, kz ? 1 : nk, src_off);
-    };
-    char* cd = (char*)h->m_costd + (size_t)k_first * B * MF_COST * h->esz;
-    rc = put(cd + (size_t)MF_OFF_QR * h->esz, MF_COST, B * MF_COST, q, n, nkr, 0);
-    if (!rc) rc = put(cd + (size_t)(MF_OFF_QR + 12) * h->esz, MF_COST, B * MF_COST, r, m, nkr, 0);
-    if (!rc) rc = put(cd + (size_t)MF_COSTD_C * h->esz, MF_COST, B * MF_COST, c, 1, nk, 0);
-    if (!rc && k_last == N)   // q_N: the last knot point of the host range (or the one shared entry)
-      rc = put((char*)h->m_costd_term + (size_t)144 * h->esz, MF_TERM, 0, q, n, 1, kz ? 0 : (nk - 1) * n);
-    return rc;
-  }
-  if (h->plan == ALTRO_HIP_PLAN_MFMA16) {
-    const int64_t B = h->batch;
-    auto put = [&](const double* src, int len, int off) -> int {
-      if (!src) return 0;
-      if (h->dtype == ALTRO_HIP_F64)
-        return aos_set<double>(h, (double*)h->m_costp + (size_t)k_first * B * MF_COSTP + off, MF_COSTP, B * MF_COSTP, src, len,
-                               nk, kz, bz);
-      return aos_set<float>(h, (float*)h->m_costp + (size_t)k_first * B * MF_COSTP + off, MF_COSTP, B * MF_COSTP, src, len, nk,
-                            kz, bz);
-    };
-    rc = put(q, n, 16);
-    if (!rc) rc = put(r, m, 28);
-    if (!rc) rc = put(c, 1, 32);
-    return rc;
-  }
-  const bool dense = h->cost_dense;
-  const int E = dense ? n * n + m * m + m * n + n + m + 1 : 2 * n + 2 * m + 1;
-  const int oq = dense ? n * n + m * m + m * n : n + m;
-  void* cost = dense ? h->l_costq : h->l_cost;
-  const size_t base = (size_t)k_first * E * h->batch;
-  auto pk = [&](const double* src, int len, int off) -> int {
-    if (!src) return 0;
-    return h->dtype == ALTRO_HIP_F64
-               ? lane_pack<double>(h, (double*)cost + base, E, src, len, off, 0, nk, 0, kz ? 1 : nk, kz, bz)
-               : lane_pack<float>(h, (float*)cost + base, E, src, len, off, 0, nk, 0, kz ? 1 : nk, kz, bz);
-  };
-  rc = pk(q, n, oq);
-  if (!rc) rc = pk(r, m, oq + n);
-  if (!rc) rc = pk(c, 1, oq + n + m);
   return rc;
 }
 int altro_hip_get_knot(altro_hip_batch* h, int k, double* x, double* u) {
@@ -1065,62 +898,14 @@ int altro_hip_get_knot(altro_hip_batch* h, int k, double* x, double* u) {
   // x [batch][n], u [batch][m] (u must be NULL at k = N); per-knot-point dimensions: [batch][nx[k]], [batch][nu[k]]
   int rc = loop_entry(h, true);
   if (rc) return rc;
-  const int n = h->n, m = h->m, N = h->N;
+  const int N = h->N;
   if (k < 0 || k > N) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "knot point %d outside [0, %d] (ErrorCodes::BadIndex)", k, N);
   if (u && k == N) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "no input at the terminal knot point");
-  if (h->plan == ALTRO_HIP_PLAN_MFMA16) {
-    if (!h->m_nom) return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_set_tracking_cost has not been called");
-    const int64_t B = h->batch;
-    if (x) {
-      rc = h->dtype == ALTRO_HIP_F64
-               ? aos_get<double>(h, x, (const double*)h->m_nom + (size_t)k * B * MF_NOM, MF_NOM, B * MF_NOM, n, 1)
-               : aos_get<float>(h, x, (const float*)h->m_nom + (size_t)k * B * MF_NOM, MF_NOM, B * MF_NOM, n, 1);
-      if (rc) return rc;
-    }
-    if (u)
-      rc = h->dtype == ALTRO_HIP_F64
-               ? aos_get<double>(h, u, (const double*)h->m_nom + (size_t)k * B * MF_NOM + 12, MF_NOM, B * MF_NOM, m, 1)
-               : aos_get<float>(h, u, (const float*)h->m_nom + (size_t)k * B * MF_NOM + 12, MF_NOM, B * MF_NOM, m, 1);
-    return rc;
-  }
-  if (h->plan == ALTRO_HIP_PLAN_GENERIC && h->ragged) {
-    if (!h->g_xn) return fail(ALTRO_HIP_ERR_NOT_SET, "no cost has been set for the iLQR loop");
-    const GenSizes gs = gen_sizes(h);
-    int64_t ox = 0, ou = 0;
-    for (int j = 0; j < k; ++j) { ox += h->nxv[j]; ou += h->nuv[j]; }
-    const int nk = h->nxv[k], mk = k < N ? h->nuv[k] : 0;
-    if (x) {
-      rc = h->dtype == ALTRO_HIP_F64 ? aos_get<double>(h, x, (const double*)h->g_xn + ox, gs.sx, nk, nk, 1)
-                                     : aos_get<float>(h, x, (const float*)h->g_xn + ox, gs.sx, nk, nk, 1);
-      if (rc) return rc;
-    }
-    if (u)
-      rc = h->dtype == ALTRO_HIP_F64 ? aos_get<double>(h, u, (const double*)h->g_un + ou, gs.su, mk, mk, 1)
-                                     : aos_get<float>(h, u, (const float*)h->g_un + ou, gs.su, mk, mk, 1);
-    return rc;
-  }
-  if (h->plan == ALTRO_HIP_PLAN_GENERIC) {
-    if (!h->g_xn) return fail(ALTRO_HIP_ERR_NOT_SET, "no cost has been set for the iLQR loop");
-    if (x) {
-      rc = h->dtype == ALTRO_HIP_F64 ? aos_get<double>(h, x, (const double*)h->g_xn + (size_t)k * n, (int64_t)(N + 1) * n, n, n, 1)
-                                     : aos_get<float>(h, x, (const float*)h->g_xn + (size_t)k * n, (int64_t)(N + 1) * n, n, n, 1);
-      if (rc) return rc;
-    }
-    if (u)
-      rc = h->dtype == ALTRO_HIP_F64 ? aos_get<double>(h, u, (const double*)h->g_un + (size_t)k * m, (int64_t)N * m, m, m, 1)
-                                     : aos_get<float>(h, u, (const float*)h->g_un + (size_t)k * m, (int64_t)N * m, m, m, 1);
-    return rc;
-  }
-  const size_t E = h->dtype == ALTRO_HIP_F64 ? 8 : 4;
-  const char* rec = (const char*)h->l_nom + (size_t)k * (n + m) * h->batch * E;
-  if (x) {
-    rc = h->dtype == ALTRO_HIP_F64 ? lane_get<double>(h, x, rec, nullptr, n + m, 0, 0, n, 1, 1)
-                                   : lane_get<float>(h, x, rec, nullptr, n + m, 0, 0, n, 1, 1);
-    if (rc) return rc;
-  }
-  if (u)
-    rc = h->dtype == ALTRO_HIP_F64 ? lane_get<double>(h, u, rec, nullptr, n + m, n, 0, m, 1, 1)
-                                   : lane_get<float>(h, u, rec, nullptr, n + m, n, 0, m, 1, 1);
+  if (h->plan == ALTRO_HIP_PLAN_MFMA16 && !h->m_nom) return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_set_tracking_cost has not been called");
+  if (h->plan == ALTRO_HIP_PLAN_GENERIC && !h->g_xn) return fail(ALTRO_HIP_ERR_NOT_SET, "no cost has been set for the iLQR loop");
+  const LoopShape s = loop_shape(h);
+  if (x && (rc = field_get(h, s, LF_NOM_X, k, 1, x))) return rc;
+  if (u) rc = field_get(h, s, LF_NOM_U, k, 1, u);
   return rc;
 }
 
@@ -1255,18 +1040,14 @@ int altro_hip_get_duals(altro_hip_batch* h, int k, int slot, double* z) {
   const int p = h->al_defs[kn.def[slot]].p;
   const int64_t B = h->batch;
   HIP_TRY(hipStreamSynchronize(h->stream));
-  if (h->dtype == ALTRO_HIP_F64) {
-    std::vector<double> t((size_t)p * B);
-    HIP_TRY(hipMemcpy(t.data(), (const double*)h->al_d_z + (size_t)kn.z_off[slot] * B, t.size() * 8, hipMemcpyDeviceToHost));
+  auto fetch = [&](auto t) -> int {   // device [p][batch] of the handle's element type -> z [batch][p]
+    std::vector<decltype(t)> v((size_t)p * B);
+    HIP_TRY(hipMemcpy(v.data(), (const decltype(t)*)h->al_d_z + (size_t)kn.z_off[slot] * B, v.size() * sizeof(t), hipMemcpyDeviceToHost));
     for (int64_t b = 0; b < B; ++b)
-      for (int r = 0; r < p; ++r) z[(size_t)b * p + r] = t[(size_t)r * B + b];
-  } else {
-    std::vector<float> t((size_t)p * B);
-    HIP_TRY(hipMemcpy(t.data(), (const float*)h->al_d_z + (size_t)kn.z_off[slot] * B, t.size() * 4, hipMemcpyDeviceToHost));
-    for (int64_t b = 0; b < B; ++b)
-      for (int r = 0; r < p; ++r) z[(size_t)b * p + r] = t[(size_t)r * B + b];
-  }
-  return 0;
+      for (int r = 0; r < p; ++r) z[(size_t)b * p + r] = v[(size_t)r * B + b];
+    return 0;
+  };
+  return h->dtype == ALTRO_HIP_F64 ? fetch(double{}) : fetch(float{});
 }
 
 // per-problem results gathered on the device into the struct's own layout: 56 bytes per problem cross PCIe, through pinned memory
@@ -1367,53 +1148,11 @@ int altro_hip_last_solve_counts(const altro_hip_batch* h, int* sweeps, int* meri
 int altro_hip_get_nominal(altro_hip_batch* h, double* x, double* u) {
   int rc = loop_entry(h, true);
   if (rc) return rc;
-  const int n = h->n, m = h->m, N = h->N;
-  if (h->plan == ALTRO_HIP_PLAN_GENERIC && h->ragged) {   // per-knot-point dimensions: packed [batch][sum nx], [batch][sum nu]
-    if (!h->g_xn) return fail(ALTRO_HIP_ERR_NOT_SET, "no cost has been set for the iLQR loop");
-    const GenSizes gs = gen_sizes(h);
-    if (x) {
-      rc = h->dtype == ALTRO_HIP_F64 ? aos_get<double>(h, x, (const double*)h->g_xn, gs.sx, gs.sx, (int)gs.sx, 1)
-                                     : aos_get<float>(h, x, (const float*)h->g_xn, gs.sx, gs.sx, (int)gs.sx, 1);
-      if (rc) return rc;
-    }
-    if (u)
-      rc = h->dtype == ALTRO_HIP_F64 ? aos_get<double>(h, u, (const double*)h->g_un, gs.su, gs.su, (int)gs.su, 1)
-                                     : aos_get<float>(h, u, (const float*)h->g_un, gs.su, gs.su, (int)gs.su, 1);
-    return rc;
-  }
-  if (h->plan == ALTRO_HIP_PLAN_MFMA16) {
-    if (!h->m_nom) return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_set_tracking_cost has not been called");
-    const int64_t B = h->batch;
-    if (x) {
-      rc = h->dtype == ALTRO_HIP_F64 ? aos_get<double>(h, x, (const double*)h->m_nom, MF_NOM, B * MF_NOM, n, N + 1)
-                                     : aos_get<float>(h, x, (const float*)h->m_nom, MF_NOM, B * MF_NOM, n, N + 1);
-      if (rc) return rc;
-    }
-    if (u)
-      rc = h->dtype == ALTRO_HIP_F64 ? aos_get<double>(h, u, (const double*)h->m_nom + 12, MF_NOM, B * MF_NOM, m, N)
-                                     : aos_get<float>(h, u, (const float*)h->m_nom + 12, MF_NOM, B * MF_NOM, m, N);
-    return rc;
-  }
-  if (h->plan == ALTRO_HIP_PLAN_GENERIC) {
-    if (!h->g_xn) return fail(ALTRO_HIP_ERR_NOT_SET, "no cost has been set for the iLQR loop");
-    if (x) {
-      rc = h->dtype == ALTRO_HIP_F64 ? aos_get<double>(h, x, (const double*)h->g_xn, (int64_t)(N + 1) * n, n, n, N + 1)
-                                     : aos_get<float>(h, x, (const float*)h->g_xn, (int64_t)(N + 1) * n, n, n, N + 1);
-      if (rc) return rc;
-    }
-    if (u)
-      rc = h->dtype == ALTRO_HIP_F64 ? aos_get<double>(h, u, (const double*)h->g_un, (int64_t)N * m, m, m, N)
-                                     : aos_get<float>(h, u, (const float*)h->g_un, (int64_t)N * m, m, m, N);
-    return rc;
-  }
-  if (x) {
-    rc = h->dtype == ALTRO_HIP_F64 ? lane_get<double>(h, x, h->l_nom, nullptr, n + m, 0, 0, n, N + 1, N + 1)
-                                   : lane_get<float>(h, x, h->l_nom, nullptr, n + m, 0, 0, n, N + 1, N + 1);
-    if (rc) return rc;
-  }
-  if (u)
-    rc = h->dtype == ALTRO_HIP_F64 ? lane_get<double>(h, u, h->l_nom, nullptr, n + m, n, 0, m, N, N)
-                                   : lane_get<float>(h, u, h->l_nom, nullptr, n + m, n, 0, m, N, N);
+  if (h->plan == ALTRO_HIP_PLAN_MFMA16 && !h->m_nom) return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_set_tracking_cost has not been called");
+  if (h->plan == ALTRO_HIP_PLAN_GENERIC && !h->g_xn) return fail(ALTRO_HIP_ERR_NOT_SET, "no cost has been set for the iLQR loop");
+  const LoopShape s = loop_shape(h);   // (per-knot-point dimensions: packed [batch][sum nx], [batch][sum nu])
+  if (x && (rc = field_get(h, s, LF_NOM_X, 0, h->N + 1, x))) return rc;
+  if (u) rc = field_get(h, s, LF_NOM_U, 0, h->N, u);
   return rc;
 }
 // Expansion the backward pass will consume: A | B | lx | lu (reference layout), for parity tests.
@@ -1427,8 +1166,7 @@ int altro_hip_get_expansion(altro_hip_batch* h, double* A, double* B, double* lx
     std::vector<double> raw;
     auto fetch = [&](const void* src, int64_t bs, int64_t ks, int off, int block, int nk) -> int {
       raw.assign((size_t)B_ * nk * block, 0.0);
-      return h->dtype == ALTRO_HIP_F64 ? aos_get<double>(h, raw.data(), (const double*)src + off, bs, ks, block, nk)
-                                       : aos_get<float>(h, raw.data(), (const float*)src + off, bs, ks, block, nk);
+      return aos_get(h, raw.data(), src, off, bs, ks, block, nk);
     };
     if (A || B) {
       if ((rc = fetch(h->m_in, h->m_st.in_bs, h->m_st.in_ks, MF_OFF_Z, 192, N))) return rc;
@@ -1436,7 +1174,7 @@ int altro_hip_get_expansion(altro_hip_batch* h, double* A, double* B, double* lx
         for (int k = 0; k < N; ++k) {
           const double* zr = raw.data() + ((size_t)b * N + k) * 192;
           if (A) for (int j = 0; j < n; ++j) for (int i = 0; i < n; ++i) A[((size_t)b * N + k) * n * n + i + (size_t)n * j] = zr[i * 16 + j];
-          if (B) for (int j = 0; j < m; ++j) for (int i = 0; i < n; ++i) B[((size_t)b * N + k) * n * m + i + (size_t)n * j] = zr[i * 16 + 12 + j];
+          if (B) for (int j = 0; j < m; ++j) for (int i = 0; i < n; ++i) B[((size_t)b * N + k) * n * m + i + (size_t)n * j] = zr[i * 16 + MF_N + j];
         }
     }
     if (lx || lu) {
@@ -1445,21 +1183,18 @@ int altro_hip_get_expansion(altro_hip_batch* h, double* A, double* B, double* lx
         for (int k = 0; k < N; ++k) {
           const double* qr = raw.data() + ((size_t)b * N + k) * 16;
           if (lx) for (int i = 0; i < n; ++i) lx[((size_t)b * (N + 1) + k) * n + i] = qr[i];
-          if (lu) for (int i = 0; i < m; ++i) lu[((size_t)b * N + k) * m + i] = qr[12 + i];
+          if (lu) for (int i = 0; i < m; ++i) lu[((size_t)b * N + k) * m + i] = qr[MF_N + i];
         }
       if (lx) {
-        if ((rc = fetch(h->m_term, MF_TERM, 0, 144, 12, 1))) return rc;
+        if ((rc = fetch(h->m_term, MF_TERM, 0, MF_TERM_q, MF_N, 1))) return rc;
         for (int64_t b = 0; b < B_; ++b)
-          for (int i = 0; i < n; ++i) lx[((size_t)b * (N + 1) + N) * n + i] = raw[(size_t)b * 12 + i];
+          for (int i = 0; i < n; ++i) lx[((size_t)b * (N + 1) + N) * n + i] = raw[(size_t)b * MF_N + i];
       }
     }
     return 0;
   }
   if (h->plan == ALTRO_HIP_PLAN_GENERIC) {   // reference layout already: A, B as given, lx / lu the backward sweep's q / r
-    auto get = [&](double* dst, int arr, int blk, int nk) -> int {
-      if (!dst) return 0;
-      return h->dtype == ALTRO_HIP_F64 ? generic_get<double>(h, arr, dst, blk, nk) : generic_get<float>(h, arr, dst, blk, nk);
-    };
+    auto get = [&](double* dst, int arr, int blk, int nk) -> int { return dst ? generic_get(h, arr, dst, blk, nk) : 0; };
     rc = get(A, G_A, n * n, N);
     if (!rc) rc = get(B, G_B, n * m, N);
     if (!rc) rc = get(lx, G_q, n, N + 1);
@@ -1470,9 +1205,7 @@ int altro_hip_get_expansion(altro_hip_batch* h, double* A, double* B, double* lx
   const int oq = 2 * n * n + 2 * n * m + m * m + n, orr = oq + n;
   auto get = [&](double* dst, int off, int len, int nk, bool with_term, int off_term) -> int {
     if (!dst) return 0;
-    return h->dtype == ALTRO_HIP_F64
-               ? lane_get<double>(h, dst, h->l_in, with_term ? h->l_term : nullptr, z.e_in, off, off_term, len, nk, N)
-               : lane_get<float>(h, dst, h->l_in, with_term ? h->l_term : nullptr, z.e_in, off, off_term, len, nk, N);
+    return lane_get(h, dst, h->l_in, 0, with_term ? h->l_term : nullptr, z.e_in, off, off_term, len, nk, N);
   };
   rc = get(A, 0, n * n, N, false, 0);
   if (!rc) rc = get(B, n * n, n * m, N, false, 0);

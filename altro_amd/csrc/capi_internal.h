@@ -23,6 +23,7 @@
 #include "kernels/ilqr_generic.hip"
 #include "kernels/mfma16_layout.h"
 #include "linesearch_sm.h"
+#include "loop_fields.h"
 #include "rtc_unit.h"
 
 namespace altro_hip {
@@ -330,6 +331,18 @@ inline int aos_set(altro_hip_batch* h, T* dst, int64_t dst_bs, int64_t dst_ks, c
     return 0;
   });
 }
+// The untyped entry points below are the ONLY places that choose the element type of a transfer: `base` is a buffer of the handle's
+// dtype, `off` counts its elements.
+inline int aos_set(altro_hip_batch* h, void* base, int64_t off, int64_t dst_bs, int64_t dst_ks, const double* host, int block, int nk,
+                   int k_zero, int b_zero, int nk_host = -1, int src_off = 0) {
+  return h->dtype == ALTRO_HIP_F64 ? aos_set<double>(h, (double*)base + off, dst_bs, dst_ks, host, block, nk, k_zero, b_zero, nk_host, src_off)
+                                   : aos_set<float>(h, (float*)base + off, dst_bs, dst_ks, host, block, nk, k_zero, b_zero, nk_host, src_off);
+}
+inline int generic_set(altro_hip_batch* h, int arr, const double* host, int block, int nk, int k_zero, int b_zero, int k0 = 0,
+                       int nk_host = -1, int src_off = 0) {
+  return h->dtype == ALTRO_HIP_F64 ? generic_set<double>(h, arr, host, block, nk, k_zero, b_zero, k0, nk_host, src_off)
+                                   : generic_set<float>(h, arr, host, block, nk, k_zero, b_zero, k0, nk_host, src_off);
+}
 // Download: run `produce(dst_device, b0, nb)` chunk by chunk into staging, then copy to the host.
 template <typename F>
 inline int download_chunks(altro_hip_batch* h, double* host, int block, int nk, F produce) {
@@ -378,6 +391,14 @@ inline int generic_get(altro_hip_batch* h, int arr, double* host, int block, int
     if (e != hipSuccess) return fail(ALTRO_HIP_ERR_HIP, "gather_copy launch: %s", hipGetErrorString(e));
     return 0;
   });
+}
+
+inline int aos_get(altro_hip_batch* h, double* host, const void* base, int64_t off, int64_t src_bs, int64_t src_ks, int block, int nk) {
+  return h->dtype == ALTRO_HIP_F64 ? aos_get<double>(h, host, (const double*)base + off, src_bs, src_ks, block, nk)
+                                   : aos_get<float>(h, host, (const float*)base + off, src_bs, src_ks, block, nk);
+}
+inline int generic_get(altro_hip_batch* h, int arr, double* host, int block, int nk) {
+  return h->dtype == ALTRO_HIP_F64 ? generic_get<double>(h, arr, host, block, nk) : generic_get<float>(h, arr, host, block, nk);
 }
 
 inline int mfma16_get(altro_hip_batch* h, int what, double* host, int block, int nk) {
@@ -483,6 +504,58 @@ inline int lane_get(altro_hip_batch* h, double* host, const void* src, const voi
     if (hipGetLastError() != hipSuccess) return fail(ALTRO_HIP_ERR_HIP, "lane_unpack launch failed");
     return 0;
   });
+}
+
+// (`off`: elements from `base` to the first record written / read; the terminal record, if any, is a buffer of its own)
+inline int lane_pack(altro_hip_batch* h, void* base, int64_t off, int E, const double* host, int len, int dst_off, int diag_n, int nk,
+                     int k_src0, int nk_host, int kz, int bz, int src_off = 0) {
+  return h->dtype == ALTRO_HIP_F64 ? lane_pack<double>(h, (double*)base + off, E, host, len, dst_off, diag_n, nk, k_src0, nk_host, kz, bz, src_off)
+                                   : lane_pack<float>(h, (float*)base + off, E, host, len, dst_off, diag_n, nk, k_src0, nk_host, kz, bz, src_off);
+}
+inline int lane_get(altro_hip_batch* h, double* host, const void* base, int64_t off, const void* src_term, int E, int rec_off, int off_term,
+                    int len, int nk, int nk_main) {
+  return h->dtype == ALTRO_HIP_F64 ? lane_get<double>(h, host, (const double*)base + off, src_term, E, rec_off, off_term, len, nk, nk_main)
+                                   : lane_get<float>(h, host, (const float*)base + off, src_term, E, rec_off, off_term, len, nk, nk_main);
+}
+
+// ---- the iLQR loop's fields (loop_fields.h says where each lives) ---------------------------------------------
+inline LoopShape loop_shape(const altro_hip_batch* h) {
+  return LoopShape{h->plan, h->ragged, h->cost_dense, h->n, h->m, h->N, h->batch, h->m_st.xuy_bs, h->m_st.xuy_ks, h->nxv.data(), h->nuv.data()};
+}
+inline void* loop_buffer(const altro_hip_batch* h, int buf) {
+  void* const p[] = {nullptr, h->g_arr[G_x], h->g_arr[G_u], h->g_xn, h->g_un, h->g_cQ, h->g_cR, h->g_cH, h->g_cq, h->g_cr, h->g_cc,
+                     h->m_xuy, h->m_nom, h->m_costp, h->m_costd, h->m_costd_term, h->l_xuy, h->l_nom, h->l_cost, h->l_costq};
+  return p[buf];
+}
+// knot points k0 .. k0 + nk - 1 of one field <- a reference-layout host array of nk_host (default: 1 with kz, else nk) knot points per
+// problem, read from element src_off on.  Each kind keeps its transport: lane_pack / put_src (whole arrays, honours host-batch
+// tiling), aos_set / upload_chunks (staged in chunks; the candidate arrays of plan GENERIC refuse tiling like generic_set does).
+inline int ref_set(altro_hip_batch* h, const FieldRef& r, int k0, int nk, const double* host, int kz, int bz, int nk_host = -1, int src_off = 0) {
+  if (r.kind == LK_LANE)
+    return lane_pack(h, loop_buffer(h, r.buf), k0 * r.ks, r.E, host, r.len, (int)r.off, 0, nk, 0, nk_host < 0 ? (kz ? 1 : nk) : nk_host, kz, bz, src_off);
+  if ((r.buf == LB_G_X || r.buf == LB_G_U) && h->host_batch > 0 && h->host_batch < h->batch && !bz)
+    return fail(ALTRO_HIP_ERR_UNSUPPORTED, "altro_hip_set_host_batch tiling is not available on plan GENERIC");
+  return aos_set(h, loop_buffer(h, r.buf), r.off, r.bs, r.ks, host, r.len, nk, kz, bz, nk_host, src_off);
+}
+// (per-knot-point dimensions: the blocks of a run of knot points lie back to back and move as ONE block per problem)
+inline FieldRef field_run(const LoopShape& s, int field, int k0, int* nk, int* nk_host = nullptr) {
+  FieldRef r = loop_field(s, field, k0);
+  if (s.ragged) {
+    const FieldRef last = loop_field(s, field, k0 + *nk - 1);
+    r.len = (int)(last.off + last.len - r.off); r.ks = r.len; *nk = 1;
+    if (nk_host) *nk_host = -1;
+  }
+  return r;
+}
+inline int field_set(altro_hip_batch* h, const LoopShape& s, int field, int k0, int nk, const double* host, int kz, int bz, int nk_host = -1,
+                     int src_off = 0) {
+  const FieldRef r = field_run(s, field, k0, &nk, &nk_host);
+  return r.len > 0 ? ref_set(h, r, k0, nk, host, kz, bz, nk_host, src_off) : 0;
+}
+inline int field_get(altro_hip_batch* h, const LoopShape& s, int field, int k0, int nk, double* host) {
+  const FieldRef r = field_run(s, field, k0, &nk);
+  if (r.kind == LK_LANE) return lane_get(h, host, loop_buffer(h, r.buf), k0 * r.ks, nullptr, r.E, (int)r.off, 0, r.len, nk, nk);
+  return aos_get(h, host, loop_buffer(h, r.buf), r.off, r.bs, r.ks, r.len, nk);
 }
 
 constexpr int kCounterSlots = 2048;   // counter slots of one handle (altro_hip_batch::i_counters)

@@ -137,7 +137,7 @@ int SolveRun::configure(const altro_hip_solve_options* opts) {
   h->spec_beta = la.ls.beta_decrease; h->spec_max_iters = la.ls.max_iters;
   lane_plan = h->plan == ALTRO_HIP_PLAN_LANE;
   generic_plan = h->plan == ALTRO_HIP_PLAN_GENERIC;   // (constraint rows in their one-wave-per-knot-point form: no merged end pass)
-  const int64_t cand_elems = (int64_t)h->batch * (h->N + 1) * (lane_plan ? lane_sizes(h->n, h->m).e_xuy : 28);
+  const int64_t cand_elems = (int64_t)h->batch * (h->N + 1) * (lane_plan ? lane_sizes(h->n, h->m).e_xuy : MF_XUY);
   spare_each = (size_t)cand_elems * h->esz;   // one spare candidate trajectory
   trials_cap = spec_trials_cap(h);
   // speculative backtracking: how much of the chip the searching problems occupy, and how much there is

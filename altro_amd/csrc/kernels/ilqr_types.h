@@ -6,6 +6,7 @@
 #include "../linesearch_sm.h"
 #include "../models.h"
 #include "al_types.h"
+#include "mfma16_layout.h"
 
 namespace altro_hip {
 
@@ -130,8 +131,7 @@ struct IlqrLoopArgs {
 };
 
 // ---- plan MFMA16 ((12, 4), wave per problem, dynamics given as data): kernels/ilqr_mfma16.hip ----------------
-constexpr int MF_NOM = 16;     // nominal record: x 12 | u 4
-constexpr int MF_COSTP = 36;   // cost-parameter record: Qd 12 | Rd 4 | q 12 | r 4 | c 1 | pad 3
+// (record sizes and sub-offsets MF_NOM*, MF_COSTP*, MF_COSTD_C: mfma16_layout.h)
 
 template <typename S>
 struct IlqrWaveArgs {
@@ -176,7 +176,6 @@ struct IlqrWaveArgs {
   int* aff_on = nullptr;                     // [ILQR_SPEC_TRIALS][b]
   int aff = 0;                               // IK_MERIT: launch the affine form
 };
-constexpr int MF_COSTD_C = 78;    // the constant term c inside a dense cost record (the first pad slot of the COST layout)
 constexpr int ROLLOUT_INIT = 4;   // wave_rollout_kernel also writes the nominal record and the cost gradient (the head of
                                   // Solve for an unconstrained problem: rollout + CopyTrajectory + expansion in one pass)
 

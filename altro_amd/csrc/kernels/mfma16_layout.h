@@ -19,6 +19,15 @@ constexpr int MF_OFF_Z = 0, MF_OFF_F = 192;                   // inside a dynami
 constexpr int MF_OFF_Q = 0, MF_OFF_HR = 80, MF_OFF_QR = 144;  // inside a cost record
 constexpr int MF_OFF_P = 52, MF_OFF_p = 130, MF_OFF_PAD = 142;   // inside an OUT record, after Kt = [K | -d] 4x13
 constexpr int MF_QB = 256 + 16;  // optional Q-block record: G tile (16x16 row-major) | [Qx Qu]
+constexpr int MF_TERM_q = 144;                                 // inside a TERM record: Q_N rows 144 | q_N 12
+constexpr int MF_XUY = 28;     // elements per candidate record:            x 12 | y 12 | u 4
+constexpr int MF_XUY_X = 0, MF_XUY_Y = 12, MF_XUY_U = 24;
+// the iLQR loop's own records (kernels/ilqr_mfma16.hip), [k][b][record]
+constexpr int MF_NOM = 16;     // nominal record: x 12 | u 4
+constexpr int MF_NOM_X = 0, MF_NOM_U = 12;
+constexpr int MF_COSTP = 36;   // cost-parameter record: Qd 12 | Rd 4 | q 12 | r 4 | c 1 | pad 3
+constexpr int MF_COSTP_QD = 0, MF_COSTP_RD = 12, MF_COSTP_q = 16, MF_COSTP_r = 28, MF_COSTP_c = 32;
+constexpr int MF_COSTD_C = 78; // the constant term c inside a dense cost record (the first pad slot of the COST layout)
 
 // offset of entry (i, j) of a symmetric 12 x 12 block inside its packed upper triangle (row-major: row i holds
 // columns i..11); every record is a multiple of 64 bytes, so no two problems' records share a cache line.
