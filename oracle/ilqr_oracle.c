@@ -753,6 +753,21 @@ void oracle_ilqr_refresh_expansions(void* h) {
   }
 }
 
+/* ConstraintValues' z_ and rho_ of block `block` at knot point k (knotpoint_data.hpp: the duals and the penalty the
+ * AL terms are built from).  Returns the block's dimension p (-1: no such block); out may be NULL. */
+int oracle_ilqr_get_duals(void* h, int k, int block, double* out) {
+  oracle_ilqr* s = (oracle_ilqr*)h;
+  if (k < 0 || k > s->N || block < 0 || block >= s->cons[k].ncon) return -1;
+  const oracle_con* c = &s->cons[k].con[block];
+  if (out) memcpy(out, c->z, sizeof(double) * c->p);
+  return c->p;
+}
+double oracle_ilqr_get_penalty(void* h, int k, int block) {
+  oracle_ilqr* s = (oracle_ilqr*)h;
+  if (k < 0 || k > s->N || block < 0 || block >= s->cons[k].ncon) return NAN;
+  return s->cons[k].con[block].rho;
+}
+
 int oracle_ilqr_iterations(void* h) { return ((oracle_ilqr*)h)->iterations; }
 int oracle_ilqr_merit_evals(void* h) { return ((oracle_ilqr*)h)->n_merit_evals; }
 double oracle_ilqr_delta_V(void* h, int i) { return ((oracle_ilqr*)h)->delta_V[i]; }

@@ -111,6 +111,12 @@ def lib():
             getattr(L, "oracle_ilqr_" + name).argtypes = [C.c_void_p]
             getattr(L, "oracle_ilqr_" + name).restype = None
         L.oracle_ilqr_feasibility.restype = C.c_double
+        L.oracle_ilqr_get_duals.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.oracle_ilqr_get_duals.restype = C.c_int
+        L.oracle_ilqr_get_penalty.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.oracle_ilqr_get_penalty.restype = C.c_double
+        L.oracle_al_knot_eval.restype = C.c_double
+        L.oracle_al_knot_eval.argtypes = [C.c_int] * 4 + [C.c_void_p] * 5 + [C.c_double] + [C.c_void_p] * 7
         L.oracle_cone_projection.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.oracle_cone_jacobian.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.oracle_cone_hessian.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -265,6 +271,20 @@ class ILQR:
 
     def feasibility(self):
         return self.L.oracle_ilqr_feasibility(self.h)
+
+    def duals(self, k, block):
+        """The duals z of constraint block `block` (in the order it was added) at knot point k, [p]."""
+        p = self.L.oracle_ilqr_get_duals(self.h, int(k), int(block), None)
+        assert p >= 0, "no constraint block %d at knot point %d" % (block, k)
+        out = np.zeros(p)
+        self.L.oracle_ilqr_get_duals(self.h, int(k), int(block), _p(out))
+        return out
+
+    def penalty(self, k, block):
+        """The penalty rho of constraint block `block` at knot point k."""
+        rho = self.L.oracle_ilqr_get_penalty(self.h, int(k), int(block))
+        assert rho == rho, "no constraint block %d at knot point %d" % (block, k)
+        return rho
 
     def solve(self, log_cap=256):
         log = np.zeros((log_cap, 8))   # alpha, phi0, phi, dphi0, stationarity, ls_iters, feasibility, rho

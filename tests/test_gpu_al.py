@@ -10,6 +10,7 @@ from oracle import oracle
 from tests import problems
 
 pytestmark = pytest.mark.gpu
+DUALS_TOL = 1e-12      # relative to the block's largest dual (at least 1): tests/test_gpu_cone_regions.py's, measured 1.5e-14 there
 
 
 def _di_hip(kats, kind, x0s):
@@ -99,25 +100,37 @@ def test_constrained_batch_matches_per_problem_oracle(kats, kind):
 
 
 def test_al_merit_and_expansion_parity(kats):
-    """CalcCost / CalcCostGradient / CalcCostHessian with AL terms (knotpoint_data.cpp:421-448, :572-613) at a
-    point with nonzero duals: run two sweeps on both sides, then compare phi, dphi, lx, lu."""
+    """CalcCost / CalcCostGradient / CalcCostHessian with AL terms (knotpoint_data.cpp:421-448, :572-613): run two sweeps on both
+    sides, then compare lx, lu, the trajectory, feasibility and the duals; then four sweeps, after which the oracle has taken a dual
+    update (asserted): the point has nonzero duals, and they are the oracle's (DUALS_TOL)."""
     kind = "soc"
     c = kats["double_integrator_constrained"][kind]
+    N = kats["double_integrator_constrained"]["N"]
     x0s = np.tile(np.array(c["x0"], dtype=float), (4, 1))
     x0s[1] += [0.1, -0.2, 0.05, 0.0]
-    bt, kat, xf = _di_hip(kats, kind, x0s)
-    res = bt.ilqr_solve(penalty_initial=1.0, penalty_scaling=100.0, iterations_max=2)
-    for b in [0, 1]:
-        s = _di_oracle(kats, kind, x0s[b])
-        s.L.oracle_ilqr_set_options(s.h, 2, 1e-4, 1e-4, 1e-8, 0)
-        s.solve()
-        A, B, lx, lu = bt.get_expansion()
-        np.testing.assert_allclose(lx[b], s.get("lx"), rtol=1e-9, atol=1e-9)
-        np.testing.assert_allclose(lu[b], s.get("lu"), rtol=1e-9, atol=1e-9)
-        np.testing.assert_allclose(bt.get("x")[b], s.get("x"), rtol=1e-10, atol=1e-10)
-        assert abs(res["feasibility"][b] - s.feasibility()) < 1e-10
-        z_dev = bt.get_duals(0, 0, 3)[b]
-        assert np.isfinite(z_dev).all()
+    worst = 0.0
+    for sweeps in (2, 4):
+        bt, kat, xf = _di_hip(kats, kind, x0s)
+        res = bt.ilqr_solve(penalty_initial=1.0, penalty_scaling=100.0, iterations_max=sweeps)
+        for b in [0, 1]:
+            s = _di_oracle(kats, kind, x0s[b])
+            s.set_penalty(1.0, 100.0)
+            s.L.oracle_ilqr_set_options(s.h, sweeps, 1e-4, 1e-4, 1e-8, 0)
+            s.solve()
+            A, B, lx, lu = bt.get_expansion()
+            np.testing.assert_allclose(lx[b], s.get("lx"), rtol=1e-9, atol=1e-9)
+            np.testing.assert_allclose(lu[b], s.get("lu"), rtol=1e-9, atol=1e-9)
+            np.testing.assert_allclose(bt.get("x")[b], s.get("x"), rtol=1e-10, atol=1e-10)
+            assert abs(res["feasibility"][b] - s.feasibility()) < 1e-10
+            moved = 0.0
+            for k in range(N):
+                z_dev, z_ref = bt.get_duals(k, 0, 3)[b], s.duals(k, 0)
+                assert np.abs(z_dev - z_ref).max() <= DUALS_TOL * max(1.0, np.abs(z_ref).max()), (sweeps, b, k, z_dev, z_ref)
+                moved = max(moved, np.abs(z_ref).max())
+                worst = max(worst, np.abs(z_dev - z_ref).max() / max(1.0, np.abs(z_ref).max()))
+            assert (moved > 0.1) == (sweeps == 4) and res["penalty"][b] == s.penalty(0, 0)
+        bt.close()
+    print("duals against the oracle, worst relative error %.1e" % worst)
 
 
 def test_pendulum_goal_constraint_on_device(kats):

@@ -168,12 +168,15 @@ def test_constrained_solves_generic(n, m, dense, soc, backtracking):
     res = bt.ilqr_solve(iterations_max=60, penalty_initial=1.0, penalty_scaling=10.0, use_backtracking=backtracking)
     x, u = bt.get_nominal()
     assert (res["dual_updates"] > 0).all()
+    duals = {(k, slot): bt.get_duals(k, slot, bl[3].shape[0]) for k in range(N + 1)
+             for slot, bl in enumerate([bl for bl in blocks if bl[0] <= k <= bl[1]])}
     nconv = 0
     for b in [0, 4, 8]:
         s = make_oracle(p, b, N, n, m, dense)
-        for (k0, k1, cone, G, g) in blocks:
-            for k in range(k0, k1 + 1):
-                s.add_linear_constraint(k, cone, G, g)
+        for k in range(N + 1):                # (per knot point in the order the blocks are registered: the handle's block order)
+            for (k0, k1, cone, G, g) in blocks:
+                if k0 <= k <= k1:
+                    s.add_linear_constraint(k, cone, G, g)
         s.L.oracle_ilqr_initialize(s.h)
         for k in range(N):
             s.L.oracle_ilqr_set_input(s.h, k, np.ascontiguousarray(p["u0"][b, k]))
@@ -188,6 +191,13 @@ def test_constrained_solves_generic(n, m, dense, soc, backtracking):
         np.testing.assert_allclose(x[b], s.get("x"), rtol=1e-7, atol=1e-7)
         np.testing.assert_allclose(u[b], s.get("u"), rtol=1e-6, atol=1e-6)
         assert np.abs(u[b][:, :4]).max() <= 0.3 + 2e-4 and abs(u[b][0, 0] - 0.05) < 2e-4
+        zmax = 0.0
+        for k in range(N + 1):                # the duals of every block (slot: its place among the blocks of knot point k, as registered)
+            for slot, (k0, k1, cone, G, g) in enumerate([bl for bl in blocks if bl[0] <= k <= bl[1]]):
+                z_ref = s.duals(k, slot)
+                np.testing.assert_allclose(duals[(k, slot)][b], z_ref, rtol=1e-6, atol=1e-6, err_msg="duals b %d k %d block %d" % (b, k, slot))
+                zmax = max(zmax, np.abs(z_ref).max())
+        assert zmax > 1e-3                    # (they moved)
     assert nconv >= 1
     assert (bt.feasibility() >= 0.0).all()
     z = bt.get_duals(0, 0, 8)

@@ -628,3 +628,64 @@ def test_quaternion_quadrotor_test_model_jacobian_by_central_differences():
     out = np.zeros(n)
     L.oracle_discrete_dynamics(C.byref(mdl), out, hover_x, hover_u, h)
     assert np.abs(out - hover_x).max() < 1e-15
+
+
+def test_dual_and_penalty_getters():
+    """ILQR.duals / ILQR.penalty: after oracle_ilqr_dual_update the duals of a block are the projection of z - rho c onto the block's
+    DUAL cone (knotpoint_data.cpp:503-510, :523-535; z = 0 and rho = 1 before the first update), for every cone type; the second
+    update starts from the first one's duals; oracle_ilqr_penalty_update moves rho by the scaling (:512-517)."""
+    N, n, m = 3, 4, 2
+    w = n + m
+    rng = np.random.default_rng(5)
+    s = oracle.ILQR(N, n, m, 0.1, oracle.DYN_MODEL, oracle.MODEL_DI, model_dim=2, cost_kind=oracle.COST_DIAGONAL)
+    L = s.L
+    for k in range(N + 1):
+        L.oracle_ilqr_set_lqr_cost(s.h, k, np.ones(n), np.ones(m), np.zeros(n), np.zeros(m))
+    L.oracle_ilqr_set_initial_state(s.h, np.array([1.0, -0.5, 0.3, 0.2]))
+    dual = {oracle.CONE_EQUALITY: oracle.CONE_IDENTITY, oracle.CONE_IDENTITY: oracle.CONE_EQUALITY,
+            oracle.CONE_INEQUALITY: oracle.CONE_INEQUALITY, oracle.CONE_SOC: oracle.CONE_SOC}
+    blocks = [(cone, rng.normal(size=(3, w)), rng.normal(size=3)) for cone in sorted(dual)]
+    for k in range(N):
+        for (cone, G, g) in blocks:
+            s.add_linear_constraint(k, cone, G, g)
+    s.add_linear_constraint(N, oracle.CONE_SOC, blocks[3][1], blocks[3][2])
+    L.oracle_ilqr_initialize(s.h)
+    for k in range(N):
+        L.oracle_ilqr_set_input(s.h, k, rng.normal(size=m))
+    s.set_penalty(1.0, 10.0)
+    L.oracle_ilqr_open_loop_rollout(s.h); L.oracle_ilqr_copy_trajectory(s.h)
+    x, u = s.get("x"), np.vstack([s.get("u"), np.zeros((1, m))])
+
+    def expected(k, cone, G, g, z, rho):
+        v = np.concatenate([x[k], u[k]])
+        val = np.zeros(3)
+        for i in range(3):                            # the oracle's order of summation: equality below is bit for bit
+            acc = 0.0
+            for e in range(w):
+                acc += G[i, e] * v[e]
+            val[i] = acc - g[i]
+        ze = z - rho * val
+        out = np.zeros(3)
+        L.oracle_cone_projection(dual[cone], 3, ze.ctypes.data, out.ctypes.data)
+        return out
+
+    where = [(k, j, blocks[j]) for k in range(N) for j in range(4)] + [(N, 0, blocks[3])]
+    assert all(np.array_equal(s.duals(k, j), np.zeros(3)) and s.penalty(k, j) == 1.0 for (k, j, _) in where)
+    L.oracle_ilqr_calc_cost(s.h)                      # constraint values and projected duals of the trajectory
+    L.oracle_ilqr_dual_update(s.h)
+    first = {}
+    moved = {cone: 0.0 for cone in dual}
+    for (k, j, (cone, G, g)) in where:
+        first[(k, j)] = s.duals(k, j)
+        assert np.array_equal(first[(k, j)], expected(k, cone, G, g, np.zeros(3), 1.0)), (k, j)
+        moved[cone] = max(moved[cone], np.abs(first[(k, j)]).max())
+    assert moved[oracle.CONE_IDENTITY] == 0.0 and all(v > 0.0 for c, v in moved.items() if c != oracle.CONE_IDENTITY), moved
+    L.oracle_ilqr_penalty_update(s.h)
+    assert all(s.penalty(k, j) == 10.0 for (k, j, _) in where)
+    L.oracle_ilqr_calc_cost(s.h)
+    L.oracle_ilqr_dual_update(s.h)
+    for (k, j, (cone, G, g)) in where:
+        assert np.array_equal(s.duals(k, j), expected(k, cone, G, g, first[(k, j)], 10.0)), (k, j)
+    L.oracle_ilqr_penalty_update(s.h)
+    assert all(s.penalty(k, j) == 100.0 for (k, j, _) in where)
+    assert L.oracle_ilqr_get_duals(s.h, N, 1, None) == -1 and np.isnan(L.oracle_ilqr_get_penalty(s.h, N + 1, 0))
