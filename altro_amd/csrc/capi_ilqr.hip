@@ -30,7 +30,9 @@ int al_upload_typed(altro_hip_batch* h) {
   h->al_Gpad_count = 0;
   for (void** p : {(void**)&h->al_d_knots, (void**)&h->al_d_big, (void**)&h->al_d_gsel, (void**)&h->al_d_guser, &h->al_d_G, &h->al_d_Gpad, &h->al_d_g, &h->al_d_z})
     if (*p) { (void)hipFree(*p); *p = nullptr; }
+  h->al_has_user = false;
   if (h->al_defs.empty()) { h->al_rows = 0; return 0; }
+  for (const AlDef& d : h->al_defs) if (d.user) h->al_has_user = true;
   // G on the device: p x (n + m) column-major as given on plan LANE; on plan MFMA16 p x 16 in the tile's own column order
   // (states in columns 0..11, inputs in 12..15), so that a padded shape's blocks address the padded [x; u] correctly
   const bool tile = h->plan == ALTRO_HIP_PLAN_MFMA16;
@@ -42,6 +44,10 @@ int al_upload_typed(altro_hip_batch* h) {
   auto nslots = [&](const AlDef& d) { return (tile && d.cone != CONE_SOC) ? (d.p + AL_MAXP - 1) / AL_MAXP : 1; };
   std::vector<int> slot_base(h->al_defs.size() + 1, 0);
   for (size_t i = 0; i < h->al_defs.size(); ++i) slot_base[i + 1] = slot_base[i] + nslots(h->al_defs[i]);
+  // ... and gp_base[i] its first entry in the zero-padded pool Gpad (AL_TILE_MAXSLOTDEF of them): a block from the caller's source has
+  // none -- its Jacobian is evaluated at every point (kernels/ilqr_merit2_dpp.hip, MD_USER_BLOCKS)
+  std::vector<int> gp_base(h->al_defs.size() + 1, 0);
+  for (size_t i = 0; i < h->al_defs.size(); ++i) gp_base[i + 1] = gp_base[i] + (h->al_defs[i].user ? 0 : nslots(h->al_defs[i]));
   std::vector<T> G;
   std::vector<int> G_off_dev(tile ? (size_t)slot_base.back() : h->al_defs.size(), 0);   // plan MFMA16: per slot definition
   for (size_t i = 0; i < h->al_defs.size(); ++i) {
@@ -69,13 +75,13 @@ int al_upload_typed(altro_hip_batch* h) {
   }
   std::vector<T> Gpad;   // the same slots zero-padded for the row-layout kernels (al_types.h: AL_GP_DEF)
   if (tile) {
-    Gpad.assign((size_t)slot_base.back() * (size_t)AL_GP_DEF, (T)0);
+    Gpad.assign((size_t)gp_base.back() * (size_t)AL_GP_DEF, (T)0);
     for (size_t i = 0; i < h->al_defs.size(); ++i) {
       const AlDef& d0 = h->al_defs[i];
       if (d0.user) continue;
       for (int e = 0; e < w_log; ++e)
         for (int r = 0; r < d0.p; ++r)
-          Gpad[(size_t)(slot_base[i] + r / AL_MAXP) * AL_GP_DEF + (size_t)(r % AL_MAXP) * AL_GP_LD + dev_col(e)] =
+          Gpad[(size_t)(gp_base[i] + r / AL_MAXP) * AL_GP_DEF + (size_t)(r % AL_MAXP) * AL_GP_LD + dev_col(e)] =
               (T)h->al_G[(size_t)d0.G_off + r + (size_t)e * d0.p];
     }
   }
@@ -119,7 +125,7 @@ int al_upload_typed(altro_hip_batch* h) {
         kn.G_off[ns] = tile ? G_off_dev[(size_t)slot_base[bk.def[j]] + sl] : G_off_dev[bk.def[j]];
         kn.g_off[ns] = d.g_off + (d.g_per_problem ? (int64_t)r0 * B : (int64_t)r0);   // g is [p] or [p][batch]: row r0 on
         kn.user[ns] = d.user;
-        kn.Gp_off[ns] = tile ? (slot_base[bk.def[j]] + sl) * AL_GP_DEF : 0;
+        kn.Gp_off[ns] = (tile && !d.user) ? (gp_base[bk.def[j]] + sl) * AL_GP_DEF : 0;
         // bound-type slot: every row of G is +-e_idx
         bool sel = d.cone != CONE_SOC;
         for (int r = 0, at, sg; r < ps && sel; ++r) {
@@ -287,6 +293,11 @@ int wave_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int
   IlqrWaveArgs<S> a;
   a.al = al_table<S>(h);
   a.mode = mode;
+  // a slot from the caller's source (altro_hip_add_user_constraint): evaluated by the row-layout kernels of the run-time module only
+  const bool user_al = a.al.enabled && h->al_has_user;
+  if (user_al && (h->forms & (ALTRO_HIP_FORM_MERIT_LDS | ALTRO_HIP_FORM_ALROWS_LDS | ALTRO_HIP_FORM_EXPAND_LDS)))
+    return fail(ALTRO_HIP_ERR_UNSUPPORTED, "constraint blocks from source on plan MFMA16 run in the row-layout kernels only: the LDS comparison forms "
+                                           "(ALTRO_HIP_FORM_MERIT_LDS, _ALROWS_LDS, _EXPAND_LDS) do not evaluate them");
   a.penalty_scaling = h->expand_penalty_scaling; a.penalty_max = h->expand_penalty_max;
   if (which == IK_STATIONARITY || which == IK_DUAL)   // constraint rows in the DPP form unless ALTRO_HIP_FORM_ALROWS_LDS
     a.mode = form(h, ALTRO_HIP_FORM_ALROWS_LDS) ? 0 : STAT_NO_FEAS;
@@ -327,6 +338,14 @@ int wave_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int
       if (which == IK_EXPAND && (a.mode & EXPAND_DYN)) {
         const int rcm = rtc_tile_launch(h, IK_EXPAND, a);
         if (rcm) return rcm;
+      }
+      if (user_al && (which == IK_EXPAND || which == IK_DUAL)) return rtc_tile_al_launch(h, which, a);   // (IK_EXPAND: the cost's terms included)
+      if (user_al && which == IK_STATIONARITY) {   // the residual from the library's kernel (it reads no constraint data), then the rows' walk
+        a.mp.kind = MODEL_LINEAR;
+        a.mode |= STAT_FEAS_USER;
+        const int rcs = ilqr_wave_launch_kernel<S>(h->stream, which, a);
+        if (rcs) return fail(ALTRO_HIP_ERR_HIP, "iLQR kernel launch failed");
+        return rtc_tile_al_launch(h, which, a);
       }
     }
     a.mp.kind = MODEL_LINEAR;   // (what follows are the cost kernels: none of them steps the dynamics)
@@ -909,8 +928,9 @@ int altro_hip_get_knot(altro_hip_batch* h, int k, double* x, double* u) {
   return rc;
 }
 
-int altro_hip_add_linear_constraint(altro_hip_batch* h, int k_first, int k_last, int cone, int p, const double* G,
-                                    const double* g, int g_per_problem) {
+// One more block on the handle's host tables: altro_hip_add_linear_constraint (user = 0), or altro_hip_add_user_constraint with
+// user = id + 1 and placeholders for G and g (AlDef::user)
+static int add_block(altro_hip_batch* h, int k_first, int k_last, int cone, int p, const double* G, const double* g, int g_per_problem, int user) {
   // ALTROSolver::SetConstraint (altro_solver.cpp:175-215) for c(x,u) = G [x;u] - g
   int rc = loop_entry(h, true);
   if (rc) return rc;
@@ -931,8 +951,8 @@ int altro_hip_add_linear_constraint(altro_hip_batch* h, int k_first, int k_last,
     return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "knot point range [%d, %d] outside [0, %d] (ErrorCodes::BadIndex)", k_first, k_last, h->N);
   auto slots_of = [&](int cn, int rows) { return cn == CONE_SOC ? 1 : (rows + AL_MAXP - 1) / AL_MAXP; };
   if (tile) {   // slots: per knot point and per handle
-    int defslots = slots_of(cone, p);
-    for (const AlDef& d0 : h->al_defs) defslots += slots_of(d0.cone, d0.p);
+    int defslots = user ? 0 : slots_of(cone, p);   // (a block from source has no entry in the padded pool: al_upload_typed's gp_base)
+    for (const AlDef& d0 : h->al_defs) if (!d0.user) defslots += slots_of(d0.cone, d0.p);
     if (defslots > AL_TILE_MAXSLOTDEF)
       return fail(ALTRO_HIP_ERR_UNSUPPORTED, "at most %d constraint slots (blocks, counted in units of %d rows) per handle on this plan: "
                                              "ALTRO_HIP_PLAN_GENERIC takes 64 blocks", AL_TILE_MAXSLOTDEF, AL_MAXP);
@@ -960,7 +980,7 @@ int altro_hip_add_linear_constraint(altro_hip_batch* h, int k_first, int k_last,
                                                 "(register it per range, like ALTROSolver::SetConstraint per index)", k_first, k);
     w = nk + mk;
   }
-  AlDef d{cone, p, g_per_problem ? 1 : 0, (int)h->al_G.size(), 0, 0, w};
+  AlDef d{cone, p, g_per_problem ? 1 : 0, (int)h->al_G.size(), 0, user, w};
   h->al_G.insert(h->al_G.end(), G, G + (size_t)p * w);
   h->al_g.emplace_back(g, g + (size_t)p * (g_per_problem ? h->batch : 1));
   const int id = (int)h->al_defs.size();
@@ -972,16 +992,36 @@ int altro_hip_add_linear_constraint(altro_hip_batch* h, int k_first, int k_last,
   h->al_dirty = true;
   return id;
 }
+int altro_hip_add_linear_constraint(altro_hip_batch* h, int k_first, int k_last, int cone, int p, const double* G,
+                                    const double* g, int g_per_problem) {
+  return add_block(h, k_first, k_last, cone, p, G, g, g_per_problem, 0);
+}
 int altro_hip_add_user_constraint(altro_hip_batch* h, int k_first, int k_last, int cone, int p, int id) {
   // ALTROSolver::SetConstraint with a general callback pair (altro_solver.cpp:192-223): value and Jacobian of block `id` come
   // from the source given to altro_hip_set_model_source (altro_user_constraint / altro_user_constraint_jacobian)
   int rc = loop_entry(h);
   if (rc) return rc;
   const bool gen = h->plan == ALTRO_HIP_PLAN_GENERIC;
-  if ((h->plan != ALTRO_HIP_PLAN_LANE && !gen) || h->model.kind != MODEL_USER || !h->rtc_has_constraints)
+  // (plan MFMA16: rtc_has_constraints is only ever set on a handle created with ALTRO_HIP_TILE_USER_BLOCKS, fp64 -- capi_rtc.hip)
+  const bool tile = h->plan == ALTRO_HIP_PLAN_MFMA16;
+  if ((h->plan != ALTRO_HIP_PLAN_LANE && !gen && !tile) || h->model.kind != MODEL_USER || !h->rtc_has_constraints)
     return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_set_model_source must come first, with a source that defines "
                                        "altro_user_constraint and altro_user_constraint_jacobian (plans LANE and GENERIC / MFMA32)");
   if (id < 0) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "constraint id %d", id);
+  if (tile) {   // one slot per block, AL_TILE_USER_MAXC such slots per knot point (kernels/al_types.h); the six slots in all: add_block
+    if (cone < CONE_EQUALITY || cone > CONE_SOC) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "unknown cone %d", cone);
+    const int pmax = cone == CONE_SOC ? AL_MAXSOC : AL_MAXP;
+    if (p < 1 || p > pmax)
+      return fail(ALTRO_HIP_ERR_UNSUPPORTED, "a constraint block from source has 1 .. %d rows on plan MFMA16 (%s: one slot; got %d): "
+                                             "ALTRO_HIP_PLAN_GENERIC takes 32", pmax, cone == CONE_SOC ? "AL_MAXSOC" : "AL_MAXP", p);
+    for (int k = std::max(k_first, 0); k <= std::min(k_last, h->N); ++k) {
+      int slots = 1;
+      for (int j = 0; j < h->al_knots[k].ncon; ++j) slots += h->al_defs[h->al_knots[k].def[j]].user ? 1 : 0;
+      if (slots > AL_TILE_USER_MAXC)
+        return fail(ALTRO_HIP_ERR_UNSUPPORTED, "at most %d constraint blocks from source per knot point on plan MFMA16 (AL_TILE_USER_MAXC; k = %d "
+                                               "would have %d): ALTRO_HIP_PLAN_GENERIC takes 32 rows of them", AL_TILE_USER_MAXC, k, slots);
+    }
+  }
   if (gen) {   // plan GENERIC stages the user blocks' values and Jacobians of a knot point in LDS (kernels/ilqr_generic.hip: GEN_USER_MAXROWS)
     if (p < 1 || p > GEN_USER_MAXROWS)
       return fail(ALTRO_HIP_ERR_UNSUPPORTED, "a constraint block from source has 1 .. %d rows on plan GENERIC (GEN_USER_MAXROWS; got %d)",
@@ -998,11 +1038,7 @@ int altro_hip_add_user_constraint(altro_hip_batch* h, int k_first, int k_last, i
     }
   }
   std::vector<double> G((size_t)std::max(p, 0) * (h->n + h->m), 0.0), g((size_t)std::max(p, 0), 0.0);   // placeholders: never read
-  rc = altro_hip_add_linear_constraint(h, k_first, k_last, cone, p, G.data(), g.data(), 0);
-  if (rc < 0) return rc;
-  h->al_defs[rc].user = id + 1;
-  h->al_dirty = true;
-  return rc;
+  return add_block(h, k_first, k_last, cone, p, G.data(), g.data(), 0, id + 1);
 }
 int altro_hip_clear_constraints(altro_hip_batch* h) {
   int rc = loop_entry(h, true);

@@ -101,7 +101,7 @@ struct altro_hip_batch {
   bool rtc_has_constraints = false;   // ... whose source also defines altro_user_constraint / _jacobian
   void* rtc = nullptr;            // run-time compiled model (capi_rtc.hip: RtcModule, shared through a per-process cache)
   std::string rtc_source;         // ... its source, and the cost kind (IlqrArgs::cost_kind) its cost-reading kernels were instantiated for
-  int rtc_ck = 0;                 // (plan MFMA16: constraint blocks | dense cost << 1 | more than AL_MAXC slots << 2, rtc_tile_launch)
+  int rtc_ck = 0;                 // (plan MFMA16: constraint blocks | dense cost << 1 | more than AL_MAXC slots << 2 | a slot from the source << 3, rtc_tile_launch)
   int x0_stride = 0;              // elements between two problems' x0 on the device (12 on plan MFMA16, else n)
   int spare_count = 0;            // spare candidate trajectories i_cand_spec holds (sized to the path in use, see spec_trials_cap)
   int spare_failed = 0;           // > 0: an allocation of this many spares failed on this handle (no retry at this size or above)
@@ -151,6 +151,7 @@ struct altro_hip_batch {
   int al_max_ncon = 0;                   // most blocks (plan MFMA16: slots, al_types.h) any knot point has
   int al_G_count = 0;                        // elements of the device G pool
   int al_has_soc = 0;                        // some block is a second-order cone
+  bool al_has_user = false;                  // some block comes from the caller's source (AlDef::user): plan MFMA16 then runs the run-time module's constraint kernels
   int al_all_sel = 0;                        // every block is bound-type (rows +-e_idx: AlKnot::sel)
   double expand_penalty_scaling = 10.0, expand_penalty_max = 1e8;   // what EXPAND_DUAL's look-ahead of PenaltyUpdate needs
   const int* bwd_active = nullptr;           // per-problem mask for the backward sweep inside ilqr_solve
@@ -565,6 +566,7 @@ constexpr int kStatsBlocks = 1024, kStatsStride = 16;   // capi_stats.hip: parti
 template <typename T>
 int rtc_launch(altro_hip_batch* h, int which, const IlqrArgs<T>& a);
 int rtc_tile_launch(altro_hip_batch* h, int which, const IlqrWaveArgs<double>& a);   // plan MFMA16: the model kernels of a caller's source
+int rtc_tile_al_launch(altro_hip_batch* h, int which, const IlqrWaveArgs<double>& a);   // ... and their constraint kernels (user slots)
 int rtc_gen_launch(altro_hip_batch* h, int which, const IlqrGenArgs<double>& a);     // plans GENERIC / MFMA32: likewise
 int rtc_gen_al_launch(altro_hip_batch* h, int which, const IlqrGenArgs<double>& a);  // ... and their constraint kernels (user blocks)
 

@@ -189,9 +189,10 @@ static int rtc_build(altro_hip_batch* h, const RtcUnit& unit, const std::string&
 static int rtc_lane_module(altro_hip_batch* h, const std::string& source, int ck, RtcModule** out) {
   return rtc_build(h, rtc_unit_lane(h->n, h->m, h->dtype == ALTRO_HIP_F64 ? "double" : "float", ck, source), source, out);
 }
-// (ck: constraint blocks | dense cost << 1 | more than AL_MAXC slots at some knot point << 2 -- altro_hip_batch::rtc_ck)
+// (ck: constraint blocks | dense cost << 1 | more than AL_MAXC slots at some knot point << 2 | a slot from the source << 3 --
+//  altro_hip_batch::rtc_ck)
 static int rtc_tile_module(altro_hip_batch* h, int ck, RtcModule** out) {
-  return rtc_build(h, rtc_unit_tile(h->n, h->m, ck & 1, (ck >> 1) & 1, h->rtc_source, (ck >> 2) & 1), h->rtc_source, out);
+  return rtc_build(h, rtc_unit_tile(h->n, h->m, ck & 1, (ck >> 1) & 1, h->rtc_source, (ck >> 2) & 1, (ck >> 3) & 1), h->rtc_source, out);
 }
 // One launch from a run-time module.  `a`: the kernel's one parameter (only read); fmt, p...: the message of a failed launch, the error's text last.
 template <typename A, typename... P>
@@ -243,16 +244,39 @@ int rtc_gen_al_launch(altro_hip_batch* h, int which, const IlqrGenArgs<double>& 
 }
 
 // A model kernel of plan MFMA16's loop from the handle's run-time module: the grids of ilqr_launch_mfma16_model.hip.
-int rtc_tile_launch(altro_hip_batch* h, int which, const IlqrWaveArgs<double>& a) {
+// the handle's tile module for the tables `a` carries: blocks, a dense cost, a third slot or a slot from the source came or went since
+// the module was built -- the instantiations for this combination (compiled once per key and process)
+static int rtc_tile_current(altro_hip_batch* h, const IlqrWaveArgs<double>& a, const RtcModule** out) {
   if (h->rtc_source.empty()) return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_set_model_source has not been called");
-  const int ck = (a.al.enabled ? 1 : 0) | (a.cost_dense ? 2 : 0) | ((a.al.enabled && a.al.max_ncon > AL_MAXC) ? 4 : 0);
-  if (!h->rtc || h->rtc_ck != ck) {   // blocks, a dense cost or a third slot came or went since the handle's module was built: the instantiations for this combination
+  const int ck = (a.al.enabled ? 1 : 0) | (a.cost_dense ? 2 : 0) | ((a.al.enabled && a.al.max_ncon > AL_MAXC) ? 4 : 0) |
+                 ((a.al.enabled && h->al_has_user) ? 8 : 0);
+  if (!h->rtc || h->rtc_ck != ck) {
     RtcModule* m2 = nullptr;
     if (const int rc = rtc_tile_module(h, ck, &m2)) return rc;
     h->rtc = m2; h->rtc_ck = ck;
   }
-  const RtcModule* mod = (const RtcModule*)h->rtc;
-  const unsigned gsh = a.al.enabled ? (unsigned)a.al.Gpad_count * 8u : 0u;   // the merit kernels' dynamic LDS (padded constraint Jacobians)
+  *out = (const RtcModule*)h->rtc;
+  return 0;
+}
+// The row-layout kernels that evaluate constraint rows outside the merit pass, from the handle's run-time module: a handle of plan
+// MFMA16 with a slot from the source (altro_hip_add_user_constraint).  IK_EXPAND is the whole AL expansion (the cost's terms included);
+// IK_STATIONARITY the feasibility walk alone (the caller has launched the library's residual kernel, which reads no constraint data).
+int rtc_tile_al_launch(altro_hip_batch* h, int which, const IlqrWaveArgs<double>& a) {
+  const RtcModule* mod = nullptr;
+  if (const int rc = rtc_tile_current(h, a, &mod)) return rc;
+  const int w = which == IK_EXPAND ? RTT_EXPAND_AL : which == IK_DUAL ? RTT_DUAL : which == IK_STATIONARITY ? RTT_FEAS : -1;
+  if (w < 0 || !mod->fn[w]) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "operation %d has no run-time compiled constraint kernel on plan MFMA16", which);
+  // four (problem, knot point) pairs per wave: the grids of ilqr_launch_mfma16.hip
+  return rtc_go(h, mod->fn[w], (unsigned)((int64_t)((a.batch + 3) / 4) * (a.N + 1)), 1, 64, 0, a,
+                "launch of the run-time compiled tile constraint kernel %d failed: %s", w);
+}
+
+int rtc_tile_launch(altro_hip_batch* h, int which, const IlqrWaveArgs<double>& a) {
+  const RtcModule* mod = nullptr;
+  if (const int rc = rtc_tile_current(h, a, &mod)) return rc;
+  // the merit kernels' dynamic LDS (padded constraint Jacobians; with a slot from the source at least one definition's worth: such a
+  // slot's unused row read lands there when the handle has no block given as data)
+  const unsigned gsh = a.al.enabled ? (unsigned)std::max(a.al.Gpad_count, h->al_has_user ? AL_GP_DEF : 0) * 8u : 0u;
   auto go = [&](int w, unsigned gx, unsigned gy) {
     return rtc_go(h, mod->fn[w], gx, gy, 64, (w == RTT_MERIT || w == RTT_MERIT2) ? gsh : 0u, a, "launch of the run-time compiled tile kernel %d failed: %s", w);
   };
@@ -327,7 +351,9 @@ int altro_hip_set_model_source(altro_hip_batch* h, const char* source, float tim
                 c_val ? "altro_user_constraint" : "altro_user_constraint_jacobian", c_val ? "altro_user_constraint_jacobian" : "altro_user_constraint");
   // nonlinear constraint blocks from source are plans LANE's and GENERIC's: an ALTRO_HIP_PLAN_AUTO handle that rides the padded tile only
   // because of its shape / batch size moves to one of them while it is still empty -- LANE for n <= 6, else GENERIC
-  if (h->plan == ALTRO_HIP_PLAN_MFMA16 && h->auto_plan && c_val &&
+  // (a handle created with ALTRO_HIP_TILE_USER_BLOCKS keeps them on the tile: fp64 records, kernels/ilqr_merit2_dpp.hip MD_USER_BLOCKS)
+  const bool tile_user = h->plan == ALTRO_HIP_PLAN_MFMA16 && (h->flags & ALTRO_HIP_TILE_USER_BLOCKS) != 0 && h->dtype == ALTRO_HIP_F64;
+  if (h->plan == ALTRO_HIP_PLAN_MFMA16 && h->auto_plan && c_val && !tile_user &&
       (rc = replan_empty_handle(h, lane_supported(h->n, h->m) ? ALTRO_HIP_PLAN_LANE : ALTRO_HIP_PLAN_GENERIC))) return rc;
   if (h->plan == ALTRO_HIP_PLAN_GENERIC) {   // plans GENERIC / MFMA32: the caller's model inside that plan's loop kernels (any n, m <= 32)
     if (h->ragged) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "device models need uniform dimensions");
@@ -347,16 +373,25 @@ int altro_hip_set_model_source(altro_hip_batch* h, const char* source, float tim
   if (h->plan == ALTRO_HIP_PLAN_MFMA16) {   // the tile plan's row-layout kernels around the caller's model (kernels/ilqr_tile_model.hip)
     if (h->dtype != ALTRO_HIP_F64)
       return fail(ALTRO_HIP_ERR_UNSUPPORTED, "device models on plan MFMA16 run on fp64 records (create the handle with ALTRO_HIP_F64)");
-    if (c_val || c_jac)
+    if ((c_val || c_jac) && !tile_user)
       return fail(ALTRO_HIP_ERR_UNSUPPORTED, "nonlinear constraint blocks from source run on plan GENERIC (ALTRO_HIP_PLAN_GENERIC, any n, m <= 32) "
                                              "and plan LANE; plan MFMA16 takes the model's two functions and linear blocks (altro_hip_add_linear_constraint)");
     h->rtc_source = src;
     h->model = ModelParams{MODEL_USER, timestep, 0, 2.7, 1.5};
     RtcModule* tm = nullptr;   // compile now: a source that does not build must fail HERE, with the compiler's log
     if (!h->al_defs.empty() && (rc = al_upload(h))) { h->rtc_source.clear(); h->model = ModelParams{MODEL_LINEAR, 0.0f, 0, 2.7, 1.5}; return rc; }   // (al_max_ncon: the slots of the blocks so far)
-    const int ck = (h->al_defs.empty() ? 0 : 1) | (h->cost_dense ? 2 : 0) | ((!h->al_defs.empty() && h->al_max_ncon > AL_MAXC) ? 4 : 0);
+    const bool user = !h->al_defs.empty() && h->al_has_user;   // (a source that replaces one whose blocks the handle still has)
+    if (user && !c_val) {
+      h->rtc_source.clear(); h->model = ModelParams{MODEL_LINEAR, 0.0f, 0, 2.7, 1.5};
+      return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "the handle has constraint blocks from source (altro_hip_add_user_constraint): the new source must define "
+                                              "altro_user_constraint and altro_user_constraint_jacobian, or altro_hip_clear_constraints must come first");
+    }
+    // (a flagged handle whose source defines the pair announces blocks from it: the unit compiled -- and checked -- here is the one a
+    //  handle with such a block launches, at the width of the blocks registered so far; rtc_tile_current builds another if it turns out otherwise)
+    const bool expect_user = user || (tile_user && c_val);
+    const int ck = ((h->al_defs.empty() && !expect_user) ? 0 : 1) | (h->cost_dense ? 2 : 0) | ((!h->al_defs.empty() && h->al_max_ncon > AL_MAXC) ? 4 : 0) | (expect_user ? 8 : 0);
     if ((rc = rtc_tile_module(h, ck, &tm))) { h->rtc_source.clear(); return rc; }
-    h->rtc = tm; h->rtc_ck = ck; h->model_set = true; h->rtc_has_constraints = false;
+    h->rtc = tm; h->rtc_ck = ck; h->model_set = true; h->rtc_has_constraints = tile_user && c_val && c_jac;
     return model_takes_dynamics(h);
   }
   RtcModule* m = nullptr;

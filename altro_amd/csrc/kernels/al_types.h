@@ -14,7 +14,12 @@ constexpr int AL_MAXP = 8;     // rows per zero / identity / orthant block (plan
 // slots to spare.  The row-layout kernels loop over the slots a knot point has; the merit kernel, which carries per-slot values in
 // registers across the ring of knot points, is instantiated for 2 and for AL_TILE_MAXC slots (AlTable::max_ncon picks).
 constexpr int AL_TILE_MAXC = 6;
-constexpr int AL_TILE_MAXSLOTDEF = 32;   // distinct slots per handle on plan MFMA16 (their padded Jacobians sit in the merit kernel's LDS: 32 x 1296 B)
+// Slots of a knot point whose rows and Jacobian come from the caller's source on plan MFMA16 (altro_hip_add_user_constraint on a handle
+// created with ALTRO_HIP_TILE_USER_BLOCKS; kernels/ilqr_merit2_dpp.hip, MD_USER_BLOCKS): each is one slot of at most AL_MAXP rows
+// (AL_MAXSOC in a second-order cone) among the knot point's AL_TILE_MAXC, and has no entry in AlTable::Gpad -- the row-layout kernels
+// keep a per-row LDS image of c and dc/d[x;u] for as many of them, which the two-slot merit kernel holds across a knot point's step
+constexpr int AL_TILE_USER_MAXC = 2;
+constexpr int AL_TILE_MAXSLOTDEF = 32;  // distinct slots per handle on plan MFMA16 (their padded Jacobians sit in the merit kernel's LDS: 32 x 1296 B)
 constexpr int AL_MAXSOC = 4;   // rows per second-order-cone block (plans LANE / MFMA16; plan GENERIC: up to GEN_MAXSOC)
 constexpr int AL_MAXDEF = 16;  // distinct blocks per handle
 // AlTable::Gpad: every block as 9 rows x 16 tile columns, rows padded to 18 (16-byte aligned, eight lanes reading one column hit

@@ -157,12 +157,76 @@ __device__ __forceinline__ void md_gather4(double v, double (&o)[4]) {
       : "=&v"(o[0]), "=&v"(o[1]), "=&v"(o[2]), "=&v"(o[3])
       : "v"(v));
 }
+// ---- slots whose rows come from the caller's source (AlKnot::user; altro_hip_add_user_constraint on plan MFMA16) -------------------
+// Only in the unit hiprtc compiles around a source that defines altro_user_constraint / _jacobian for a handle that has such a slot
+// (rtc_unit.h: rtc_unit_tile's `user`); the library's own instantiations do not contain a line of this.
+// A user slot differs from a linear one in two places: row i's value is c_i(x, u) itself instead of the chain G_i [x; u] - g_i, and
+// the column coefficients are column j of the caller's Jacobian at this point instead of AlTable::Gpad's.  Lane 0 of a row of 16
+// lanes gathers the row's [x; u] (16 DPP moves, every lane takes part), calls the caller's pair and leaves c (AL_MAXP) and
+// dc/d[x;u] (p x (n + m) column-major in the CALLER's column order, as written) in the row's LDS image; lane i then reads c_i and
+// lane j the p entries of its column (tile column j = caller's column j, or n + (j - 12) for the inputs).  The block's id and its row
+// count are run-time values of the table, so a Jacobian kept in registers would be indexed dynamically -- scratch memory; written
+// through the LDS pointer it is p (n + m) ds_writes by one lane and 1 + p ds_reads per lane.  Every block is one wave: the barriers
+// only order the image's writes and reads.
+#if defined(ALTRO_HIP_USER_MODEL) && defined(ALTRO_HIP_USER_CONSTRAINTS) && defined(ALTRO_HIP_TILE_N)
+#define MD_USER_BLOCKS 1
+constexpr int MD_UW = ALTRO_HIP_TILE_N + ALTRO_HIP_TILE_M;
+constexpr int MD_UIMG = AL_MAXP + AL_MAXP * MD_UW;          // c | J
+constexpr int MD_UIMG_ROW = AL_TILE_USER_MAXC * MD_UIMG;    // one row of 16 lanes' images
+__device__ __forceinline__ void md_gather16(double v, double (&o)[16]);   // (ilqr_tile_model.hip, below)
+// Every user slot of knot point `kn` into the row's images, in slot order (the u-th user slot: image u).  ONE copy of the caller's
+// pair per call site -- a loop over the table entry in constant memory, not unrolled: inlined per slot of the unrolled slot loops it
+// would be there NC times, and the merit kernel's knot-point loop would then no longer unroll (its record ring would go to scratch).
+// Must be called by every lane of the wave; w: the row's [x; u], zero in the input lanes at the terminal knot point.
+__device__ __forceinline__ void tile_user_eval_knot(const AlKnot ALTRO_CONST_AS& kn, double w, int j, double* uimg) {
+  double z[16];
+  md_gather16(w, z);
+  __syncthreads();                                  // the images' last readers are done
+  int nu = 0;
+#pragma unroll 1
+  for (int c = 0; c < kn.ncon; ++c) {
+    const int uid = kn.user[c];
+    if (uid == 0) continue;                         // (wave-uniform: the table is the handle's)
+    if (j == 0 && nu < AL_TILE_USER_MAXC) {
+      altro_user_constraint<double>(uid - 1, z, z + 12, uimg + nu * MD_UIMG);
+      altro_user_constraint_jacobian<double>(uid - 1, z, z + 12, uimg + nu * MD_UIMG + AL_MAXP);
+    }
+    ++nu;
+  }
+  __syncthreads();
+}
+__device__ __forceinline__ double tile_user_val(const double* img, int j, int p) {
+  const double v = img[j < p ? j : 0];
+  return j < p ? v : 0.0;
+}
+// column jcol (tile order) of the block's Jacobian; the input columns do not enter at the terminal knot point
+__device__ __forceinline__ void tile_user_col(const double* img, int jcol, int p, bool terminal, double (&cC)[8]) {
+  const int e = jcol < 12 ? jcol : ALTRO_HIP_TILE_N + (jcol - 12);
+  const bool ok = jcol < 12 ? jcol < ALTRO_HIP_TILE_N : (!terminal && jcol - 12 < ALTRO_HIP_TILE_M);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const bool in = ok && i < p;
+    const double v = img[AL_MAXP + (in ? i + e * p : 0)];
+    cC[i] = in ? v : 0.0;
+  }
+}
+#endif
+
 // (DU: DualUpdate, knotpoint_data.cpp:503-510 -- the projected dual becomes the dual; `store`: this row has a problem of its own)
+// (uimg: MD_USER_BLOCKS, this row's LDS image for the slots from the caller's source)
 template <typename S, bool DU = false, bool SOC = true>
 __device__ __forceinline__ void dpp_al_rows(const AlTable<S>& t, int k, int b, int64_t B, double w, bool terminal, double rho_est, int j,
-                                            double (&jvr)[AL_TILE_MAXC], double& cost, double& viol, bool store = false) {
+                                            double (&jvr)[AL_TILE_MAXC], double& cost, double& viol, bool store = false
+#ifdef MD_USER_BLOCKS
+                                            , double* uimg = nullptr
+#endif
+                                            ) {
   int zshift;
   const AlKnot ALTRO_CONST_AS& kn = al_knot<S>(t, k, zshift);
+#ifdef MD_USER_BLOCKS
+  tile_user_eval_knot(kn, w, j, uimg);
+  int nu = 0;                                       // user slots so far: the next one's image
+#endif
 #pragma unroll
   for (int c = 0; c < AL_TILE_MAXC; ++c) {
     jvr[c] = 0.0;
@@ -178,6 +242,12 @@ __device__ __forceinline__ void dpp_al_rows(const AlTable<S>& t, int k, int b, i
       cG[e] = (rl && !(terminal && e >= 12)) ? ge : 0.0;
     }
     double sacc = 0.0;
+#ifdef MD_USER_BLOCKS
+    if (kn.user[c]) {                               // c_i(x, u) from the caller's source (its g is zero) instead of the chain
+      sacc = tile_user_val(uimg + (nu < AL_TILE_USER_MAXC ? nu : 0) * MD_UIMG, j, p);
+      ++nu;
+    } else
+#endif
     md_chain16(sacc, w, cG);
     S* const zp_ = t.z + (int64_t)(kn.z_off[c] + zshift + jr) * B + b;
     const double gi = rl ? (kn.g_per_problem[c] ? (double)t.g[kn.g_off[c] + (int64_t)jr * B + b] : (double)t.g[kn.g_off[c] + jr]) : 0.0;
@@ -237,15 +307,25 @@ template <int NC>
 struct AlpKnot {
   int ncon, p[NC], cone[NC], gp_off[NC], z_off[NC], gpp[NC];
   int64_t g_off[NC];
+#ifdef MD_USER_BLOCKS
+  int user[NC];                                     // 0, or 1 + the slot's image (the u-th slot from the caller's source: image u)
+#endif
 };
 template <typename S, int NC>
 __device__ __forceinline__ void alp_knot(const AlTable<S>& t, int k, AlpKnot<NC>& s) {
   const AlKnot ALTRO_CONST_AS& kn = *(const AlKnot ALTRO_CONST_AS*)(t.knots + k);
   s.ncon = kn.ncon;
+#ifdef MD_USER_BLOCKS
+  int nu = 0;
+#endif
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     s.p[c] = kn.p[c]; s.cone[c] = kn.cone[c]; s.gp_off[c] = kn.Gp_off[c]; s.z_off[c] = kn.z_off[c]; s.gpp[c] = kn.g_per_problem[c];
     s.g_off[c] = kn.g_off[c];
+#ifdef MD_USER_BLOCKS
+    s.user[c] = 0;
+    if (c < kn.ncon && kn.user[c] != 0) { s.user[c] = 1 + (nu < AL_TILE_USER_MAXC ? nu : 0); ++nu; }
+#endif
   }
 }
 // (z_i, g_i) of the knot point whose entry is s (zshift: al_knot's, for uniform tables)
@@ -267,7 +347,11 @@ __device__ __forceinline__ void alp_fetch(const AlTable<S>& t, const AlpKnot<NC>
 // registers less, which is what lets the six-slot instantiation run two waves per SIMD.  jvr is then a single scratch value.
 template <bool SOC, int NC, bool FUSE = false>
 __device__ __forceinline__ void alp_rows(const AlpKnot<NC>& s, double w, double rho_est, int j, int rowb, double (&jvr)[FUSE ? 1 : NC], double& cost,
-                                         double& viol, const double* Gp, const double (&pre)[NC][2], int jcol = 0, double* colsum = nullptr) {
+                                         double& viol, const double* Gp, const double (&pre)[NC][2], int jcol = 0, double* colsum = nullptr
+#ifdef MD_USER_BLOCKS
+                                         , const double* uimg = nullptr, bool terminal = false
+#endif
+                                         ) {
   if constexpr (FUSE) *colsum = 0.0;
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
@@ -280,6 +364,12 @@ __device__ __forceinline__ void alp_rows(const AlpKnot<NC>& s, double w, double 
 #pragma unroll
     for (int e = 0; e < 8; ++e) { const md_d2 v = Gr[e]; cG[2 * e] = v[0]; cG[2 * e + 1] = v[1]; }
     double sacc = 0.0;
+#ifdef MD_USER_BLOCKS
+    // (a user slot's Gp_off is 0: the row read above stays inside the pool's image and is not used)
+    const double* const ui = uimg + (s.user[c] ? s.user[c] - 1 : 0) * MD_UIMG;   // (filled by tile_user_eval_knot before this call)
+    if (s.user[c]) sacc = tile_user_val(ui, j, p);  // c_i(x, u) from the caller's source (its g is zero) instead of the chain
+    else
+#endif
     md_chain16(sacc, w, cG);
     const bool rl = j < p;
     const double val = sacc - pre[c][1];
@@ -314,6 +404,10 @@ __device__ __forceinline__ void alp_rows(const AlpKnot<NC>& s, double w, double 
     if constexpr (FUSE) {                             // alp_col's chain for this slot
       const double* Gc = Gp + s.gp_off[c] + jcol;
       double cC[8];
+#ifdef MD_USER_BLOCKS
+      if (s.user[c]) tile_user_col(ui, jcol, p, terminal, cC);
+      else
+#endif
 #pragma unroll
       for (int i = 0; i < 8; ++i) cC[i] = Gc[i * AL_GP_LD];
       md_chain8(*colsum, jv, cC);
@@ -321,13 +415,21 @@ __device__ __forceinline__ void alp_rows(const AlpKnot<NC>& s, double w, double 
   }
 }
 template <int NC>
-__device__ __forceinline__ double alp_col(const AlpKnot<NC>& s, int j, const double (&jvr)[NC], const double* Gp) {
+__device__ __forceinline__ double alp_col(const AlpKnot<NC>& s, int j, const double (&jvr)[NC], const double* Gp
+#ifdef MD_USER_BLOCKS
+                                          , const double* uimg = nullptr, bool terminal = false
+#endif
+                                          ) {
   double sum = 0.0;
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
     if (c >= s.ncon) continue;
     const double* Gc = Gp + s.gp_off[c] + j;
     double cC[8];
+#ifdef MD_USER_BLOCKS
+    if (s.user[c]) tile_user_col(uimg + (s.user[c] - 1) * MD_UIMG, j, s.p[c], terminal, cC);
+    else
+#endif
 #pragma unroll
     for (int i = 0; i < 8; ++i) cC[i] = Gc[i * AL_GP_LD];
     md_chain8(sum, jvr[c], cC);
@@ -361,6 +463,14 @@ namespace altro_hip {
 // line-search round then costs a chunk's walk (16 knot points) instead of the horizon's (256 for C1: 0.36 ms however few problems
 // search).  The trial points equal the rollout's to rounding (1e-13), not bit for bit -- like everything on this plan.
 constexpr int MD_AFF_CHUNK = 16;                    // even (the image ping-pong is the parity of k)
+// (MD_USER_BLOCKS: the row's LDS image of the slots from the caller's source and `terminal`, to alp_rows / alp_col)
+#ifdef MD_USER_BLOCKS
+#define MD_UARGS(T_) , uimg_row, T_
+#define MD_UARGS0(T_) , 0, nullptr, uimg_row, T_
+#else
+#define MD_UARGS(T_)
+#define MD_UARGS0(T_)
+#endif
 template <typename S, bool AL, bool DUAL, bool DENSE = false, int MK = 0, bool SOC = true, bool AFF = false, int NC = AL_MAXC>
 __global__ __launch_bounds__(64, ((MK != 0 || (AL && DENSE && sizeof(S) == 8)) ? 1 : 2)) void wave_merit_dpp_kernel(IlqrWaveArgs<S> a) {
   static_assert(NC >= AL_MAXC && NC <= AL_TILE_MAXC, "two to AL_TILE_MAXC slots per knot point");
@@ -372,6 +482,10 @@ __global__ __launch_bounds__(64, ((MK != 0 || (AL && DENSE && sizeof(S) == 8)) ?
   constexpr int CPE = DENSE ? MF_COST : MF_COSTP;   // elements of a knot point's cost record
   __shared__ double img[2][2][IMG];                 // [parity][slot]; after the sweep: the final sums (red, below)
   extern __shared__ double Gdyn[];                  // AlTable::Gpad as doubles: the constraint Jacobians, read at every knot point (the launchers pass Gpad_count * 8 bytes)
+#ifdef MD_USER_BLOCKS
+  __shared__ double uimg[AL ? 4 : 1][MD_UIMG_ROW];  // [row of 16 lanes]: c and dc/d[x;u] of the slots from the caller's source
+  double* const uimg_row = uimg[AL ? (threadIdx.x >> 4) : 0];
+#endif
   const int lane = threadIdx.x;
   const int npairs = (a.batch + 1) >> 1;
   const int pr = mf_problem(blockIdx.x, npairs);
@@ -510,6 +624,9 @@ __global__ __launch_bounds__(64, ((MK != 0 || (AL && DENSE && sizeof(S) == 8)) ?
     const double w = isx ? x : uval, dw = isx ? dxda : duval;
     if (al) {   // both trials' constraint rows at the candidate point [x; u]; the feasibility that counts is trial 1's
       double Ja = 0.0, vv = 0.0;
+#ifdef MD_USER_BLOCKS
+      if (live) tile_user_eval_knot(*(const AlKnot ALTRO_CONST_AS*)(a.al.knots + (al_uni ? 0 : k)), w, j, uimg_row);   // (a padding step's rows are discarded)
+#endif
       if (live) {
         if (k + 1 >= N) alp_knot<S, NC>(a.al, N, kn_s);           // (k + 1 <= N: the terminal knot point's too)
         else if (!al_uni) alp_knot<S, NC>(a.al, k + 1, kn_s);
@@ -517,18 +634,18 @@ __global__ __launch_bounds__(64, ((MK != 0 || (AL && DENSE && sizeof(S) == 8)) ?
           // the wide table: the next knot point's (z_i, g_i) are asked for AFTER this one's have been used, into the same registers --
           // the loads then have the rest of this step and the head of the next to land in, and six slots cost 24 registers less
           // than with a second set (with alp_rows' FUSE: the six-slot instantiation at two waves per SIMD, no spills)
-          alp_rows<SOC, NC, FUSE>(kc_s, w, rho, j, rowb, jvr, Ja, vv, Gdyn, zg, j, &colsum);
+          alp_rows<SOC, NC, FUSE>(kc_s, w, rho, j, rowb, jvr, Ja, vv, Gdyn, zg, j, &colsum MD_UARGS(false));
           alp_fetch<S, NC>(a.al, kn_s, (al_uni && k + 1 < N) ? (k + 1) * a.al.rows_per_knot : 0, b, a.batch, j, zg);
         } else {
           double zgn[NC][2];
           alp_fetch<S, NC>(a.al, kn_s, (al_uni && k + 1 < N) ? (k + 1) * a.al.rows_per_knot : 0, b, a.batch, j, zgn);
-          alp_rows<SOC, NC>(kc_s, w, rho, j, rowb, jvr, Ja, vv, Gdyn, zg);
+          alp_rows<SOC, NC>(kc_s, w, rho, j, rowb, jvr, Ja, vv, Gdyn, zg MD_UARGS0(false));
 #pragma unroll
           for (int c = 0; c < NC; ++c) { zg[c][0] = zgn[c][0]; zg[c][1] = zgn[c][1]; }
         }
         Jal += Ja;
       } else {
-        alp_rows<SOC, NC, FUSE>(kc_s, w, rho, j, rowb, jvr, Ja, vv, Gdyn, zg, j, &colsum);   // a padding step: discarded
+        alp_rows<SOC, NC, FUSE>(kc_s, w, rho, j, rowb, jvr, Ja, vv, Gdyn, zg, j, &colsum MD_UARGS(false));   // a padding step: discarded
       }
       if (cand && live) viol = fmax(viol, vv);               // (live: a padding step's point is not on the trajectory)
     }
@@ -600,7 +717,7 @@ __global__ __launch_bounds__(64, ((MK != 0 || (AL && DENSE && sizeof(S) == 8)) ?
     }
     if (al) {
       if constexpr (FUSE) l -= colsum;
-      else l -= alp_col(kc_s, j, jvr, Gdyn);
+      else l -= alp_col(kc_s, j, jvr, Gdyn MD_UARGS(false));
       if (live) kc_s = kn_s;
     }
     if (live) dJ += l * dw;
@@ -648,11 +765,14 @@ __global__ __launch_bounds__(64, ((MK != 0 || (AL && DENSE && sizeof(S) == 8)) ?
     }
     if (al) {
       double Ja = 0.0, vv = 0.0;
+#ifdef MD_USER_BLOCKS
+      tile_user_eval_knot(*(const AlKnot ALTRO_CONST_AS*)(a.al.knots + N), isx ? x : 0.0, j, uimg_row);
+#endif
       if constexpr (DUAL) {
-        alp_rows<SOC, NC, FUSE>(kc_s, isx ? x : 0.0, rho, j, rowb, jvr, Ja, vv, Gdyn, zg, jr, &colsum);
+        alp_rows<SOC, NC, FUSE>(kc_s, isx ? x : 0.0, rho, j, rowb, jvr, Ja, vv, Gdyn, zg, jr, &colsum MD_UARGS(true));
         Jal += Ja;
       } else {   // (wave_merit_kernel adds the terminal blocks' shares to its running sum one by one)
-        alp_rows<SOC, NC, FUSE>(kc_s, isx ? x : 0.0, rho, j, rowb, jvr, Jal, vv, Gdyn, zg, jr, &colsum);
+        alp_rows<SOC, NC, FUSE>(kc_s, isx ? x : 0.0, rho, j, rowb, jvr, Jal, vv, Gdyn, zg, jr, &colsum MD_UARGS(true));
       }
       if (cand) viol = fmax(viol, vv);
     }
@@ -665,7 +785,7 @@ __global__ __launch_bounds__(64, ((MK != 0 || (AL && DENSE && sizeof(S) == 8)) ?
     double lx = DENSE ? gN + q : __builtin_fma(Qd, x, q);
     if (al) {
       if constexpr (FUSE) lx -= colsum;
-      else lx -= alp_col(kc_s, jr, jvr, Gdyn);
+      else lx -= alp_col(kc_s, jr, jvr, Gdyn MD_UARGS(true));
     }
     if (isx) dJ += lx * dxda;
     if (cand) {
@@ -821,6 +941,10 @@ template <typename S, bool DENSE = false, bool BOUNDS = false, int NC = AL_MAXC>
 __global__ __launch_bounds__(64) void wave_expand_dpp_kernel(IlqrWaveArgs<S> a) {
   static_assert(!(DENSE && BOUNDS), "the diagonal form is the diagonal cost's");
   const int lane = threadIdx.x, j = lane & 15;
+#ifdef MD_USER_BLOCKS
+  __shared__ double uimg[4][MD_UIMG_ROW];           // [row of 16 lanes]: c and dc/d[x;u] of the slots from the caller's source
+  double* const uimg_row = uimg[lane >> 4];
+#endif
   // four problems of ONE knot point per wave (the constraint table entry is the knot point's: wave-uniform control flow)
   const int wpk = (a.batch + 3) >> 2;
   const int k = (int)(blockIdx.x / wpk), b0 = (int)(blockIdx.x % wpk) * 4, b_own = b0 + (lane >> 4);
@@ -880,6 +1004,10 @@ __global__ __launch_bounds__(64) void wave_expand_dpp_kernel(IlqrWaveArgs<S> a) 
   double dacc = 0.0;                                // BOUNDS: this lane's diagonal entry of (J G)^T (J G), summed over the blocks
   double scol = 0.0;
   bool tile_counts = true;
+#ifdef MD_USER_BLOCKS
+  tile_user_eval_knot(kn, w, j, uimg_row);
+  int nu = 0;                                       // user slots so far: the next one's image
+#endif
 #pragma unroll
   for (int cidx = 0; cidx < NC; ++cidx) {
     if (cidx >= kn.ncon) continue;
@@ -891,6 +1019,14 @@ __global__ __launch_bounds__(64) void wave_expand_dpp_kernel(IlqrWaveArgs<S> a) 
     const int jr = rl ? j : 0;
     double cC[8];
     double sacc = 0.0;
+#ifdef MD_USER_BLOCKS
+    if (kn.user[cidx]) {                            // c_i(x, u) and column j of dc/d[x;u] from the caller's source (its g is zero)
+      const double* const ui = uimg_row + (nu < AL_TILE_USER_MAXC ? nu : 0) * MD_UIMG;
+      ++nu;
+      sacc = tile_user_val(ui, j, p);
+      tile_user_col(ui, j, p, terminal, cC);
+    } else
+#endif
     if constexpr (BOUNDS) {
       // every row of the slot is +-e_idx (AlKnot::sidx, scalar registers): nothing of G is loaded.  Row i's value is +-w_idx -- the
       // 16-term chain would add that one product to fifteen exact zeros -- fetched from lane idx of this lane's row of sixteen; column
@@ -1069,7 +1205,12 @@ __global__ __launch_bounds__(64) void wave_dual_update_dpp_kernel(IlqrWaveArgs<S
   const S* c = a.cand + (size_t)b * a.xuy_bs + (size_t)k * a.xuy_ks;
   const double w = j < 12 ? (double)c[j] : (terminal ? 0.0 : (double)c[12 + j]);
   double jvr[AL_TILE_MAXC], cost = 0.0, viol = 0.0;
+#ifdef MD_USER_BLOCKS
+  __shared__ double uimg[4][MD_UIMG_ROW];
+  dpp_al_rows<S, true>(a.al, k, b, a.batch, w, terminal, a.prob[b].rho_est, j, jvr, cost, viol, on, uimg[lane >> 4]);
+#else
   dpp_al_rows<S, true>(a.al, k, b, a.batch, w, terminal, a.prob[b].rho_est, j, jvr, cost, viol, on);
+#endif
 }
 // One wave per (four problems, knot point), like the dual update; the maximum over the knot points is an atomic maximum on the
 // bit pattern (violations are non-negative doubles, whose order is their bit patterns' order as unsigned integers) into the
@@ -1090,7 +1231,12 @@ __global__ __launch_bounds__(64) void wave_feasibility_dpp_kernel(IlqrWaveArgs<S
   const S* c = a.cand + (size_t)b * a.xuy_bs + (size_t)k * a.xuy_ks;
   const double w = j < 12 ? (double)c[j] : (terminal ? 0.0 : (double)c[12 + j]);
   double jvr[AL_TILE_MAXC], cost = 0.0, viol = 0.0;
+#ifdef MD_USER_BLOCKS
+  __shared__ double uimg[4][MD_UIMG_ROW];
+  dpp_al_rows<S>(a.al, k, b, a.batch, w, terminal, a.prob[b].rho, j, jvr, cost, viol, false, uimg[lane >> 4]);
+#else
   dpp_al_rows<S>(a.al, k, b, a.batch, w, terminal, a.prob[b].rho, j, jvr, cost, viol);
+#endif
 #pragma unroll
   for (int o = 8; o > 0; o >>= 1) viol = fmax(viol, __shfl_xor(viol, o, 64));
   if (j == 0 && on && viol > 0.0)

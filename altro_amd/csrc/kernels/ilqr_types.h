@@ -71,6 +71,8 @@ struct IlqrArgs {
   int cost_kind = 0;
 };
 constexpr int STAT_NO_FEAS = 32;   // IK_STATIONARITY / IK_DUAL on plan MFMA16: the constraint rows in the DPP form (ilqr_merit2_dpp.hip)
+constexpr int STAT_FEAS_USER = 1024; // IK_STATIONARITY with STAT_NO_FEAS: the launcher leaves out wave_feasibility_dpp_kernel -- a slot comes from the caller's
+                                     // source, and the caller launches the run-time compiled instantiation after it (capi_rtc.hip: rtc_tile_al_launch)
 enum { EXPAND_GRADIENT = 1, EXPAND_HESSIAN = 2, EXPAND_LDS = 16 /* plan MFMA16: wave_expand_kernel instead of the DPP form (A/B, tests) */,
        EXPAND_NEXT = 64 /* wave_expand_dpp_kernel at the end of a sweep: the gradient for the problems of the active mask (those whose
                            duals changed), the cost Hessians of the NEXT sweep for every problem still running (IlqrProb::running) */,

@@ -18,7 +18,9 @@ enum RtcKernel { RTC_ROLLOUT = 0, RTC_ACCEPT, RTC_EXPAND, RTC_MERIT, RTC_MERIT_R
                  RTC_ZERO_RESIDUALS, RTC_STATIONARITY, RTC_DUAL, RTC_SHIFT, RTC_NUM };
 // tile: the rollout, the dynamics expansion and the two merit kernels (line-search round / two-trial pass) of one (source, n, m,
 // constraint blocks?, dense cost?, more than AL_MAXC slots?) -- four kernels instead of ten, the merit kernels being the library's heaviest compiles
-enum RtcTileKernel { RTT_ROLLOUT = 0, RTT_EXPAND_DYN, RTT_MERIT, RTT_MERIT2, RTT_NUM };
+// A unit for a handle with a slot from the caller's source (rtc_unit_tile's `user`: ALTRO_HIP_USER_CONSTRAINTS, kernels/ilqr_merit2_dpp.hip
+// MD_USER_BLOCKS) has three more: the AL expansion (the cost's part included: it is one kernel), the dual update and the feasibility walk
+enum RtcTileKernel { RTT_ROLLOUT = 0, RTT_EXPAND_DYN, RTT_MERIT, RTT_MERIT2, RTT_NUM, RTT_EXPAND_AL = RTT_NUM, RTT_DUAL, RTT_FEAS, RTT_NUM_ALL };
 // generic: three kernels per (source, n, m): the open-loop rollout, the dynamics expansion and the merit evaluation.
 // On plan MFMA32's shapes three more: the merit kernel, its two-trial pass and the dynamics expansion in the row layout
 // (kernels/ilqr_row32.hip: every lane evaluates the caller's model; r32_model_step).  They are USED when they compiled without scratch
@@ -31,7 +33,7 @@ enum RtcTileKernel { RTT_ROLLOUT = 0, RTT_EXPAND_DYN, RTT_MERIT, RTT_MERIT2, RTT
 enum RtcGenKernel { RTG_ROLLOUT = 0, RTG_EXPAND_DYN, RTG_MERIT, RTG_NUM, RTG_ROW_MERIT = RTG_NUM, RTG_ROW_MERIT2, RTG_ROW_EXPAND_DYN, RTG_NUM_ROW,
                     RTG_STATIONARITY = RTG_NUM_ROW, RTG_EXPAND_AL, RTG_DUAL, RTG_NUM_ALL };
 constexpr int RTC_MAX_SLOTS = RTC_NUM;   // the largest kind's table
-static_assert(RTT_NUM <= RTC_MAX_SLOTS && RTG_NUM_ALL <= RTC_MAX_SLOTS, "RtcModule::fn holds every kind's kernels");
+static_assert(RTT_NUM_ALL <= RTC_MAX_SLOTS && RTG_NUM_ALL <= RTC_MAX_SLOTS, "RtcModule::fn holds every kind's kernels");
 
 enum class RtcKind : char { lane = 'l', tile = 't', generic = 'g' };
 struct RtcUnit {
@@ -111,12 +113,16 @@ inline RtcUnit rtc_unit_lane(int n, int m, const char* T, int ck, const std::str
 // wide: some knot point of the handle has more than AL_MAXC constraint slots -- the merit kernels are then the AL_TILE_MAXC-slot
 // instantiations (the ones ilqr_launch_mfma16_wide.hip holds for the compiled-in models); a two-slot kernel would skip the slots past
 // the second while the expansion, the dual update and the feasibility walk honour them.
-inline RtcUnit rtc_unit_tile(int n, int m, int al, int dense, const std::string& source, int wide = 0) {
+// user: some slot of the handle comes from the source's altro_user_constraint / _jacobian (al != 0, and the source defines the pair):
+// the unit is compiled with ALTRO_HIP_USER_CONSTRAINTS and also instantiates the three row-layout kernels that evaluate constraint
+// rows outside the merit pass -- the library's own instantiations of them know nothing of such a slot.
+inline RtcUnit rtc_unit_tile(int n, int m, int al, int dense, const std::string& source, int wide = 0, int user = 0) {
   RtcUnit u;
   u.kind = RtcKind::tile; u.program = "altro_user_tile_model.hip"; u.where = " for the tile plan"; u.noun = "tile model";
   u.key = std::string(1, (char)u.kind) + "|" + std::to_string(n) + "|" + std::to_string(m) + "|" + std::to_string(al) + "|" + std::to_string(dense) + "|" +
-          std::to_string(wide) + "|" + source;
+          std::to_string(wide) + (user ? "u" : "") + "|" + source;
   u.defines = "#define ALTRO_HIP_TILE_N " + std::to_string(n) + "\n#define ALTRO_HIP_TILE_M " + std::to_string(m) + "\n";
+  if (user) u.defines += "#define ALTRO_HIP_USER_CONSTRAINTS 1\n";
   u.includes = "#include \"kernels/ilqr_mfma16.hip\"\n#include \"kernels/ilqr_merit2_dpp.hip\"\n";
   const char* B_[2] = {"false", "true"};
   u.exprs.resize(RTT_NUM);
@@ -125,6 +131,12 @@ inline RtcUnit rtc_unit_tile(int n, int m, int al, int dense, const std::string&
   const char* tail = wide ? ", altro_hip::MODEL_USER, true, false, altro_hip::AL_TILE_MAXC>" : ", altro_hip::MODEL_USER>";
   u.exprs[RTT_MERIT] = std::string("altro_hip::wave_merit_dpp_kernel<double, ") + B_[al] + ", false, " + B_[dense] + tail;
   u.exprs[RTT_MERIT2] = std::string("altro_hip::wave_merit_dpp_kernel<double, ") + B_[al] + ", true, " + B_[dense] + tail;
+  if (user) {
+    u.exprs.resize(RTT_NUM_ALL);
+    u.exprs[RTT_EXPAND_AL] = std::string("altro_hip::wave_expand_dpp_kernel<double, ") + B_[dense] + ", false, altro_hip::" + (wide ? "AL_TILE_MAXC" : "AL_MAXC") + ">";
+    u.exprs[RTT_DUAL] = "altro_hip::wave_dual_update_dpp_kernel<double>";
+    u.exprs[RTT_FEAS] = "altro_hip::wave_feasibility_dpp_kernel<double>";
+  }
   u.args = "IlqrWaveArgs<double>"; u.options = kRtcRowOptions;
   return u;
 }

@@ -111,6 +111,13 @@ typedef enum altro_hip_plan {
                                         v_mfma_f32_16x16x4_f32 (cost-to-go carried in fp32: ~5e-4 relative).
                                         Default for F32 is fp32 storage with fp64 tile arithmetic (2e-5): on
                                         MI355X both are bound by the same fp32 record traffic */
+#define ALTRO_HIP_TILE_USER_BLOCKS 0x2u /* fp64 records on plan MFMA16: a source given to altro_hip_set_model_source that also defines the
+                                      * constraint pair of altro_hip_add_user_constraint is accepted and the handle STAYS on the tile (an
+                                      * ALTRO_HIP_PLAN_AUTO handle too, and the zero-padded shapes n <= 12, m <= 4); such blocks then take
+                                      * slots of the knot points' six next to the linear blocks.  Opt-in: without it such a source is
+                                      * refused on an explicit MFMA16 handle and moves an empty AUTO one to plan GENERIC / LANE.  The bit
+                                      * is ALTRO_HIP_F32_PURE's, which only fp32 handles read; this one only fp64 handles of plan MFMA16
+                                      * do, and it changes nothing but what they do with such a source.  DESIGN.md 4.29.               */
 #define ALTRO_HIP_GENERIC_MATRIX_CORES 0x8u /* plan GENERIC, fp64: the backward sweep's products as v_mfma_f64_16x16x4 tiles (any
                                       * n, m, per-knot-point dimensions included) instead of one multiply-add at a time in the CPU
                                       * path's order: 1.0-1.9 x faster from n = 14 up, results equal to rounding
@@ -247,7 +254,8 @@ int altro_hip_set_model(altro_hip_batch* h, int model, float timestep, int bicyc
  * launch-sequenced loop.  Plans GENERIC / MFMA32 (fp64, uniform n, m <= 32) and MFMA16 take the model the same way.  A source that
  * also defines the constraint pair of altro_hip_add_user_constraint is taken by plans LANE and GENERIC / MFMA32 (an empty
  * ALTRO_HIP_PLAN_AUTO handle of the tile moves to LANE for n <= 6, else to GENERIC); plan MFMA16 refuses it
- * (ALTRO_HIP_ERR_UNSUPPORTED), and a source that defines only one of the pair is ALTRO_HIP_ERR_BAD_ARGUMENT.               */
+ * (ALTRO_HIP_ERR_UNSUPPORTED) unless the handle was created with ALTRO_HIP_TILE_USER_BLOCKS (fp64 records): then it takes the
+ * source and an AUTO handle stays on the tile.  A source that defines only one of the pair is ALTRO_HIP_ERR_BAD_ARGUMENT.   */
 int altro_hip_set_model_source(altro_hip_batch* h, const char* source, float timestep);
 /* Plans GENERIC / MFMA32: 1 when the handle's device model (compiled in, or the caller's source) runs the loop's ROW-LAYOUT model kernels
  * (kernels/ilqr_row32.hip: two problems per wave, every lane evaluates the model -- plan MFMA32's shapes), 0 when it runs the
@@ -263,8 +271,12 @@ int altro_hip_model_row_layout(const altro_hip_batch* h);
  * points k_first..k_last -- next to the linear blocks; the AL terms treat it as the reference treats any constraint
  * (knotpoint_data.cpp:489-613: projected duals, Gauss-Newton in the Jacobian).  Plans LANE (p <= 8, SOC p <= 4, two blocks per
  * knot point) and GENERIC / MFMA32 (p <= 32 in any cone, 32 such rows per knot point; the handle then runs the wave-per-problem
- * loop kernels).  ALTRO_HIP_ERR_NOT_SET when the handle's model is not a source that defines the pair.  Returns the block id or a
- * negative error. */
+ * loop kernels).  Plan MFMA16 on a handle created with ALTRO_HIP_TILE_USER_BLOCKS (fp64): J in the caller's column order (n + m
+ * columns, whatever the padding), one slot per block -- p <= 8, SOC p <= 4 --, at most 2 such slots per knot point
+ * (AL_TILE_USER_MAXC) among its six; g = 0.  altro_hip_get_duals, _reset_duals, _clear_constraints and _feasibility treat it as any
+ * block.  The LDS comparison forms (ALTRO_HIP_FORM_MERIT_LDS, _ALROWS_LDS, _EXPAND_LDS) do not evaluate such slots: a handle that has
+ * one answers them with ALTRO_HIP_ERR_UNSUPPORTED.  ALTRO_HIP_ERR_NOT_SET when the handle's model is not a source that defines the
+ * pair.  Returns the block id or a negative error. */
 int altro_hip_add_user_constraint(altro_hip_batch* h, int k_first, int k_last, int cone, int p, int id);
 /* ALTROSolver::SetLQRCost (altro_solver.cpp:138-172): Qd, xref [batch][N+1][n]; Rd, uref [batch][N][m];
  * with k_stride_zero Qd/xref hold {running, terminal} and Rd/uref one knot point.                   */
@@ -319,7 +331,9 @@ int altro_hip_get_expansion(altro_hip_batch* h, double* A, double* B, double* lx
  *                      boxes solves in 1.27 x the time of the input box alone).  fp32 records: 2 slots.  The capacity
  *                      is the same for handles with a device model (altro_hip_set_model) and with a model from source
  *                      (altro_hip_set_model_source): the run-time compiled merit kernels are built for the table's width, and
- *                      built again when blocks added or cleared later move it across two slots;
+ *                      built again when blocks added or cleared later move it across two slots; blocks from source
+ *                      (altro_hip_add_user_constraint, handles created with ALTRO_HIP_TILE_USER_BLOCKS) take one slot each -- p <= 8,
+ *                      a second-order cone p <= 4 --, at most 2 of a knot point's 6 (AL_TILE_USER_MAXC), and none of the handle's 32;
  *   plan LANE          2 blocks per knot point, p <= 8 (SOC: p <= 4), 16 blocks per handle (the blocks ride registers of the
  *                      lane-per-problem kernels); rows of one cone can be stacked into one block.
  * Returns the block id (>= 0) or a negative error.  Duals and penalties live on the device per problem and,
