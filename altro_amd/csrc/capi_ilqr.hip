@@ -12,213 +12,65 @@ namespace altro_hip {
 namespace capi {   // (external linkage: capi_solve.hip drives these)
 
 // ---- iLQR loop (plan LANE) ---------------------------------------------------------------------------
-// Is row r of block d's G (as the caller gave it: p x w, column-major) +e_idx or -e_idx?  idx and sign are those of the row's only
-// nonzero, whatever its size (the tables record them for a multiple of e_idx too, which is no bound row); idx < 0: not exactly one.
-static bool al_bound_row(const altro_hip_batch* h, const AlDef& d, int r, int w, int& idx, int& sign) {
-  int nz = 0; bool unit = true;
-  for (int e = 0; e < w; ++e) {
-    const double v = h->al_G[(size_t)d.G_off + r + (size_t)e * d.p];
-    if (v != 0.0) { ++nz; idx = e; sign = v > 0 ? 1 : -1; unit = unit && (v == 1.0 || v == -1.0); }
-  }
-  if (nz != 1) idx = -1;
-  return unit && nz == 1;
+// the handle's blocks as al_tables.h takes them
+static AlInput al_input(const altro_hip_batch* h) {
+  return AlInput{h->plan, h->n, h->m, h->N, h->batch, h->dtype == ALTRO_HIP_F64 ? sizeof(double) : sizeof(float), h->ragged, h->nxv, h->nuv,
+                 h->al_defs, h->al_knots, h->al_G, h->al_g};
 }
-// (re)build the device tables of the constraint blocks; duals restart from zero when the structure changes
-template <typename T>
-int al_upload_typed(altro_hip_batch* h) {
-  const int64_t B = h->batch;
-  h->al_Gpad_count = 0;
+static int al_copy(altro_hip_batch* h, void** dst, const void* src, size_t bytes) {   // a host table's copy on the device
+  if (const int rc = dmalloc(h, dst, bytes)) return rc;
+  HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+  return 0;
+}
+static int al_copy_pool(altro_hip_batch* h, void** dst, const std::vector<double>& pool) {   // ... of a value pool, in the handle's element type
+  if (h->dtype == ALTRO_HIP_F64) return al_copy(h, dst, pool.data(), pool.size() * sizeof(double));
+  const std::vector<float> f = al_pool_as<float>(pool);
+  return al_copy(h, dst, f.data(), f.size() * sizeof(float));
+}
+// (re)build the device tables of the constraint blocks (al_tables.h decides what they contain); duals restart from zero when the
+// structure changes
+static int al_upload_tables(altro_hip_batch* h) {
   for (void** p : {(void**)&h->al_d_knots, (void**)&h->al_d_big, (void**)&h->al_d_gsel, (void**)&h->al_d_guser, &h->al_d_G, &h->al_d_Gpad, &h->al_d_g, &h->al_d_z})
     if (*p) { (void)hipFree(*p); *p = nullptr; }
-  h->al_has_user = false;
-  if (h->al_defs.empty()) { h->al_rows = 0; return 0; }
-  for (const AlDef& d : h->al_defs) if (d.user) h->al_has_user = true;
-  // G on the device: p x (n + m) column-major as given on plan LANE; on plan MFMA16 p x 16 in the tile's own column order
-  // (states in columns 0..11, inputs in 12..15), so that a padded shape's blocks address the padded [x; u] correctly
-  const bool tile = h->plan == ALTRO_HIP_PLAN_MFMA16;
-  const int w_log = h->n + h->m, w_dev = tile ? MF_N + MF_M : w_log;
-  auto dev_col = [&](int e) { return (tile && e >= h->n) ? MF_N + (e - h->n) : e; };
-  // Plan MFMA16 lays a block out over SLOTS of at most AL_MAXP rows (al_types.h: AL_TILE_MAXC): rows 8 s .. 8 s + 7 of a block in the
-  // zero / identity / orthant cones are a block of their own (those cones project row by row, cones.cpp:13-38) with the same duals
-  // in the same place; a second-order-cone block (p <= AL_MAXSOC) is one slot.  slot_base[i]: first slot definition of block i.
-  auto nslots = [&](const AlDef& d) { return (tile && d.cone != CONE_SOC) ? (d.p + AL_MAXP - 1) / AL_MAXP : 1; };
-  std::vector<int> slot_base(h->al_defs.size() + 1, 0);
-  for (size_t i = 0; i < h->al_defs.size(); ++i) slot_base[i + 1] = slot_base[i] + nslots(h->al_defs[i]);
-  // ... and gp_base[i] its first entry in the zero-padded pool Gpad (AL_TILE_MAXSLOTDEF of them): a block from the caller's source has
-  // none -- its Jacobian is evaluated at every point (kernels/ilqr_merit2_dpp.hip, MD_USER_BLOCKS)
-  std::vector<int> gp_base(h->al_defs.size() + 1, 0);
-  for (size_t i = 0; i < h->al_defs.size(); ++i) gp_base[i + 1] = gp_base[i] + (h->al_defs[i].user ? 0 : nslots(h->al_defs[i]));
-  std::vector<T> G;
-  std::vector<int> G_off_dev(tile ? (size_t)slot_base.back() : h->al_defs.size(), 0);   // plan MFMA16: per slot definition
-  for (size_t i = 0; i < h->al_defs.size(); ++i) {
-    const AlDef& d0 = h->al_defs[i];
-    if (tile) {   // every slot its own ps x 16 column-major matrix (the LDS-form kernels address a slot like a block)
-      for (int sl = 0; sl < nslots(d0); ++sl) {
-        const int r0 = sl * AL_MAXP, ps = std::min(d0.p - r0, AL_MAXP);
-        const size_t off = G.size();
-        G_off_dev[(size_t)slot_base[i] + sl] = (int)off;
-        G.resize(off + (size_t)ps * w_dev, (T)0);
-        for (int e = 0; e < w_log; ++e)
-          for (int r = 0; r < ps; ++r) G[off + r + (size_t)dev_col(e) * ps] = (T)h->al_G[(size_t)d0.G_off + (r0 + r) + (size_t)e * d0.p];
-      }
-      continue;
-    }
-    G_off_dev[i] = (int)G.size();
-    if (h->ragged) {   // per-knot-point dimensions (plan GENERIC): the block as given, p x (nx[k] + nu[k]) of its knot points
-      G.resize(G.size() + (size_t)d0.p * d0.w, (T)0);
-      for (size_t e = 0; e < (size_t)d0.p * d0.w; ++e) G[(size_t)G_off_dev[i] + e] = (T)h->al_G[(size_t)d0.G_off + e];
-      continue;
-    }
-    G.resize(G.size() + (size_t)d0.p * w_dev, (T)0);
-    for (int e = 0; e < w_log; ++e)
-      for (int r = 0; r < d0.p; ++r) G[(size_t)G_off_dev[i] + r + (size_t)dev_col(e) * d0.p] = (T)h->al_G[(size_t)d0.G_off + r + (size_t)e * d0.p];
-  }
-  std::vector<T> Gpad;   // the same slots zero-padded for the row-layout kernels (al_types.h: AL_GP_DEF)
-  if (tile) {
-    Gpad.assign((size_t)gp_base.back() * (size_t)AL_GP_DEF, (T)0);
-    for (size_t i = 0; i < h->al_defs.size(); ++i) {
-      const AlDef& d0 = h->al_defs[i];
-      if (d0.user) continue;
-      for (int e = 0; e < w_log; ++e)
-        for (int r = 0; r < d0.p; ++r)
-          Gpad[(size_t)(gp_base[i] + r / AL_MAXP) * AL_GP_DEF + (size_t)(r % AL_MAXP) * AL_GP_LD + dev_col(e)] =
-              (T)h->al_G[(size_t)d0.G_off + r + (size_t)e * d0.p];
-    }
-  }
-  std::vector<T> g;
-  std::vector<AlDef> defs = h->al_defs;
-  for (size_t i = 0; i < defs.size(); ++i) {
-    defs[i].g_off = (int64_t)g.size();
-    const std::vector<double>& src = h->al_g[i];
-    const int p = defs[i].p;
-    if (defs[i].g_per_problem) {
-      const size_t base = g.size();
-      g.resize(base + (size_t)p * B);
-      for (int64_t b = 0; b < B; ++b)
-        for (int r = 0; r < p; ++r) g[base + (size_t)r * B + b] = (T)src[(size_t)b * p + r];
-    } else {
-      for (int r = 0; r < p; ++r) g.push_back((T)src[r]);
-    }
-  }
-  int rows = 0;
-  const bool gen = h->plan == ALTRO_HIP_PLAN_GENERIC;
-  std::vector<AlKnotBig> big = h->al_knots;
-  std::vector<AlKnot> knots(gen ? 0 : big.size(), AlKnot{});
-  int max_ncon = 0;
-  for (size_t k = 0; k < big.size(); ++k) {
-    AlKnotBig& bk = big[k];
-    int ns = 0;   // slots of knot point k so far (plans LANE: one per block)
-    for (int j = 0; j < bk.ncon; ++j) {
-      const AlDef& d = defs[bk.def[j]];
-      bk.z_off[j] = rows; rows += d.p;
-      bk.cone[j] = d.cone; bk.p[j] = d.p; bk.g_per_problem[j] = d.g_per_problem; bk.G_off[j] = tile ? G_off_dev[slot_base[bk.def[j]]] : G_off_dev[bk.def[j]];
-      bk.g_off[j] = d.g_off;
-      if (gen) continue;
-      AlKnot& kn = knots[k];
-      for (int sl = 0; sl < nslots(d); ++sl, ++ns) {
-        if (ns >= (tile ? AL_TILE_MAXC : AL_MAXC))   // (altro_hip_add_linear_constraint counted the slots: not reached)
-          return fail(ALTRO_HIP_ERR_UNSUPPORTED, "knot point %d: more constraint rows than the plan's table holds", (int)k);
-        const int r0 = sl * AL_MAXP, ps = tile ? std::min(d.p - r0, d.cone == CONE_SOC ? d.p : AL_MAXP) : d.p;
-        kn.def[ns] = bk.def[j];
-        kn.z_off[ns] = bk.z_off[j] + r0;
-        kn.cone[ns] = d.cone; kn.p[ns] = ps; kn.g_per_problem[ns] = d.g_per_problem;
-        kn.G_off[ns] = tile ? G_off_dev[(size_t)slot_base[bk.def[j]] + sl] : G_off_dev[bk.def[j]];
-        kn.g_off[ns] = d.g_off + (d.g_per_problem ? (int64_t)r0 * B : (int64_t)r0);   // g is [p] or [p][batch]: row r0 on
-        kn.user[ns] = d.user;
-        kn.Gp_off[ns] = (tile && !d.user) ? (gp_base[bk.def[j]] + sl) * AL_GP_DEF : 0;
-        // bound-type slot: every row of G is +-e_idx
-        bool sel = d.cone != CONE_SOC;
-        for (int r = 0, at, sg; r < ps && sel; ++r) {
-          sel = al_bound_row(h, d, r0 + r, w_log, at, sg);
-          if (at >= 0) kn.sidx[ns][r] = sg * (dev_col(at) + 1);
-        }
-        kn.sel[ns] = sel ? 1 : 0;
-      }
-      kn.ncon = ns;
-    }
-    max_ncon = std::max(max_ncon, gen ? bk.ncon : ns);
-  }
-  h->al_max_ncon = max_ncon;
-  auto upload = [&](void** dst, const void* src, size_t bytes) -> int {   // a host table's copy on the device
-    if (const int rcu = dmalloc(h, dst, bytes)) return rcu;
-    HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    return 0;
-  };
+  h->al_sum = AlSummary{}; h->al_rows = 0;   // (nothing on the device: what a handle without blocks has)
+  const AlTables t = al_build(al_input(h));
+  if (t.error == AL_BUILD_SLOTS)
+    return fail(ALTRO_HIP_ERR_UNSUPPORTED, "knot point %d: more constraint rows than the plan's table holds", t.err_k);
+  if (t.error == AL_BUILD_WINDOW)
+    return fail(ALTRO_HIP_ERR_UNSUPPORTED, "plan LANE: %d dual rows x batch %d exceed the 2 GiB buffer window; split the batch", t.rows, h->batch);
+  if (h->al_defs.empty()) return 0;
   int rc = 0;
-  h->al_all_gsel = gen && !h->ragged && !defs.empty();
-  if (gen && !h->ragged) {   // plan GENERIC: which blocks are bound-type (AlTable::gsel; the expansion's Gauss-Newton term is then diagonal)
-    std::vector<int> gsel(defs.size() * (size_t)(1 + GEN_MAXP), 0);
-    for (size_t i = 0; i < defs.size(); ++i) {
-      const AlDef& d = defs[i];
-      bool sel = d.cone != CONE_SOC && !d.user && d.p <= GEN_MAXP;
-      for (int r = 0, at, sg; r < d.p && sel; ++r) {
-        sel = al_bound_row(h, d, r, w_log, at, sg);
-        if (at >= 0) gsel[i * (size_t)(1 + GEN_MAXP) + 1 + r] = sg * (at + 1);
-      }
-      gsel[i * (size_t)(1 + GEN_MAXP)] = sel ? 1 : 0;
-      if (!sel) h->al_all_gsel = false;
-    }
-    if (!gsel.empty() && (rc = upload((void**)&h->al_d_gsel, gsel.data(), gsel.size() * sizeof(int)))) return rc;
-    // blocks from the caller's source (AlTable::guser): only the run-time compiled kernels read the table, and only a handle with
-    // such a block has one
-    std::vector<int> guser(defs.size(), 0);
-    bool any_user = false;
-    for (size_t i = 0; i < defs.size(); ++i) { guser[i] = defs[i].user; any_user = any_user || defs[i].user != 0; }
-    if (any_user && (rc = upload((void**)&h->al_d_guser, guser.data(), guser.size() * sizeof(int)))) return rc;
-  }
-  h->al_row32_ok = true;   // (kernels/ilqr_row32.hip: a lane position per row, the row-wise cones)
-  for (const AlDef& d : defs) if (d.cone == CONE_SOC || d.p > 32 || d.user) h->al_row32_ok = false;
-  h->al_rows = rows;
-  if (h->plan == ALTRO_HIP_PLAN_LANE && (uint64_t)rows * (uint64_t)B * sizeof(T) >= (1ull << 31))
-    return fail(ALTRO_HIP_ERR_UNSUPPORTED, "plan LANE: %d dual rows x batch %d exceed the 2 GiB buffer window; split the batch", rows, h->batch);
-  {   // uniform running knot points?  (then the dual rows of knot point k start k * rows_per_knot after those of 0)
-    const AlKnotBig& k0 = big[0];
-    int r0 = 0;
-    for (int j = 0; j < k0.ncon; ++j) r0 += defs[k0.def[j]].p;
-    bool uni = h->N >= 1 && k0.ncon > 0;
-    for (int k = 1; k < h->N && uni; ++k) {
-      uni = big[k].ncon == k0.ncon;
-      for (int j = 0; j < k0.ncon && uni; ++j) uni = big[k].def[j] == k0.def[j] && big[k].z_off[j] == k0.z_off[j] + k * r0;
-    }
-    h->al_uniform = uni ? 1 : 0;
-    h->al_rows_per_knot = r0;
-  }
-  if (gen && (rc = upload((void**)&h->al_d_big, big.data(), big.size() * sizeof(AlKnotBig)))) return rc;
-  if ((rc = dmalloc(h, (void**)&h->al_d_knots, std::max<size_t>(knots.size(), 1) * sizeof(AlKnot)))) return rc;   // (plan GENERIC: no entries)
-  if (!knots.empty()) HIP_TRY(hipMemcpy(h->al_d_knots, knots.data(), knots.size() * sizeof(AlKnot), hipMemcpyHostToDevice));
-  if ((rc = upload(&h->al_d_G, G.data(), G.size() * sizeof(T)))) return rc;
-  if ((rc = upload(&h->al_d_g, g.data(), g.size() * sizeof(T)))) return rc;
-  if (!Gpad.empty()) {
-    if ((rc = upload(&h->al_d_Gpad, Gpad.data(), Gpad.size() * sizeof(T)))) return rc;
-    h->al_Gpad_count = (int)Gpad.size();
-  }
-  if ((rc = dmalloc(h, &h->al_d_z, (size_t)rows * B * sizeof(T)))) return rc;
+  if (!t.gsel.empty() && (rc = al_copy(h, (void**)&h->al_d_gsel, t.gsel.data(), t.gsel.size() * sizeof(int)))) return rc;
+  if (!t.guser.empty() && (rc = al_copy(h, (void**)&h->al_d_guser, t.guser.data(), t.guser.size() * sizeof(int)))) return rc;
+  if (h->plan == ALTRO_HIP_PLAN_GENERIC && (rc = al_copy(h, (void**)&h->al_d_big, t.big.data(), t.big.size() * sizeof(AlKnotBig)))) return rc;
+  if ((rc = dmalloc(h, (void**)&h->al_d_knots, std::max<size_t>(t.knots.size(), 1) * sizeof(AlKnot)))) return rc;   // (plan GENERIC: no entries)
+  if (!t.knots.empty()) HIP_TRY(hipMemcpy(h->al_d_knots, t.knots.data(), t.knots.size() * sizeof(AlKnot), hipMemcpyHostToDevice));
+  if ((rc = al_copy_pool(h, &h->al_d_G, t.G))) return rc;
+  if ((rc = al_copy_pool(h, &h->al_d_g, t.g))) return rc;
+  if (!t.Gpad.empty() && (rc = al_copy_pool(h, &h->al_d_Gpad, t.Gpad))) return rc;
+  const size_t zbytes = (size_t)t.rows * h->batch * (h->dtype == ALTRO_HIP_F64 ? sizeof(double) : sizeof(float));
+  if ((rc = dmalloc(h, &h->al_d_z, zbytes))) return rc;
   // (memsets go on the handle's own stream: it is non-blocking, so a null-stream memset would race the kernels)
-  HIP_TRY(hipMemsetAsync(h->al_d_z, 0, (size_t)rows * B * sizeof(T), h->stream));
-  h->al_knots = big;
-  h->al_G_count = (int)G.size();
-  h->al_has_soc = 0;
-  for (const AlDef& d : defs) if (d.cone == CONE_SOC) h->al_has_soc = 1;
-  h->al_all_sel = gen ? 0 : 1;
-  for (const AlKnot& kn : knots)
-    for (int j = 0; j < kn.ncon; ++j) if (!kn.sel[j]) h->al_all_sel = 0;
+  HIP_TRY(hipMemsetAsync(h->al_d_z, 0, zbytes, h->stream));
+  h->al_knots = t.big;
+  h->al_sum = t.sum; h->al_rows = t.rows;
   return 0;
 }
 int al_upload(altro_hip_batch* h) {
   if (!h->al_dirty) return 0;
-  int rc = h->dtype == ALTRO_HIP_F64 ? al_upload_typed<double>(h) : al_upload_typed<float>(h);
+  const int rc = al_upload_tables(h);
   if (!rc) h->al_dirty = false;
   return rc;
 }
 
-// The kernels' view of the handle's constraint tables, on every plan: what a plan does not have is null / zero on the handle (al_upload_typed:
+// The kernels' view of the handle's constraint tables, on every plan: what a plan does not have is null / zero on the handle (al_upload_tables:
 // Gpad is plan MFMA16's; big, gsel and guser are plan GENERIC's), and max_ncon is read by plan MFMA16's launcher alone.
 template <typename T>
 AlTable<T> al_table(const altro_hip_batch* h) {
   AlTable<T> t;
   t.knots = h->al_d_knots; t.big = h->al_d_big; t.G = (const T*)h->al_d_G; t.g = (const T*)h->al_d_g; t.z = (T*)h->al_d_z; t.enabled = h->al_defs.empty() ? 0 : 1;
-  t.uniform = h->al_uniform; t.rows_per_knot = h->al_rows_per_knot; t.N = h->N; t.G_count = h->al_G_count; t.Gpad = (const T*)h->al_d_Gpad; t.Gpad_count = h->al_Gpad_count;
-  t.all_sel = h->al_all_sel; t.has_soc = h->al_has_soc; t.gsel = h->al_d_gsel; t.max_ncon = h->al_max_ncon; t.guser = h->al_d_guser;
+  t.uniform = h->al_sum.uniform; t.rows_per_knot = h->al_sum.rows_per_knot; t.N = h->N; t.G_count = h->al_sum.G_count; t.Gpad = (const T*)h->al_d_Gpad; t.Gpad_count = h->al_sum.Gpad_count;
+  t.all_sel = h->al_sum.all_sel; t.has_soc = h->al_sum.has_soc; t.gsel = h->al_d_gsel; t.max_ncon = h->al_sum.max_ncon; t.guser = h->al_d_guser;
   return t;
 }
 
@@ -294,7 +146,7 @@ int wave_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int
   a.al = al_table<S>(h);
   a.mode = mode;
   // a slot from the caller's source (altro_hip_add_user_constraint): evaluated by the row-layout kernels of the run-time module only
-  const bool user_al = a.al.enabled && h->al_has_user;
+  const bool user_al = a.al.enabled && h->al_sum.has_user;
   if (user_al && (h->forms & (ALTRO_HIP_FORM_MERIT_LDS | ALTRO_HIP_FORM_ALROWS_LDS | ALTRO_HIP_FORM_EXPAND_LDS)))
     return fail(ALTRO_HIP_ERR_UNSUPPORTED, "constraint blocks from source on plan MFMA16 run in the row-layout kernels only: the LDS comparison forms "
                                            "(ALTRO_HIP_FORM_MERIT_LDS, _ALROWS_LDS, _EXPAND_LDS) do not evaluate them");
@@ -370,14 +222,14 @@ GenSizes gen_sizes(const altro_hip_batch* h) {
 // uniform dimensions, dynamics as data, every constraint block in a row-wise cone with at most 32 rows
 bool row32_eligible(const altro_hip_batch* h) {
   return h->plan == ALTRO_HIP_PLAN_GENERIC && h->dtype == ALTRO_HIP_F64 && !h->ragged && !h->model_set && tile32_supported(h->n, h->m) &&
-         !form(h, ALTRO_HIP_FORM_GENERIC_MERIT_LDS) && (h->al_defs.empty() || h->al_row32_ok);
+         !form(h, ALTRO_HIP_FORM_GENERIC_MERIT_LDS) && (h->al_defs.empty() || h->al_sum.row32_ok);
 }
 // the same with a compiled-in device model (row32_model.hip has the kernels: ilqr_generic_model_supported's models)
 bool row32_model_eligible(const altro_hip_batch* h) {
   return h->plan == ALTRO_HIP_PLAN_GENERIC && h->dtype == ALTRO_HIP_F64 && !h->ragged && h->model_set && tile32_supported(h->n, h->m) &&
          (ilqr_generic_model_supported(h->model.kind, h->n, h->m) || (h->model.kind == MODEL_USER && h->rtc_row32_ok)) &&
          !form(h, ALTRO_HIP_FORM_GENERIC_MERIT_LDS) &&
-         (h->al_defs.empty() || h->al_row32_ok);
+         (h->al_defs.empty() || h->al_sum.row32_ok);
 }
 // plan GENERIC: any (n_k, m_k) up to 64, dynamics as data, quadratic cost, linear constraint blocks (kernels/ilqr_generic.hip)
 template <typename T>
@@ -553,7 +405,7 @@ int ilqr_check(altro_hip_batch* h, bool need_guess) {
 }
 
 // A device model on plan GENERIC or MFMA16: A_k, B_k (plan MFMA16: the DYN records, Z = [A B]) are the EXPANSION's from now on, written
-// by the expansion / merit kernels, and f = 0.  (memsets on the handle's own stream: see al_upload_typed)
+// by the expansion / merit kernels, and f = 0.  (memsets on the handle's own stream: see al_upload_tables)
 int model_takes_dynamics(altro_hip_batch* h) {
   if (h->plan == ALTRO_HIP_PLAN_GENERIC) for (int a : {G_f, G_A, G_B}) HIP_TRY(hipMemsetAsync(h->g_arr[a], 0, (size_t)h->batch * h->g_bstride[a] * h->esz, h->stream));
   if (h->plan == ALTRO_HIP_PLAN_MFMA16) HIP_TRY(hipMemsetAsync(h->m_in, 0, (size_t)h->batch * h->N * MF_DYN * h->esz, h->stream));
@@ -936,50 +788,34 @@ static int add_block(altro_hip_batch* h, int k_first, int k_last, int cone, int 
   if (rc) return rc;
   h->expansion_current = false;
   if (!G || !g) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "G and g are required");
-  if (cone < CONE_EQUALITY || cone > CONE_SOC) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "unknown cone %d", cone);
-  // capacities (stated in altro_hip.h): plan GENERIC loops over the blocks with one lane per row, plan LANE unrolls two blocks, plan
-  // MFMA16 lays the rows out over slots of eight (kernels/al_types.h: AL_TILE_MAXC)
-  const bool gen = h->plan == ALTRO_HIP_PLAN_GENERIC, tile = h->plan == ALTRO_HIP_PLAN_MFMA16;
-  const int tile_slots = h->dtype == ALTRO_HIP_F64 ? AL_TILE_MAXC : AL_MAXC;   // (fp32 records: the two-slot kernels only)
-  const int pmax = cone == CONE_SOC ? (gen ? GEN_MAXSOC : AL_MAXSOC) : (gen ? GEN_MAXP : tile ? tile_slots * AL_MAXP : AL_MAXP);
-  const int cmax = gen ? GEN_MAXC : AL_MAXC, dmax = gen ? GEN_MAXDEF : tile ? AL_TILE_MAXSLOTDEF : AL_MAXDEF;
-  if (p < 1 || p > pmax)
-    return fail(ALTRO_HIP_ERR_UNSUPPORTED, "constraint dimension %d outside [1, %d]%s", p, pmax,
-                gen ? "" : cone == CONE_SOC ? " on this plan (ALTRO_HIP_PLAN_GENERIC takes second-order cones of up to 32 rows)"
-                                            : " on this plan (ALTRO_HIP_PLAN_GENERIC takes up to 64 rows per block and 8 blocks per knot point)");
-  if (k_first < 0 || k_last > h->N || k_first > k_last)
-    return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "knot point range [%d, %d] outside [0, %d] (ErrorCodes::BadIndex)", k_first, k_last, h->N);
-  auto slots_of = [&](int cn, int rows) { return cn == CONE_SOC ? 1 : (rows + AL_MAXP - 1) / AL_MAXP; };
-  if (tile) {   // slots: per knot point and per handle
-    int defslots = user ? 0 : slots_of(cone, p);   // (a block from source has no entry in the padded pool: al_upload_typed's gp_base)
-    for (const AlDef& d0 : h->al_defs) if (!d0.user) defslots += slots_of(d0.cone, d0.p);
-    if (defslots > AL_TILE_MAXSLOTDEF)
+  // capacities (stated in altro_hip.h; al_tables.h: al_admit)
+  const bool gen = h->plan == ALTRO_HIP_PLAN_GENERIC;
+  const AlAdmit ad = al_admit(al_input(h), k_first, k_last, cone, p, user);
+  switch (ad.limit) {
+    case AL_LIMIT_CONE: return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "unknown cone %d", cone);
+    case AL_LIMIT_ROWS:
+      return fail(ALTRO_HIP_ERR_UNSUPPORTED, "constraint dimension %d outside [1, %d]%s", p, ad.pmax,
+                  gen ? "" : cone == CONE_SOC ? " on this plan (ALTRO_HIP_PLAN_GENERIC takes second-order cones of up to 32 rows)"
+                                              : " on this plan (ALTRO_HIP_PLAN_GENERIC takes up to 64 rows per block and 8 blocks per knot point)");
+    case AL_LIMIT_RANGE:
+      return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "knot point range [%d, %d] outside [0, %d] (ErrorCodes::BadIndex)", k_first, k_last, h->N);
+    case AL_LIMIT_DEFS:
+      if (h->plan != ALTRO_HIP_PLAN_MFMA16) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "at most %d constraint blocks", ad.dmax);
       return fail(ALTRO_HIP_ERR_UNSUPPORTED, "at most %d constraint slots (blocks, counted in units of %d rows) per handle on this plan: "
-                                             "ALTRO_HIP_PLAN_GENERIC takes 64 blocks", AL_TILE_MAXSLOTDEF, AL_MAXP);
-    for (int k = k_first; k <= k_last; ++k) {
-      int used = slots_of(cone, p);
-      for (int j = 0; j < h->al_knots[k].ncon; ++j) { const AlDef& d0 = h->al_defs[h->al_knots[k].def[j]]; used += slots_of(d0.cone, d0.p); }
-      if (used > tile_slots)
-        return fail(ALTRO_HIP_ERR_UNSUPPORTED, "at most %d constraint slots of %d rows per knot point on this plan (k = %d would need %d; a block "
-                                               "takes ceil(p / %d) of them, a second-order cone one): ALTRO_HIP_PLAN_GENERIC takes 8 blocks of 64 rows",
-                    tile_slots, AL_MAXP, k, used, AL_MAXP);
-    }
-  } else {
-    if ((int)h->al_defs.size() >= dmax) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "at most %d constraint blocks", dmax);
-    for (int k = k_first; k <= k_last; ++k)
-      if (h->al_knots[k].ncon >= cmax)
-        return fail(ALTRO_HIP_ERR_UNSUPPORTED, "at most %d constraint blocks per knot point on this plan (k = %d)%s", cmax, k,
+                                             "ALTRO_HIP_PLAN_GENERIC takes 64 blocks", ad.dmax, AL_MAXP);
+    case AL_LIMIT_KNOT:
+      if (h->plan != ALTRO_HIP_PLAN_MFMA16)
+        return fail(ALTRO_HIP_ERR_UNSUPPORTED, "at most %d constraint blocks per knot point on this plan (k = %d)%s", ad.cmax, ad.k,
                     gen ? "" : ": ALTRO_HIP_PLAN_GENERIC takes 8");
+      return fail(ALTRO_HIP_ERR_UNSUPPORTED, "at most %d constraint slots of %d rows per knot point on this plan (k = %d would need %d; a block "
+                                             "takes ceil(p / %d) of them, a second-order cone one): ALTRO_HIP_PLAN_GENERIC takes 8 blocks of 64 rows",
+                  ad.cmax, AL_MAXP, ad.k, ad.count, AL_MAXP);
+    case AL_LIMIT_RAGGED:
+      return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "knot points %d and %d differ in dimension: one constraint block takes one [x; u] size "
+                                              "(register it per range, like ALTROSolver::SetConstraint per index)", k_first, ad.k);
+    default: break;   // (the limits of a block from source: altro_hip_add_user_constraint has answered them)
   }
-  int w = h->n + h->m;
-  if (h->ragged) {   // G is p x (nx[k] + nu[k]): every knot point of the range must have the dimensions of the first (the terminal one: its nx)
-    const int nk = h->nxv[k_first], mk = k_first < h->N ? h->nuv[k_first] : 0;   // (a block of the terminal knot point alone: p x nx[N])
-    for (int k = k_first; k <= k_last; ++k)
-      if (h->nxv[k] != nk || (k < h->N && h->nuv[k] != mk))
-        return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "knot points %d and %d differ in dimension: one constraint block takes one [x; u] size "
-                                                "(register it per range, like ALTROSolver::SetConstraint per index)", k_first, k);
-    w = nk + mk;
-  }
+  const int w = ad.w;
   AlDef d{cone, p, g_per_problem ? 1 : 0, (int)h->al_G.size(), 0, user, w};
   h->al_G.insert(h->al_G.end(), G, G + (size_t)p * w);
   h->al_g.emplace_back(g, g + (size_t)p * (g_per_problem ? h->batch : 1));
@@ -1008,35 +844,21 @@ int altro_hip_add_user_constraint(altro_hip_batch* h, int k_first, int k_last, i
     return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_set_model_source must come first, with a source that defines "
                                        "altro_user_constraint and altro_user_constraint_jacobian (plans LANE and GENERIC / MFMA32)");
   if (id < 0) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "constraint id %d", id);
-  if (tile) {   // one slot per block, AL_TILE_USER_MAXC such slots per knot point (kernels/al_types.h); the six slots in all: add_block
-    if (cone < CONE_EQUALITY || cone > CONE_SOC) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "unknown cone %d", cone);
-    const int pmax = cone == CONE_SOC ? AL_MAXSOC : AL_MAXP;
-    if (p < 1 || p > pmax)
-      return fail(ALTRO_HIP_ERR_UNSUPPORTED, "a constraint block from source has 1 .. %d rows on plan MFMA16 (%s: one slot; got %d): "
-                                             "ALTRO_HIP_PLAN_GENERIC takes 32", pmax, cone == CONE_SOC ? "AL_MAXSOC" : "AL_MAXP", p);
-    for (int k = std::max(k_first, 0); k <= std::min(k_last, h->N); ++k) {
-      int slots = 1;
-      for (int j = 0; j < h->al_knots[k].ncon; ++j) slots += h->al_defs[h->al_knots[k].def[j]].user ? 1 : 0;
-      if (slots > AL_TILE_USER_MAXC)
-        return fail(ALTRO_HIP_ERR_UNSUPPORTED, "at most %d constraint blocks from source per knot point on plan MFMA16 (AL_TILE_USER_MAXC; k = %d "
-                                               "would have %d): ALTRO_HIP_PLAN_GENERIC takes 32 rows of them", AL_TILE_USER_MAXC, k, slots);
-    }
-  }
-  if (gen) {   // plan GENERIC stages the user blocks' values and Jacobians of a knot point in LDS (kernels/ilqr_generic.hip: GEN_USER_MAXROWS)
-    if (p < 1 || p > GEN_USER_MAXROWS)
-      return fail(ALTRO_HIP_ERR_UNSUPPORTED, "a constraint block from source has 1 .. %d rows on plan GENERIC (GEN_USER_MAXROWS; got %d)",
-                  GEN_USER_MAXROWS, p);
-    for (int k = std::max(k_first, 0); k <= std::min(k_last, h->N); ++k) {
-      int rows = p;
-      for (int j = 0; j < h->al_knots[k].ncon; ++j) {
-        const AlDef& d0 = h->al_defs[h->al_knots[k].def[j]];
-        if (d0.user) rows += d0.p;
-      }
-      if (rows > GEN_USER_MAXROWS)
-        return fail(ALTRO_HIP_ERR_UNSUPPORTED, "at most %d rows of constraint blocks from source per knot point on plan GENERIC "
-                                               "(GEN_USER_MAXROWS; k = %d would have %d)", GEN_USER_MAXROWS, k, rows);
-    }
-  }
+  // one slot per block and AL_TILE_USER_MAXC such slots per knot point on plan MFMA16, GEN_USER_MAXROWS rows per block and per knot
+  // point on plan GENERIC (al_tables.h: al_admit); every other limit: add_block
+  const AlAdmit ad = al_admit(al_input(h), k_first, k_last, cone, p, id + 1);
+  if (ad.limit == AL_LIMIT_USER_CONE) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "unknown cone %d", cone);
+  if (ad.limit == AL_LIMIT_USER_ROWS && tile)
+    return fail(ALTRO_HIP_ERR_UNSUPPORTED, "a constraint block from source has 1 .. %d rows on plan MFMA16 (%s: one slot; got %d): "
+                                           "ALTRO_HIP_PLAN_GENERIC takes 32", ad.pmax, cone == CONE_SOC ? "AL_MAXSOC" : "AL_MAXP", p);
+  if (ad.limit == AL_LIMIT_USER_ROWS)
+    return fail(ALTRO_HIP_ERR_UNSUPPORTED, "a constraint block from source has 1 .. %d rows on plan GENERIC (GEN_USER_MAXROWS; got %d)", ad.pmax, p);
+  if (ad.limit == AL_LIMIT_USER_KNOT && tile)
+    return fail(ALTRO_HIP_ERR_UNSUPPORTED, "at most %d constraint blocks from source per knot point on plan MFMA16 (AL_TILE_USER_MAXC; k = %d "
+                                           "would have %d): ALTRO_HIP_PLAN_GENERIC takes 32 rows of them", ad.cmax, ad.k, ad.count);
+  if (ad.limit == AL_LIMIT_USER_KNOT)
+    return fail(ALTRO_HIP_ERR_UNSUPPORTED, "at most %d rows of constraint blocks from source per knot point on plan GENERIC "
+                                           "(GEN_USER_MAXROWS; k = %d would have %d)", ad.cmax, ad.k, ad.count);
   std::vector<double> G((size_t)std::max(p, 0) * (h->n + h->m), 0.0), g((size_t)std::max(p, 0), 0.0);   // placeholders: never read
   return add_block(h, k_first, k_last, cone, p, G.data(), g.data(), 0, id + 1);
 }

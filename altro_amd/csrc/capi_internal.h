@@ -23,6 +23,7 @@
 #include "kernels/ilqr_generic.hip"
 #include "kernels/mfma16_layout.h"
 #include "linesearch_sm.h"
+#include "al_tables.h"
 #include "loop_fields.h"
 #include "rtc_unit.h"
 
@@ -133,26 +134,18 @@ struct altro_hip_batch {
   // augmented-Lagrangian constraint blocks (plan LANE): host mirrors + device tables, uploaded lazily
   std::vector<AlDef> al_defs;
   std::vector<AlKnotBig> al_knots;       // (the device table is AlKnot for plans LANE / MFMA16, AlKnotBig for plan GENERIC)
-  int al_uniform = 0, al_rows_per_knot = 0;  // knot points 0..N-1 carry the same blocks (kernels/al_types.h)
   std::vector<double> al_G;                  // pool of G blocks, column-major p x (n+m)
   std::vector<std::vector<double>> al_g;     // per block: [p] or [batch][p]
   int al_rows = 0;
+  capi::AlSummary al_sum;                         // what al_upload derived from the blocks (al_tables.h), assigned as one value
   bool al_dirty = false;
   AlKnot* al_d_knots = nullptr;
   AlKnotBig* al_d_big = nullptr;
   void *al_d_G = nullptr, *al_d_g = nullptr, *al_d_z = nullptr;
   void* al_d_Gpad = nullptr;                 // AlTable::Gpad (plan MFMA16)
-  int al_Gpad_count = 0;
-  bool al_all_gsel = false;              // plan GENERIC: every block is bound-type (the Hessian blocks change on their diagonals only)
   double* g_stat_part = nullptr; size_t g_stat_part_bytes = 0;   // row32_stationarity_kernel's per-chunk maxima (capi_ilqr.hip: gen_run)
   int* al_d_gsel = nullptr;              // plan GENERIC: AlTable::gsel (bound-type blocks)
   int* al_d_guser = nullptr;             // plan GENERIC: AlTable::guser (blocks from the caller's source), null without such a block
-  bool al_row32_ok = false;              // every block fits kernels/ilqr_row32.hip (row-wise cone, <= 32 rows)
-  int al_max_ncon = 0;                   // most blocks (plan MFMA16: slots, al_types.h) any knot point has
-  int al_G_count = 0;                        // elements of the device G pool
-  int al_has_soc = 0;                        // some block is a second-order cone
-  bool al_has_user = false;                  // some block comes from the caller's source (AlDef::user): plan MFMA16 then runs the run-time module's constraint kernels
-  int al_all_sel = 0;                        // every block is bound-type (rows +-e_idx: AlKnot::sel)
   double expand_penalty_scaling = 10.0, expand_penalty_max = 1e8;   // what EXPAND_DUAL's look-ahead of PenaltyUpdate needs
   const int* bwd_active = nullptr;           // per-problem mask for the backward sweep inside ilqr_solve
   const double* bwd_reg = nullptr;           // per-problem regularisation inside ilqr_solve (retry extension)

@@ -249,7 +249,7 @@ int rtc_gen_al_launch(altro_hip_batch* h, int which, const IlqrGenArgs<double>& 
 static int rtc_tile_current(altro_hip_batch* h, const IlqrWaveArgs<double>& a, const RtcModule** out) {
   if (h->rtc_source.empty()) return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_set_model_source has not been called");
   const int ck = (a.al.enabled ? 1 : 0) | (a.cost_dense ? 2 : 0) | ((a.al.enabled && a.al.max_ncon > AL_MAXC) ? 4 : 0) |
-                 ((a.al.enabled && h->al_has_user) ? 8 : 0);
+                 ((a.al.enabled && h->al_sum.has_user) ? 8 : 0);
   if (!h->rtc || h->rtc_ck != ck) {
     RtcModule* m2 = nullptr;
     if (const int rc = rtc_tile_module(h, ck, &m2)) return rc;
@@ -276,7 +276,7 @@ int rtc_tile_launch(altro_hip_batch* h, int which, const IlqrWaveArgs<double>& a
   if (const int rc = rtc_tile_current(h, a, &mod)) return rc;
   // the merit kernels' dynamic LDS (padded constraint Jacobians; with a slot from the source at least one definition's worth: such a
   // slot's unused row read lands there when the handle has no block given as data)
-  const unsigned gsh = a.al.enabled ? (unsigned)std::max(a.al.Gpad_count, h->al_has_user ? AL_GP_DEF : 0) * 8u : 0u;
+  const unsigned gsh = a.al.enabled ? (unsigned)std::max(a.al.Gpad_count, h->al_sum.has_user ? AL_GP_DEF : 0) * 8u : 0u;
   auto go = [&](int w, unsigned gx, unsigned gy) {
     return rtc_go(h, mod->fn[w], gx, gy, 64, (w == RTT_MERIT || w == RTT_MERIT2) ? gsh : 0u, a, "launch of the run-time compiled tile kernel %d failed: %s", w);
   };
@@ -379,8 +379,8 @@ int altro_hip_set_model_source(altro_hip_batch* h, const char* source, float tim
     h->rtc_source = src;
     h->model = ModelParams{MODEL_USER, timestep, 0, 2.7, 1.5};
     RtcModule* tm = nullptr;   // compile now: a source that does not build must fail HERE, with the compiler's log
-    if (!h->al_defs.empty() && (rc = al_upload(h))) { h->rtc_source.clear(); h->model = ModelParams{MODEL_LINEAR, 0.0f, 0, 2.7, 1.5}; return rc; }   // (al_max_ncon: the slots of the blocks so far)
-    const bool user = !h->al_defs.empty() && h->al_has_user;   // (a source that replaces one whose blocks the handle still has)
+    if (!h->al_defs.empty() && (rc = al_upload(h))) { h->rtc_source.clear(); h->model = ModelParams{MODEL_LINEAR, 0.0f, 0, 2.7, 1.5}; return rc; }   // (al_sum.max_ncon: the slots of the blocks so far)
+    const bool user = !h->al_defs.empty() && h->al_sum.has_user;   // (a source that replaces one whose blocks the handle still has)
     if (user && !c_val) {
       h->rtc_source.clear(); h->model = ModelParams{MODEL_LINEAR, 0.0f, 0, 2.7, 1.5};
       return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "the handle has constraint blocks from source (altro_hip_add_user_constraint): the new source must define "
@@ -389,7 +389,7 @@ int altro_hip_set_model_source(altro_hip_batch* h, const char* source, float tim
     // (a flagged handle whose source defines the pair announces blocks from it: the unit compiled -- and checked -- here is the one a
     //  handle with such a block launches, at the width of the blocks registered so far; rtc_tile_current builds another if it turns out otherwise)
     const bool expect_user = user || (tile_user && c_val);
-    const int ck = ((h->al_defs.empty() && !expect_user) ? 0 : 1) | (h->cost_dense ? 2 : 0) | ((!h->al_defs.empty() && h->al_max_ncon > AL_MAXC) ? 4 : 0) | (expect_user ? 8 : 0);
+    const int ck = ((h->al_defs.empty() && !expect_user) ? 0 : 1) | (h->cost_dense ? 2 : 0) | ((!h->al_defs.empty() && h->al_sum.max_ncon > AL_MAXC) ? 4 : 0) | (expect_user ? 8 : 0);
     if ((rc = rtc_tile_module(h, ck, &tm))) { h->rtc_source.clear(); return rc; }
     h->rtc = tm; h->rtc_ck = ck; h->model_set = true; h->rtc_has_constraints = tile_user && c_val && c_jac;
     return model_takes_dynamics(h);

@@ -111,7 +111,7 @@ int SolveRun::configure(const altro_hip_solve_options* opts) {
   if (opts) o = *opts;
   else altro_hip_default_solve_options(&o);
   h->forms = forms0 | o.forms;
-  // the constraint tables (and the flags derived from them: al_row32_ok, al_all_gsel, read below) describe the blocks as they are NOW:
+  // the constraint tables (and the flags derived from them: al_sum.row32_ok, al_sum.all_gsel, read below) describe the blocks as they are NOW:
   // a block added since the last solve must not leave this one choosing kernels for the old set
   if (int rc = al_upload(h)) return rc;
   la.prob = h->i_prob; la.alpha = h->i_alpha; la.active = h->i_active; la.phi = h->i_phi; la.dphi = h->i_dphi;
@@ -154,8 +154,8 @@ int SolveRun::configure(const altro_hip_solve_options* opts) {
   // after this solve's first (full) Hessian expansion the later ones store 16 values per knot point instead of 158 (EXPAND_DIAG)
   // (plan GENERIC / MFMA32, every block bound-type -- AlTable::gsel --: the constraints touch the Hessian blocks' diagonals only,
   //  whatever the cost's own blocks are: generic_expand_al_kernel then rewrites n + m entries per knot point instead of (n + m)^2)
-  diag_mode = ((h->plan == ALTRO_HIP_PLAN_MFMA16 && al && !h->cost_dense && h->al_all_sel) ||
-               (h->plan == ALTRO_HIP_PLAN_GENERIC && al && !h->ragged && h->al_all_gsel)) ? EXPAND_DIAG : 0;
+  diag_mode = ((h->plan == ALTRO_HIP_PLAN_MFMA16 && al && !h->cost_dense && h->al_sum.all_sel) ||
+               (h->plan == ALTRO_HIP_PLAN_GENERIC && al && !h->ragged && h->al_sum.all_gsel)) ? EXPAND_DIAG : 0;
   running = h->batch;
   // Affine line-search trials (kernels/ilqr_merit2_dpp.hip, AFF): plan MFMA16, dynamics as data, fp64; the sweep's phi(0) evaluation
   // leaves the base trajectory and its sensitivity behind.  ALTRO_HIP_FORM_ROLLOUT_ROUNDS keeps every trial a rollout.
