@@ -8,7 +8,7 @@
  * the MI355X: host blocks are gathered into one device arena, the GENERIC HIP kernel
  * (altro_amd/csrc/kernels/tvlqr_generic.hip, one wavefront) performs the recursion with the
  * reference's operation order, and the results are scattered back to the caller's pointers.
- *   - per-knot-point dimensions nx[k], nu[k] are honoured (max 32 each);
+ *   - per-knot-point dimensions nx[k], nu[k] are honoured (max 256 each: TVLQR_UNSUPPORTED_SIZE beyond);
  *   - return value: TVLQR_SUCCESS (-1) or the knot point whose Quu + reg I is not positive definite,
  *     with K_k = Qux, d_k = -Qu left unsolved exactly like tvlqr.cpp:162-164;
  *   - all of Qxx..Qu and the five *_tmp blocks are written, as the reference leaves them;

@@ -1,0 +1,324 @@
+"""Makes tests/golden/loop_phases_<config>.npz: the extended-precision reference of the iLQR loop's phases on the seven configurations
+of tests/cone_region_cases.py (N = 5, batch 7, zero duals, penalties 1 and 50).
+
+    python tests/golden/make_loop_phase_fixtures.py [config ...]      (needs mpmath; every configuration when none is named)
+
+Per configuration and penalty the phase sequence of cone_region_cases.expand / phases is restated with mpmath at 60 digits and rounded
+to double once; a second run at 120 digits must give the identical arrays:
+  constraint values c = G [x; u] - g, ze = -rho c;  the projection onto the dual cone with its Jacobian J and, outside a second-order
+  cone, the Hessian term d/dz (J^T z_proj);  the AL cost |z_proj|^2 / (2 rho), gradient -G^T J^T z_proj and Hessian
+  rho (J G)^T (J G) + rho G^T Hs G;  the cost expansion (tracking form: q = -Qd xref, r = -Rd uref, c = the constant, all exact);
+  the backward sweep (f = 0: the expansion is about the guess);  the closed-loop rollout of the merit function from x0 at alpha = 0 and
+  alpha_b with phi, phi' and the candidates;  feasibility and stationarity of the last candidate.
+Dynamics are linear in all seven; the two double-integrator configurations take the A, B that oracle/models_oracle.c forms with
+H_DI (problems.di_blocks: b = h h / 2 in float arithmetic) as data.
+
+Branches are FROZEN: which region a cone's ze lies in and which orthant rows are active is taken per (evaluation point, block,
+problem, knot point, row) from the fp64 classification (loop_scale_cases.class_tables: cone_region_cases.classify_* at the guess and
+at the oracle's two candidates), because at an exact tie the projection is continuous and its Jacobian is not; that branch's formulas
+are what is evaluated here.  The table is stored, with the number of entries at which the comparison in extended precision would
+have chosen otherwise (flips: zero in all seven).
+
+Stored:  sum  checksum of the inputs (loop_scale_cases.inputs through golden_cases.checksum);  tab_<i>  the table of penalty RHOS[i];
+ref_<i>_<quantity>  the results in the old units, batch-shaped, in the layouts of the oracle's getters;  ecpu_<i>  blockerr of the
+oracle against them per quantity (loop_scale_cases.QUANTITIES);  flips_<i>.   Data only."""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT)
+
+from tests import cone_region_cases as crc            # noqa: E402
+from tests import loop_scale_cases as lsc             # noqa: E402
+from tests import problems                            # noqa: E402
+from tests.golden_cases import checksum               # noqa: E402
+
+N, BATCH, RHOS = crc.N, crc.BATCH, crc.RHOS
+
+
+def mp_phases(cfg, b, rho, tab, digits):
+    """Problem b of `cfg` at penalty rho with the branches of `tab` ([3, blocks, BATCH, N + 1, rows]: the guess, the candidate of
+    alpha = 0, the candidate of alpha_b).  Returns ({quantity: float array in the oracle's layout}, flips)."""
+    import mpmath as mp
+    mp.mp.dps = digits
+    n, m, w = cfg.n, cfg.m, cfg.w
+    F = lambda v: mp.mpf(float(v))
+    V = lambda a: [F(v) for v in a]
+    M = lambda a, r, c: [[F(a[i + r * j]) for j in range(c)] for i in range(r)]          # column-major block -> rows
+    dot = mp.fdot
+    zero, half = mp.mpf(0), mp.mpf(1) / 2
+    mv = lambda A, v: [dot(row, v) for row in A]
+    mtv = lambda A, v: [dot([A[i][j] for i in range(len(A))], v) for j in range(len(A[0]))]
+    add = lambda a, c: [x + y for x, y in zip(a, c)]
+    rho_ = F(rho)
+    flips = [0]
+
+    # ---- inputs ----
+    if cfg.dyn == "di":
+        A_, B_ = problems.di_blocks(m, crc.H_DI)
+        A = [[[F(v) for v in row] for row in A_]] * N
+        B = [[[F(v) for v in row] for row in B_]] * N
+        aff = [[zero] * n] * N
+    else:
+        p = cfg.p
+        A = [M(p["A"][b, k], n, n) for k in range(N)]
+        B = [M(p["B"][b, k], n, m) for k in range(N)]
+        aff = [V(p["f"][b, k]) for k in range(N)]
+    cost = []                                          # per knot point: (Q rows, R rows, H rows, q, r, c)
+    for k in range(N + 1):
+        kk = min(k, N - 1)
+        if cfg.dense:
+            p = cfg.p
+            cost.append((M(p["Q"][b, k], n, n), M(p["R"][b, kk], m, m), M(p["H"][b, kk], m, n), V(p["q"][b, k]), V(p["r"][b, kk]), F(p["c"][b, k])))
+        else:
+            if cfg.dyn == "di":
+                Qd, Rd, xr, ur = V(cfg.Qd), V(cfg.Rd), V(cfg.xref), [zero] * m
+            else:
+                p = cfg.p
+                Qd, Rd, xr, ur = V(p["Qd"][b, k]), V(p["Rd"][b, kk]), V(p["xref"][b, k]), V(p["uref"][b, kk])
+            c = half * dot([a * r for a, r in zip(Qd, xr)], xr) + (half * dot([a * r for a, r in zip(Rd, ur)], ur) if k < N else zero)
+            cost.append(([[Qd[i] if i == j else zero for j in range(n)] for i in range(n)],
+                         [[Rd[i] if i == j else zero for j in range(m)] for i in range(m)], [[zero] * n for _ in range(m)],
+                         [-(a * r) for a, r in zip(Qd, xr)], [-(a * r) for a, r in zip(Rd, ur)], c))
+    Gm = [[V(row) for row in bl["G"]] for bl in cfg.blocks]
+    gm = [V(bl["g"]) for bl in cfg.blocks]
+
+    def stage(k, x, u):
+        """The cost's own value and gradient at (x, u) of knot point k."""
+        Q, R, H, q, r, c = cost[k]
+        Qx = mv(Q, x)
+        J = half * dot(x, Qx) + dot(q, x) + c
+        gx, gu = add(Qx, q), None
+        if k < N:
+            Ru, Hx = mv(R, u), mv(H, x)
+            J += half * dot(u, Ru) + dot(r, u) + dot(u, Hx)
+            gx = add(gx, mtv(H, u))
+            gu = add(add(Ru, r), Hx)
+        return J, gx, gu
+
+    def al(k, x, u, cls, hess):
+        """The AL terms at (x, u) of knot point k with the branches cls [blocks, rows]: cost, gradient over [x; u], Hessian (or None),
+        violation."""
+        z = x + (u if k < N else [zero] * m)
+        J, gz, viol = zero, [zero] * w, zero
+        W = [[zero] * w for _ in range(w)] if hess else None
+        for j in cfg.at(k):
+            bl, G, g, t = cfg.blocks[j], Gm[j], gm[j], cls[j]
+            pp = bl["p"]
+            val = [dot(G[i], z) - g[i] for i in range(pp)]
+            ze = [-(rho_ * c) for c in val]
+            Jd = Jf = Hs = None
+            if bl["kind"] == "eq":
+                zp, Jd = ze, [1] * pp
+                viol = max([viol] + [abs(c) for c in val])
+            elif bl["kind"] == "orth":
+                Jd = [int(t[i]) for i in range(pp)]
+                flips[0] += sum(int(Jd[i] != (1 if ze[i] <= 0 else 0)) for i in range(pp))
+                zp = [ze[i] if Jd[i] else zero for i in range(pp)]
+                viol = max([viol] + [abs(val[i]) for i in range(pp) if Jd[i]])
+            else:
+                nv = pp - 1
+                v, s = ze[:nv], ze[nv]
+                a = mp.sqrt(dot(v, v))
+                region = int(t[0])
+                flips[0] += int(region != (0 if a <= -s else (1 if a <= s else 2)))
+                if region == 0:                        # ze below its cone: projection 0, the value itself inside: no violation
+                    continue
+                if region == 1:                        # ze inside: identity; the value is below its cone: its projection is 0
+                    zp, Jd = ze, [1] * pp
+                    viol = max([viol] + [abs(c) for c in val])
+                else:
+                    c = half * (1 + s / a)
+                    zp = [c * e for e in v] + [c * a]
+                    Jf = [[zero] * pp for _ in range(pp)]
+                    for i in range(nv):
+                        for jj in range(nv):
+                            Jf[i][jj] = -half * s / (a * a * a) * v[i] * v[jj] + (c if i == jj else zero)
+                        Jf[i][nv] = half * v[i] / a
+                        Jf[nv][i] = (-half * s / (a * a) + c / a) * v[i]
+                    Jf[nv][nv] = half
+                    vv, sv = val[:nv], val[nv]         # the value's own projection: outside as well
+                    av = mp.sqrt(dot(vv, vv))
+                    cv = half * (1 + sv / av)
+                    viol = max([viol] + [abs(cv * e - e) for e in vv] + [abs(cv * av - sv)])
+                    if hess:
+                        bs, vbv = zp[nv], dot(v, zp[:nv])
+                        Hs = [[zero] * pp for _ in range(pp)]
+                        for i in range(nv):
+                            hi = dot([-v[i] * v[jj] / (a * a) + (1 if i == jj else 0) for jj in range(nv)], zp[:nv])
+                            Hs[i][nv] = Hs[nv][i] = hi / (2 * a)
+                            for jj in range(i + 1):
+                                vij = v[i] * v[jj]
+                                H1 = hi * v[jj] * (-s / (a * a * a))
+                                H2 = vij * (2 * vbv) / (a * a * a * a) - v[i] * zp[jj] / (a * a)
+                                H3 = -vij / (a * a)
+                                if i == jj:
+                                    H2 -= vbv / (a * a)
+                                    H3 += 1
+                                Hs[i][jj] = Hs[jj][i] = (H1 + H2 * (s / a) + H3 * (bs / a)) / 2
+            J += dot(zp, zp) / (2 * rho_)
+            if Jd is not None:
+                rows = [i for i in range(pp) if Jd[i]]
+                jvp = [zp[i] if Jd[i] else zero for i in range(pp)]
+                JG = [G[i] for i in rows]
+            else:
+                jvp = [dot([Jf[kk][i] for kk in range(pp)], zp) for i in range(pp)]
+                cols = [[G[kk][e] for kk in range(pp)] for e in range(w)]
+                JG = [[dot(Jf[i], cols[e]) for e in range(w)] for i in range(pp)]
+            for e in range(w):
+                gz[e] -= dot([G[i][e] for i in range(pp)], jvp)
+            if hess:
+                ct = [[row[e] for row in JG] for e in range(w)]
+                for e in range(w):
+                    for f in range(e + 1):
+                        W[e][f] += rho_ * dot(ct[e], ct[f])
+                if Hs is not None:
+                    cols = [[G[kk][e] for kk in range(pp)] for e in range(w)]
+                    HG = [[dot(Hs[i], cols[e]) for e in range(w)] for i in range(pp)]
+                    hgc = [[row[e] for row in HG] for e in range(w)]
+                    for e in range(w):
+                        for f in range(e + 1):
+                            W[e][f] += rho_ * dot(cols[e], hgc[f])
+        if hess:
+            for e in range(w):
+                for f in range(e):
+                    W[f][e] = W[e][f]
+        return J, gz, W, viol
+
+    # ---- the expansion about the guess ----
+    xn = [V(cfg.x[b, k]) for k in range(N + 1)]
+    un = [V(cfg.u[b, k]) for k in range(N)] + [[zero] * m]
+    lx, lu, lxx, luu, lux = [], [], [], [], []
+    for k in range(N + 1):
+        _, gx, gu = stage(k, xn[k], un[k])
+        _, gz, W, _ = al(k, xn[k], un[k], tab[0][:, b, k], True)
+        Q, R, H = cost[k][:3]
+        lx.append(add(gx, gz[:n]))
+        lxx.append([[Q[i][j] + W[i][j] for j in range(n)] for i in range(n)])
+        if k < N:
+            lu.append(add(gu, gz[n:]))
+            luu.append([[R[i][j] + W[n + i][n + j] for j in range(m)] for i in range(m)])
+            lux.append([[H[i][j] + W[n + i][j] for j in range(n)] for i in range(m)])
+    out = dict(lx=lx, lu=lu)
+
+    # ---- the backward sweep (f = 0) ----
+    mx = mp.matrix
+    P, pv, K, d = [None] * (N + 1), [None] * (N + 1), [None] * N, [None] * N
+    P[N], pv[N] = mx(lxx[N]), mx(lx[N])
+    for k in range(N - 1, -1, -1):
+        Ak, Bk = mx(A[k]), mx(B[k])
+        AtP, BtP = Ak.T * P[k + 1], Bk.T * P[k + 1]
+        Qxx, Quu, Qux = mx(lxx[k]) + AtP * Ak, mx(luu[k]) + BtP * Bk, mx(lux[k]) + BtP * Ak
+        Qx, Qu = mx(lx[k]) + Ak.T * pv[k + 1], mx(lu[k]) + Bk.T * pv[k + 1]
+        L = mp.matrix(m, m)
+        for j in range(m):
+            s = Quu[j, j] - mp.fsum(L[j, c] * L[j, c] for c in range(j))
+            assert s > 0, ("the exact recursion is indefinite", cfg.name, b, k, j)
+            L[j, j] = mp.sqrt(s)
+            for i in range(j + 1, m):
+                L[i, j] = (Quu[i, j] - mp.fsum(L[i, c] * L[j, c] for c in range(j))) / L[j, j]
+
+        def solve(rhs, cols):
+            X = mp.matrix(m, cols)
+            for c in range(cols):
+                yv = [None] * m
+                for i in range(m):
+                    yv[i] = (rhs[i, c] - mp.fsum(L[i, j] * yv[j] for j in range(i))) / L[i, i]
+                for i in range(m - 1, -1, -1):
+                    X[i, c] = (yv[i] - mp.fsum(L[j, i] * X[j, c] for j in range(i + 1, m))) / L[i, i]
+            return X
+        K[k], d[k] = solve(Qux, n), -solve(Qu, 1)
+        QK, KtQux = Quu * K[k], K[k].T * Qux
+        P[k] = Qxx + QK.T * K[k] - KtQux - KtQux.T
+        pv[k] = Qx - QK.T * d[k] - K[k].T * Qu + Qux.T * d[k]
+    rowsof = lambda X, r, c: [[X[i, j] for j in range(c)] for i in range(r)]
+    Kr, Pr = [rowsof(K[k], m, n) for k in range(N)], [rowsof(P[k], n, n) for k in range(N + 1)]
+    dr, pr = [[d[k][i] for i in range(m)] for k in range(N)], [[pv[k][i] for i in range(n)] for k in range(N + 1)]
+    out.update(K=Kr, d=dr, P=Pr, p=pr)
+
+    # ---- the merit function ----
+    def merit(alpha, ti):
+        xc, uc, yc, gxc, guc = [V(cfg.x0[b])], [], [], [], []
+        dxa = [zero] * n
+        phi = dphi = zero
+        worst = zero
+        for k in range(N + 1):
+            dx = [a - c for a, c in zip(xc[k], xn[k])]
+            yc.append(add(mv(Pr[k], dx), pr[k]))
+            if k < N:
+                Kdx = mv(Kr[k], dx)
+                uc.append([un[k][i] + (-Kdx[i] + alpha * dr[k][i]) for i in range(m)])
+                xc.append(add(add(mv(A[k], xc[k]), mv(B[k], uc[k])), aff[k]))
+            Jc, gx, gu = stage(k, xc[k], uc[k] if k < N else None)
+            Ja, gz, _, viol = al(k, xc[k], uc[k] if k < N else None, tab[ti][:, b, k], False)
+            phi += Jc + Ja
+            worst = max(worst, viol)
+            gxc.append(add(gx, gz[:n]))
+            dphi += dot(gxc[k], dxa)
+            if k < N:
+                guc.append(add(gu, gz[n:]))
+                Kda = mv(Kr[k], dxa)
+                dua = [-Kda[i] + dr[k][i] for i in range(m)]
+                dphi += dot(guc[k], dua)
+                dxa = add(mv(A[k], dxa), mv(B[k], dua))
+        return phi, dphi, xc, uc, yc, gxc, guc, worst
+
+    out["phi0"], out["dphi0"] = merit(zero, 1)[:2]
+    out["phi"], out["dphi"], xc, uc, yc, gxc, guc, out["feas"] = merit(F(crc.ALPHAS[b]), 2)
+    out["x"], out["u"] = xc, uc
+    stat = zero
+    for k in range(N):
+        ty, tu = mtv(A[k], yc[k + 1]), mtv(B[k], yc[k + 1])
+        stat = max([stat] + [abs(gxc[k][i] + ty[i] - yc[k][i]) for i in range(n)] + [abs(guc[k][i] + tu[i]) for i in range(m)])
+    out["stat"] = max([stat] + [abs(gxc[N][i] - yc[N][i]) for i in range(n)])
+
+    # ---- rounded once, in the oracle's layouts ----
+    fl = lambda rows: np.array([[float(v) for v in r] for r in rows])
+    colmajor = lambda mats: np.array([[float(Mx[i][j]) for j in range(len(Mx[0])) for i in range(len(Mx))] for Mx in mats])
+    res = {q: fl(out[q]) for q in ("lx", "lu", "d", "p", "x", "u")}
+    res["K"], res["P"] = colmajor(out["K"]), colmajor(out["P"])
+    for q in lsc.SCALARS:
+        res[q] = float(out[q])
+    return res, flips[0]
+
+
+def one(args):
+    name, ri, b, digits = args
+    cfg = crc.config(name)
+    return mp_phases(cfg, b, RHOS[ri], lsc.class_tables(cfg, RHOS[ri]), digits)
+
+
+def make(name, pool):
+    cfg = crc.config(name)
+    arrays = {"sum": checksum(lsc.inputs(cfg))}
+    jobs = [(name, ri, b, digits) for ri in range(len(RHOS)) for digits in (60, 120) for b in range(BATCH)]
+    done = dict(zip(jobs, pool.map(one, jobs, chunksize=1)))
+    for ri, rho in enumerate(RHOS):
+        per, per2 = ([done[(name, ri, b, digits)] for b in range(BATCH)] for digits in (60, 120))
+        ref = {q: np.stack([np.asarray(r[0][q], dtype=np.float64) for r in per]) for q in lsc.QUANTITIES}
+        ref2 = {q: np.stack([np.asarray(r[0][q], dtype=np.float64) for r in per2]) for q in lsc.QUANTITIES}
+        for q in lsc.QUANTITIES:
+            assert np.array_equal(ref[q], ref2[q]), ("60 and 120 digits round differently", name, rho, q)
+            arrays["ref_%d_%s" % (ri, q)] = ref[q]
+        arrays["tab_%d" % ri] = lsc.class_tables(cfg, rho)
+        arrays["flips_%d" % ri] = np.array(sum(r[1] for r in per), dtype=np.int64)
+        e = lsc.errors(lsc.oracle_phases(cfg, rho), ref)
+        arrays["ecpu_%d" % ri] = np.array([e[q] for q in lsc.QUANTITIES])
+        print(name, "rho", rho, "flips", int(arrays["flips_%d" % ri]), " ".join("%s %.1e" % (q, e[q]) for q in lsc.QUANTITIES), flush=True)
+    path = lsc.fixture_path(name)
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED) as z:       # np.savez stamps the time of day into the archive: not reproducible
+        for k in sorted(arrays):
+            with z.open(zipfile.ZipInfo(k + ".npy", (1980, 1, 1, 0, 0, 0)), "w") as f:
+                np.lib.format.write_array(f, np.asarray(arrays[k]), allow_pickle=False)
+    print("%s: %d bytes" % (os.path.relpath(path, ROOT), os.path.getsize(path)), flush=True)
+
+
+if __name__ == "__main__":
+    import multiprocessing
+    names = sys.argv[1:] or list(crc.CONFIGS)
+    with multiprocessing.Pool(min(14, os.cpu_count() or 1)) as pool:
+        for nm in names:
+            make(nm, pool)

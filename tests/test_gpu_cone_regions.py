@@ -40,9 +40,9 @@ TOL_NEW = dict(d=1e-12, P=1e-13, p=1e-13, duals=1e-12)
 PLAN = {"LANE": altro_amd.PLAN_LANE, "MFMA16": altro_amd.PLAN_MFMA16, "GENERIC": altro_amd.PLAN_GENERIC, "MFMA32": altro_amd.PLAN_MFMA32}
 
 
-def make_hip(cfg):
+def make_hip(cfg, dtype=altro_amd.F64, flags=0):
     n, m = cfg.n, cfg.m
-    bt = altro_amd.Batch(N, n, m, BATCH, plan=altro_amd.PLAN_GENERIC if cfg.plan == "GENERIC" else altro_amd.PLAN_AUTO)
+    bt = altro_amd.Batch(N, n, m, BATCH, dtype=dtype, plan=altro_amd.PLAN_GENERIC if cfg.plan == "GENERIC" else altro_amd.PLAN_AUTO, flags=flags)
     bt.set_forms(altro_amd.FORM_ROLLOUT_ROUNDS)
     if cfg.dyn == "di":
         bt.set_model(altro_amd.MODEL_DOUBLE_INTEGRATOR, crc.H_DI)
