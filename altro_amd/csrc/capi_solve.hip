@@ -129,8 +129,6 @@ int SolveRun::configure(const altro_hip_solve_options* opts) {
     return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "regularisation retry needs reg_initial >= 0, reg_scale > 1, 0 < reg_min <= reg_max");
   if (al && !(o.penalty_initial > 0.0 && o.penalty_scaling > 0.0 && o.penalty_max > 0.0))
     return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "penalty_initial, penalty_scaling and penalty_max must be positive");
-  if (h->plan == ALTRO_HIP_PLAN_GENERIC && o.reg_retry_max > 0)
-    return fail(ALTRO_HIP_ERR_UNSUPPORTED, "the regularisation retry is built for plans LANE and MFMA16 (plan GENERIC: reg_retry_max = 0)");
   la.ls = ls_default_options();
   la.ls.try_cubic_first = 1;                                   // solver.cpp:248
   la.ls.use_backtracking = o.use_backtracking_linesearch;      // solver.cpp:417

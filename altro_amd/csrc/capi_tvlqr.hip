@@ -90,6 +90,10 @@ GenericArgs<T> generic_args(altro_hip_batch* h, double reg) {
   a.store_q = (h->flags & ALTRO_HIP_STORE_QBLOCKS) ? 1 : 0;
   a.want_y = 1;
   a.no_f = h->ilqr_linear ? 1 : 0;
+  // A solve with the regularisation schedule on (bwd_reg is set for it alone): per-problem reg, and only the problems the mask names --
+  // the running ones at the head of a sweep, the failed ones in a retry (a problem that succeeded has relaxed its reg already and must
+  // not be swept with it).  Any other launch is the one it always was: every problem, including those a solve has stopped.
+  if (h->bwd_reg) { a.active = h->bwd_active; a.reg_pp = h->bwd_reg; }
   return a;
 }
 

@@ -51,6 +51,10 @@ struct GenericArgs {
   int no_f = 0;              // backward sweep: treat f as zero (altro_hip_batch::ilqr_linear: the expansion of the iLQR loop)
   T* ws = nullptr;           // generic_backward_kernel<T, true>: per-problem work blocks in global memory instead of LDS
   int64_t ws_stride = 0;     // elements between consecutive problems' work blocks (>= generic_backward_lds_bytes / sizeof(T))
+  // backward sweep inside altro_hip_ilqr_solve with the regularisation schedule on (as Mfma16Args / Tile32Args have them); null: every
+  // problem, `reg` for all
+  const int* active = nullptr;      // [batch] per-problem mask: a problem whose entry is 0 is left exactly as it is
+  const double* reg_pp = nullptr;   // [batch] per-problem regularisation, overriding `reg`
 };
 
 // e -> (e % d, e / d) for 0 <= e < 2^22, d > 0, rd ~ 1 / d: a float product and a fix-up instead of the integer division sequence
@@ -379,6 +383,8 @@ __global__ __launch_bounds__(64, BIG ? 1 : 4) void generic_backward_kernel(Gener
   const int lane = threadIdx.x;
   const int b = blockIdx.x;
   if (b >= a.batch) return;
+  if (a.active && !a.active[b]) return;   // (the whole wave, before anything is staged or stored: K, d, P, p, delta_V, status, Q blocks stay)
+  const T reg = a.reg_pp ? (T)a.reg_pp[b] : a.reg;   // enters the factorisation's pivots only; the cost-to-go keeps Quu (tvlqr.cpp:159-164, :174)
   T* smem = BIG ? a.ws + (int64_t)b * a.ws_stride : reinterpret_cast<T*>(smem_raw);
   const int nm = a.nmax, mm = a.mmax;
   // LDS carve
@@ -495,7 +501,7 @@ __global__ __launch_bounds__(64, BIG ? 1 : 4) void generic_backward_kernel(Gener
     for (int e = lane; e < m; e += 64) sd[e] = -sQu[e];
     {
       const float rmf = __builtin_amdgcn_rcpf((float)(m > 0 ? m : 1));
-      for (int e = lane; e < m * m; e += 64) { int i, j; split_index(e, m, rmf, i, j); sL[e] = sQuu[e] + ((i == j) ? a.reg : T(0)); }
+      for (int e = lane; e < m * m; e += 64) { int i, j; split_index(e, m, rmf, i, j); sL[e] = sQuu[e] + ((i == j) ? reg : T(0)); }
     }
     __syncthreads();
     // Quu + reg I = L L^T (fail when a pivot is <= 0: Eigen's llt_inplace) and solveInPlace, one right-hand side per lane

@@ -86,7 +86,8 @@ typedef enum altro_hip_error {
  * other n <= 12, m <= 4 -> MFMA16 (padded); fp64 problems with uniform dimensions, n <= 31, m <= 8, n + m <= 32 past that tile ->
  * MFMA32 (the same arrays and iLQR loop as GENERIC, the sweeps on 2 x 2 matrix-core tiles: 3-6 x faster than GENERIC); anything else
  * (<= 256) -> GENERIC (the TVLQR sweep for any size; the iLQR loop for n, m <= 64 with dynamics given as data, a quadratic cost and
- * linear constraint blocks in every cone, kernels/ilqr_generic.hip: correctness first; no device models, no regularisation retry).
+ * linear constraint blocks in every cone, kernels/ilqr_generic.hip: correctness first; the regularisation schedule of
+ * altro_hip_solve_options as on the other plans).
  * What AUTO does NOT promise is the CPU path's bits: plans LANE and GENERIC repeat it operation for operation (bit-identical K, d, P,
  * p), the matrix-core plans MFMA16 / MFMA32 agree with it to rounding (K, d within 1e-8 absolute, measured 1e-13).  A caller that
  * needs the bits names ALTRO_HIP_PLAN_LANE / ALTRO_HIP_PLAN_GENERIC; one that passes a flag only plan LANE honours
@@ -225,8 +226,9 @@ int altro_hip_get_qblocks(altro_hip_batch* h, double* qblocks);
 
 /* ---- the iLQR loop around the sweep ------------------------------------------------------------------
  * Plan GENERIC (n or m beyond the tile, up to 64): dynamics are DATA, tracking or dense quadratic cost, MPC operations; one wave per
- * problem (kernels/ilqr_generic.hip), linear constraint blocks in every cone (round 4).  Device models and the regularisation retry:
- * plans LANE / MFMA16.
+ * problem (kernels/ilqr_generic.hip), linear constraint blocks in every cone (round 4).  The regularisation schedule
+ * (reg_initial, reg_retry_max) works on this plan and on plan MFMA32 as on LANE / MFMA16: the sweep of every handle kind (uniform or per-knot-point dimensions, fp64 or fp32, dense or
+ * diagonal cost, device models) takes the per-problem reg and repeats only the problems whose factorisation failed.
  * Plan LANE (n <= 6: BASELINE.json configs[2], [3]): nonlinear dynamics from a compiled-in device model
  * (altro_hip_set_model), constraint blocks, MPC operations.
  * Plan MFMA16 ((n, m) = (12, 4): configs[1], [4]): dynamics are DATA -- the A, B, f given to
@@ -377,7 +379,8 @@ typedef struct altro_hip_solve_options { /* AltroOptions, solver_options.hpp:16-
    * reg = 0 and ignores a failed Cholesky (tvlqr.cpp:159-164, solver.cpp:363, :449).  With reg_retry_max > 0
    * a problem whose backward pass fails repeats it with reg <- max(reg * reg_scale, reg_min) (at most
    * reg_retry_max times per sweep, never above reg_max) and relaxes reg by reg_scale after a success.
-   * Defaults (0, 0) reproduce the reference.                                                              */
+   * reg_initial > 0 alone starts every problem's backward passes at that reg.  Every plan honours both
+   * (LANE, MFMA16, MFMA32, GENERIC).  Defaults (0, 0) reproduce the reference.                            */
   double reg_initial;
   int reg_retry_max;
   double reg_scale, reg_min, reg_max;
