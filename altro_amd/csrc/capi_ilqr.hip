@@ -64,7 +64,7 @@ int al_upload(altro_hip_batch* h) {
 }
 
 // The kernels' view of the handle's constraint tables, on every plan: what a plan does not have is null / zero on the handle (al_upload_tables:
-// Gpad is plan MFMA16's; big, gsel and guser are plan GENERIC's), and max_ncon is read by plan MFMA16's launcher alone.
+// Gpad is plan MFMA16's; big, gsel and guser are plan GENERIC's), and max_ncon is plan MFMA16's (the route reads the summary's: loop_route.h).
 template <typename T>
 AlTable<T> al_table(const altro_hip_batch* h) {
   AlTable<T> t;
@@ -132,13 +132,60 @@ void merit_split_prepare(altro_hip_batch* h) {
   }
 }
 
+// what the route of a loop operation may depend on (loop_route.h)
+RouteShape route_shape(const altro_hip_batch* h) {
+  return RouteShape{h->plan, h->dtype == ALTRO_HIP_F64, h->ragged, h->n, h->m, h->N, h->batch, h->model_set ? h->model.kind : (int)MODEL_LINEAR, h->cost_dense,
+                    h->merit_split == 1, h->forms, !h->al_defs.empty(), h->al_sum, h->rtc_row32_ok};
+}
+// the library's launcher unit of a step (0 launched, 1 = the unit does not carry the id, 2 = launch error)
+template <typename S>
+static int launch_step(altro_hip_batch* h, const RouteStep& st, const IlqrWaveArgs<S>& a) {
+  const int unit = route_unit(st.id);
+  return unit == RU_MFMA16_WIDE ? ilqr_wave_launch_wide<S>(h->stream, st, a) : unit == RU_MFMA16_MODEL ? ilqr_wave_launch_model<S>(h->stream, st, a)
+                                : ilqr_wave_launch_kernel<S>(h->stream, st, a);
+}
 template <typename T>
-int ilqr_launch(altro_hip_batch* h, int which, IlqrArgs<T> a) {
-  if (h->model.kind == MODEL_USER) return rtc_launch<T>(h, which, a);   // the caller's own dynamics, compiled at run time (capi_rtc.hip)
-  const int rc = ilqr_launch_kernel<T>(h->stream, which, h->model.kind, h->n, h->m, a);
-  if (rc == 1) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "no device model for (kind, n, m) = (%d, %d, %d)", h->model.kind, h->n, h->m);
-  if (rc) return fail(ALTRO_HIP_ERR_HIP, "iLQR kernel launch failed");
+static int launch_step(altro_hip_batch* h, const RouteStep& st, const IlqrGenArgs<T>& a) {
+  if constexpr (sizeof(T) == 8) {   // the row layout: fp64
+    const int unit = route_unit(st.id);
+    static Row32Launch* const row32_units[8] = {row32_merit_unit0, row32_merit_unit1, row32_merit_unit2, row32_merit_unit3,
+                                                 row32_merit_unit4, row32_merit_unit5, row32_merit_unit6, row32_merit_unit7};
+    if (unit != RU_GENERIC) return unit == RU_ROW32 ? row32_units[a.n & 7](h->stream, st, a) : row32_model_launch(h->stream, st, a);
+  }
+  return ilqr_generic_launch<T>(h->stream, st, a);
+}
+template <typename T>
+static int launch_step(altro_hip_batch* h, const RouteStep& st, const IlqrArgs<T>& a) { return ilqr_launch_kernel<T>(h->stream, st, h->model.kind, h->n, h->m, a); }
+// The steps of a route in order: each one's mode and model kind into the arguments, then its launch -- from the library, or (the caller's
+// own model, compiled at run time: capi_rtc.hip) from the handle's module
+template <typename A>
+static int route_execute(altro_hip_batch* h, const RouteShape& shape, const Route& route, A a) {
+  bool module_current = false;
+  for (int i = 0; i < route.count; ++i) {
+    const RouteStep& st = route.step[i];
+    a.mode = st.mode; a.mp.kind = st.kind;
+    if (st.rtc) {
+      if (!module_current) {   // (once per operation: the module for the shape's cost kind / tables)
+        if (const int rc = rtc_current(h, shape)) return rc;
+        module_current = true;
+      }
+      if (const int rc = rtc_step(h, st, &a)) return rc;
+      continue;
+    }
+    const int rc = launch_step(h, st, a);
+    if (rc == 1) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "internal error: kernel %#x is not in its launcher unit", st.id);
+    if (rc) return fail(ALTRO_HIP_ERR_HIP, "iLQR kernel launch failed");
+  }
   return 0;
+}
+template <typename T>
+int lane_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int want_deriv, double alpha_const, int mode) {
+  const IlqrArgs<T> a = ilqr_args<T>(h, use_alpha, use_active, want_deriv, alpha_const);
+  const RouteShape shape = route_shape(h);
+  const Route route = loop_route(shape, RouteCall{which, mode, a.spec_trials});
+  if (route.error == ROUTE_NO_MODEL) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "no device model for (kind, n, m) = (%d, %d, %d)", h->model.kind, h->n, h->m);
+  if (route.error) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "operation %d is not available on plan LANE", which);
+  return route_execute(h, shape, route, a);
 }
 template <typename S>
 int wave_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int want_deriv, double alpha_const, int mode) {
@@ -151,16 +198,8 @@ int wave_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int
     return fail(ALTRO_HIP_ERR_UNSUPPORTED, "constraint blocks from source on plan MFMA16 run in the row-layout kernels only: the LDS comparison forms "
                                            "(ALTRO_HIP_FORM_MERIT_LDS, _ALROWS_LDS, _EXPAND_LDS) do not evaluate them");
   a.penalty_scaling = h->expand_penalty_scaling; a.penalty_max = h->expand_penalty_max;
-  if (which == IK_STATIONARITY || which == IK_DUAL)   // constraint rows in the DPP form unless ALTRO_HIP_FORM_ALROWS_LDS
-    a.mode = form(h, ALTRO_HIP_FORM_ALROWS_LDS) ? 0 : STAT_NO_FEAS;
-  if (which == IK_EXPAND && form(h, ALTRO_HIP_FORM_EXPAND_LDS) && !h->cost_dense) a.mode |= EXPAND_LDS;   // (the dense cost lives in the row-layout kernels only)
   a.costd = (const S*)h->m_costd; a.costd_term = (const S*)h->m_costd_term; a.cost_dense = h->cost_dense ? 1 : 0;
-  if (h->model_set) {   // a device model: the dynamics expansion rides with every gradient expansion of a stored trajectory
-    a.mp = h->model;    // (not with the end-of-sweep refresh, EXPAND_NEXT: the merit pass that made the candidate left Z already)
-    if (which == IK_EXPAND && (a.mode & EXPAND_GRADIENT) && !(a.mode & EXPAND_NEXT)) a.mode |= EXPAND_DYN;
-  }
-  if (which == IK_MERIT)   // a line-search round: the DPP form of the merit evaluation unless ALTRO_HIP_FORM_MERIT_LDS keeps the LDS form
-    a.mode = form(h, ALTRO_HIP_FORM_MERIT_LDS) ? 0 : form(h, ALTRO_HIP_FORM_MERIT_DPP_ALWAYS) ? 3 : 2;   // (3: the DPP form whatever the launcher's rule)
+  if (h->model_set) a.mp = h->model;
   a.dyn = (const S*)h->m_in; a.dyn_bs = h->m_st.in_bs; a.dyn_ks = h->m_st.in_ks;
   a.cin = (S*)h->m_cin; a.cin_bs = h->m_st.cin_bs; a.cin_ks = h->m_st.cin_ks;
   a.term = (S*)h->m_term; a.out = (const S*)h->m_out; a.out_bs = h->m_st.out_bs; a.out_ks = h->m_st.out_ks;
@@ -174,38 +213,18 @@ int wave_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int
   a.spec_stride = (int64_t)h->batch * (h->N + 1) * MF_XUY;
   a.ls_beta = h->spec_beta; a.ls_max_iters = h->spec_max_iters;
   a.skip = which == IK_STATIONARITY ? h->stat_skip : nullptr;
-  if constexpr (sizeof(S) == 8) {   // affine line-search trials (capi_solve.hip switches them on for a solve): dynamics as data only
-    if (h->aff_enabled && !h->model_set) {
-      if (h->aff_store && (which == IK_MERIT2 || which == IK_MERIT)) {   // the sweep's phi(0) evaluation leaves base + sensitivity behind
-        a.sens = (double*)h->i_sens; a.sens_alpha = (double*)h->i_sens_alpha;
-      } else if (which == IK_MERIT && h->aff_round && a.mode >= 2 && !a.spec_pre) {
-        a.sens = (double*)h->i_sens; a.sens_alpha = (double*)h->i_sens_alpha;
-        a.aff = 1; a.aff_part = (double*)h->i_aff_part; a.aff_on = (int*)h->i_aff_on;   // (flags: zero when allocated, cleared again by the reduction)
-      }
-    }
+  // affine line-search trials (capi_solve.hip switches them on for a solve): fp64 records, dynamics as data only
+  const bool aff_on = sizeof(S) == 8 && h->aff_enabled && !h->model_set;
+  const bool aff_store = aff_on && h->aff_store && (which == IK_MERIT2 || which == IK_MERIT);   // the sweep's phi(0) evaluation leaves base + sensitivity behind
+  const RouteShape shape = route_shape(h);
+  const Route route = loop_route(shape, RouteCall{which, mode, a.spec_trials, aff_on && !aff_store && which == IK_MERIT && h->aff_round && !a.spec_pre});
+  if (route.error) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "operation %d is not available on plan MFMA16", which);
+  if constexpr (sizeof(S) == 8) {
+    a.aff = route.count && (route.step[0].id & KF_AFF) ? 1 : 0;
+    if (aff_store || a.aff) { a.sens = (double*)h->i_sens; a.sens_alpha = (double*)h->i_sens_alpha; }
+    if (a.aff) { a.aff_part = (double*)h->i_aff_part; a.aff_on = (int*)h->i_aff_on; }   // (flags: zero when allocated, cleared again by the reduction)
   }
-  if (h->model_set && h->model.kind == MODEL_USER) {   // the caller's own model, compiled at run time (capi_rtc.hip): fp64 handles only
-    if constexpr (sizeof(S) == 8) {
-      if (which == IK_ROLLOUT || which == IK_MERIT || which == IK_MERIT2) return rtc_tile_launch(h, which, a);
-      if (which == IK_EXPAND && (a.mode & EXPAND_DYN)) {
-        const int rcm = rtc_tile_launch(h, IK_EXPAND, a);
-        if (rcm) return rcm;
-      }
-      if (user_al && (which == IK_EXPAND || which == IK_DUAL)) return rtc_tile_al_launch(h, which, a);   // (IK_EXPAND: the cost's terms included)
-      if (user_al && which == IK_STATIONARITY) {   // the residual from the library's kernel (it reads no constraint data), then the rows' walk
-        a.mp.kind = MODEL_LINEAR;
-        a.mode |= STAT_FEAS_USER;
-        const int rcs = ilqr_wave_launch_kernel<S>(h->stream, which, a);
-        if (rcs) return fail(ALTRO_HIP_ERR_HIP, "iLQR kernel launch failed");
-        return rtc_tile_al_launch(h, which, a);
-      }
-    }
-    a.mp.kind = MODEL_LINEAR;   // (what follows are the cost kernels: none of them steps the dynamics)
-  }
-  const int rc = ilqr_wave_launch_kernel<S>(h->stream, which, a);
-  if (rc == 1) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "operation %d is not available on plan MFMA16", which);
-  if (rc) return fail(ALTRO_HIP_ERR_HIP, "iLQR kernel launch failed");
-  return 0;
+  return route_execute(h, shape, route, a);
 }
 // one problem's length of the dense arrays of plan GENERIC's iLQR loop (nominal trajectory, the cost's own blocks): the sum of the
 // knot points' blocks, whatever their dimensions
@@ -217,19 +236,6 @@ GenSizes gen_sizes(const altro_hip_batch* h) {
     z.sx += nk; z.su += mk; z.sQ += nk * nk; z.sR += mk * mk; z.sH += mk * nk;
   }
   return z;
-}
-// the loop kernels of kernels/ilqr_row32.hip serve this handle: plan MFMA32's shapes (also on a handle created as plan GENERIC), fp64,
-// uniform dimensions, dynamics as data, every constraint block in a row-wise cone with at most 32 rows
-bool row32_eligible(const altro_hip_batch* h) {
-  return h->plan == ALTRO_HIP_PLAN_GENERIC && h->dtype == ALTRO_HIP_F64 && !h->ragged && !h->model_set && tile32_supported(h->n, h->m) &&
-         !form(h, ALTRO_HIP_FORM_GENERIC_MERIT_LDS) && (h->al_defs.empty() || h->al_sum.row32_ok);
-}
-// the same with a compiled-in device model (row32_model.hip has the kernels: ilqr_generic_model_supported's models)
-bool row32_model_eligible(const altro_hip_batch* h) {
-  return h->plan == ALTRO_HIP_PLAN_GENERIC && h->dtype == ALTRO_HIP_F64 && !h->ragged && h->model_set && tile32_supported(h->n, h->m) &&
-         (ilqr_generic_model_supported(h->model.kind, h->n, h->m) || (h->model.kind == MODEL_USER && h->rtc_row32_ok)) &&
-         !form(h, ALTRO_HIP_FORM_GENERIC_MERIT_LDS) &&
-         (h->al_defs.empty() || h->al_sum.row32_ok);
 }
 // plan GENERIC: any (n_k, m_k) up to 64, dynamics as data, quadratic cost, linear constraint blocks (kernels/ilqr_generic.hip)
 template <typename T>
@@ -256,12 +262,11 @@ int gen_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int 
   const GenSizes gs = gen_sizes(h);
   a.sx = gs.sx; a.su = gs.su; a.sQ = gs.sQ; a.sR = gs.sR; a.sH = gs.sH;
   a.al = al_table<T>(h);
-  // MeritFunction in the row layout of kernels/ilqr_row32.hip: plan MFMA32's shapes (also on a handle created as plan GENERIC), fp64,
-  // dynamics as data, every constraint block in a row-wise cone with at most 32 rows
-  a.row32 = (sizeof(T) == 8 && row32_eligible(h)) ? 1 : 0;
-  a.row32m = (sizeof(T) == 8 && row32_model_eligible(h)) ? 1 : 0;
-  if ((a.row32 || a.row32m) && which == IK_STATIONARITY && N > 32) {   // the stationarity walk in chunks of 32 knot points: their maxima meet here
-    const size_t need = (size_t)((N + 31) / 32) * h->batch * 2 * sizeof(double);
+  const RouteShape shape = route_shape(h);
+  a.row32 = row32_eligible(shape) ? 1 : 0;   // (what the kernels read of the route: MeritFunction's layout)
+  a.row32m = row32_model_eligible(shape) ? 1 : 0;
+  if ((a.row32 || a.row32m) && which == IK_STATIONARITY && N > R32_STAT_CHUNK) {   // the stationarity walk in chunks of knot points: their maxima meet here
+    const size_t need = (size_t)((N + R32_STAT_CHUNK - 1) / R32_STAT_CHUNK) * h->batch * 2 * sizeof(double);
     if (h->g_stat_part_bytes < need) {
       if (h->g_stat_part) { (void)hipFree(h->g_stat_part); h->g_stat_part = nullptr; h->g_stat_part_bytes = 0; }
       if (hipMalloc((void**)&h->g_stat_part, need) == hipSuccess) h->g_stat_part_bytes = need;
@@ -269,35 +274,10 @@ int gen_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int 
     }
     a.stat_part = h->g_stat_part;
   }
-  if (h->model_set) {   // a device model: the dynamics expansion rides with every gradient expansion of a stored trajectory
-    a.mp = h->model;
-    if (which == IK_EXPAND && (a.mode & EXPAND_GRADIENT)) a.mode |= EXPAND_DYN;
-  }
-  if constexpr (sizeof(T) == 8) {
-    if (h->model_set && h->model.kind == MODEL_USER) {   // the caller's own model, compiled at run time (capi_rtc.hip)
-      // a block from the caller's source: every kernel that evaluates constraint rows comes from the run-time module (the merit kernel
-      // there carries them too)
-      const bool user_al = a.al.enabled && a.al.guser;
-      if (which == IK_ROLLOUT || which == IK_MERIT || (which == IK_MERIT2 && a.row32m)) return rtc_gen_launch(h, which, a);
-      if (user_al && (which == IK_STATIONARITY || which == IK_DUAL)) return rtc_gen_al_launch(h, which, a);
-      if (which == IK_EXPAND) {   // the cost's expansion from the library's kernel (the model kind it sees is not one it steps), then A_k, B_k
-        IlqrGenArgs<T> ac = a;    // (with user blocks the AL expansion -- cost and constraint terms, one kernel -- from the run-time module)
-        ac.mp.kind = MODEL_LINEAR;
-        if (user_al) {
-          const int rc0 = rtc_gen_al_launch(h, which, ac);
-          if (rc0) return rc0;
-        } else {
-          const int rc0 = ilqr_generic_launch<T>(h->stream, which, ac);
-          if (rc0) return fail(ALTRO_HIP_ERR_HIP, "iLQR kernel launch failed");
-        }
-        return (a.mode & EXPAND_DYN) ? rtc_gen_launch(h, which, a) : 0;
-      }
-    }
-  }
-  const int rc = ilqr_generic_launch<T>(h->stream, which, a);
-  if (rc == 1) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "operation %d is not available on plan GENERIC", which);
-  if (rc) return fail(ALTRO_HIP_ERR_HIP, "iLQR kernel launch failed");
-  return 0;
+  if (h->model_set) a.mp = h->model;
+  const Route route = loop_route(shape, RouteCall{which, mode, 1, false, a.stat_part != nullptr});
+  if (route.error) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "operation %d is not available on plan GENERIC", which);
+  return route_execute(h, shape, route, a);
 }
 int ilqr_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int want_deriv, double alpha_const, int mode) {
   int rc = al_upload(h);
@@ -314,14 +294,8 @@ int ilqr_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int
     return rc;
   }
   if (which == IK_MERIT) merit_split_prepare(h);
-  if (h->dtype == ALTRO_HIP_F64) {
-    auto a = ilqr_args<double>(h, use_alpha, use_active, want_deriv, alpha_const);
-    a.mode = mode;
-    return ilqr_launch<double>(h, which, a);
-  }
-  auto a = ilqr_args<float>(h, use_alpha, use_active, want_deriv, alpha_const);
-  a.mode = mode;
-  return ilqr_launch<float>(h, which, a);
+  return h->dtype == ALTRO_HIP_F64 ? lane_run<double>(h, which, use_alpha, use_active, want_deriv, alpha_const, mode)
+                                   : lane_run<float>(h, which, use_alpha, use_active, want_deriv, alpha_const, mode);
 }
 
 struct CostUpload { int field; const double* src; int nk_host; };

@@ -25,6 +25,7 @@
 #include "linesearch_sm.h"
 #include "al_tables.h"
 #include "loop_fields.h"
+#include "loop_route.h"
 #include "rtc_unit.h"
 
 namespace altro_hip {
@@ -102,7 +103,7 @@ struct altro_hip_batch {
   bool rtc_has_constraints = false;   // ... whose source also defines altro_user_constraint / _jacobian
   void* rtc = nullptr;            // run-time compiled model (capi_rtc.hip: RtcModule, shared through a per-process cache)
   std::string rtc_source;         // ... its source, and the cost kind (IlqrArgs::cost_kind) its cost-reading kernels were instantiated for
-  int rtc_ck = 0;                 // (plan MFMA16: constraint blocks | dense cost << 1 | more than AL_MAXC slots << 2 | a slot from the source << 3, rtc_tile_launch)
+  int rtc_ck = 0;                 // (plan MFMA16: constraint blocks | dense cost << 1 | more than AL_MAXC slots << 2 | a slot from the source << 3: loop_route.h, route_tile_module_key)
   int x0_stride = 0;              // elements between two problems' x0 on the device (12 on plan MFMA16, else n)
   int spare_count = 0;            // spare candidate trajectories i_cand_spec holds (sized to the path in use, see spec_trials_cap)
   int spare_failed = 0;           // > 0: an allocation of this many spares failed on this handle (no retry at this size or above)
@@ -556,12 +557,9 @@ constexpr int kCounterSlots = 2048;   // counter slots of one handle (altro_hip_
 constexpr int kStatsBlocks = 1024, kStatsStride = 16;   // capi_stats.hip: partials [kStatsBlocks][kStatsStride]
 
 // run-time compiled user models (capi_rtc.hip; RtcKernel and the other kinds' slots: rtc_unit.h)
-template <typename T>
-int rtc_launch(altro_hip_batch* h, int which, const IlqrArgs<T>& a);
-int rtc_tile_launch(altro_hip_batch* h, int which, const IlqrWaveArgs<double>& a);   // plan MFMA16: the model kernels of a caller's source
-int rtc_tile_al_launch(altro_hip_batch* h, int which, const IlqrWaveArgs<double>& a);   // ... and their constraint kernels (user slots)
-int rtc_gen_launch(altro_hip_batch* h, int which, const IlqrGenArgs<double>& a);     // plans GENERIC / MFMA32: likewise
-int rtc_gen_al_launch(altro_hip_batch* h, int which, const IlqrGenArgs<double>& a);  // ... and their constraint kernels (user blocks)
+int rtc_current(altro_hip_batch* h, const RouteShape& s);   // the handle's module for the shape's route, rebuilt where its key changed
+int rtc_step(altro_hip_batch* h, const RouteStep& st, const void* args);   // one step of a route from that module
+RouteShape route_shape(const altro_hip_batch* h);           // capi_ilqr.hip: what the route of a loop operation may depend on (loop_route.h)
 
 // the sweep launchers (capi_tvlqr.hip), also used by the iLQR loop
 int replan_empty_handle(altro_hip_batch* h, int plan);   // capi_core.hip
@@ -578,8 +576,6 @@ bool ensure_spares(altro_hip_batch* h, int count, size_t bytes_each);
 void merit_split_prepare(altro_hip_batch* h);
 int ilqr_gather_results(altro_hip_batch* h, altro_hip_solve_result* results);
 int launch_backward(altro_hip_batch* h, double reg);
-bool row32_eligible(const altro_hip_batch* h);             // capi_ilqr.hip: kernels/ilqr_row32.hip serves the handle
-bool row32_model_eligible(const altro_hip_batch* h);
 bool tile32_supported(int n, int m);                        // capi_tile32.hip: plan MFMA32
 int tile32_launch_backward(altro_hip_batch* h, double reg);
 int tile32_launch_forward(altro_hip_batch* h);

@@ -117,13 +117,12 @@ struct RtcModule {
   hipModule_t module = nullptr;
   hipFunction_t fn[RTC_MAX_SLOTS] = {};   // by the unit's slots (rtc_unit.h: RtcKernel / RtcTileKernel / RtcGenKernel)
   bool row_ok = false;   // generic: the row-layout kernels exist and none of them spills (see RtcGenKernel)
-  bool al = false;       // generic: the source's constraint blocks: RTG_STATIONARITY .. RTG_DUAL exist
 };
 constexpr int RTG_ROW_SCRATCH_MAX = 256;   // bytes of private segment per lane a row-layout kernel may use and still be chosen
 
-// generic: which of the optional kernels the module has, and whether the row-layout ones are to be chosen: when none of them spills
+// generic: whether the row-layout kernels are to be chosen: when the module has them and none of them spills
 static void rtc_gen_probe(const RtcUnit& unit, RtcModule* m) {
-  m->al = !unit.exprs[RTG_STATIONARITY].empty(); m->row_ok = !unit.exprs[RTG_ROW_MERIT].empty();
+  m->row_ok = !unit.exprs[RTG_ROW_MERIT].empty();
   for (int w = RTG_ROW_MERIT; w < RTG_NUM_ROW && m->row_ok; ++w) {
     int scratch = 0;
     if (hipFuncGetAttribute(&scratch, HIP_FUNC_ATTRIBUTE_LOCAL_SIZE_BYTES, m->fn[w]) != hipSuccess) { (void)hipGetLastError(); scratch = 1 << 30; }
@@ -189,148 +188,33 @@ static int rtc_build(altro_hip_batch* h, const RtcUnit& unit, const std::string&
 static int rtc_lane_module(altro_hip_batch* h, const std::string& source, int ck, RtcModule** out) {
   return rtc_build(h, rtc_unit_lane(h->n, h->m, h->dtype == ALTRO_HIP_F64 ? "double" : "float", ck, source), source, out);
 }
-// (ck: constraint blocks | dense cost << 1 | more than AL_MAXC slots at some knot point << 2 | a slot from the source << 3 --
-//  altro_hip_batch::rtc_ck)
+// (ck: altro_hip_batch::rtc_ck, the bits of loop_route.h: route_tile_module_key)
 static int rtc_tile_module(altro_hip_batch* h, int ck, RtcModule** out) {
   return rtc_build(h, rtc_unit_tile(h->n, h->m, ck & 1, (ck >> 1) & 1, h->rtc_source, (ck >> 2) & 1, (ck >> 3) & 1), h->rtc_source, out);
 }
-// One launch from a run-time module.  `a`: the kernel's one parameter (only read); fmt, p...: the message of a failed launch, the error's text last.
-template <typename A, typename... P>
-static int rtc_go(altro_hip_batch* h, hipFunction_t f, unsigned gx, unsigned gy, unsigned bx, unsigned lds, const A& a, const char* fmt, P... p) {
-  void* params[] = {const_cast<A*>(&a)};
-  const hipError_t e = hipModuleLaunchKernel(f, gx, gy, 1, bx, 1, 1, lds, h->stream, params, nullptr);
-  return e == hipSuccess ? 0 : fail(ALTRO_HIP_ERR_HIP, fmt, p..., hipGetErrorString(e));
-}
-
-// A model kernel of plan GENERIC's loop from the handle's run-time module: the grids of ilqr_launch_generic.hip.  (IK_EXPAND: the
-// dynamics expansion only -- the caller has launched the cost's.)
-int rtc_gen_launch(altro_hip_batch* h, int which, const IlqrGenArgs<double>& a) {
-  if (h->rtc_source.empty() || !h->rtc) return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_set_model_source has not been called");
-  const RtcModule* mod = (const RtcModule*)h->rtc;
-  auto go = [&](int w, unsigned gx, unsigned lds) {
-    return rtc_go(h, mod->fn[w], gx, 1, 64, lds, a, "launch of the run-time compiled kernel %d of plan GENERIC's loop failed: %s", w);
-  };
-  const bool row = a.row32m && mod->row_ok;   // (the host set row32m knowing row_ok: row32_model_eligible)
-  switch (which) {
-    case IK_ROLLOUT: return go(RTG_ROLLOUT, (unsigned)((a.batch + 63) / 64), 0);
-    case IK_EXPAND:
-      if (row) return go(RTG_ROW_EXPAND_DYN, (unsigned)(((int64_t)a.batch * a.N + 1) / 2), 0);
-      return go(RTG_EXPAND_DYN, (unsigned)(((int64_t)a.batch * a.N + 63) / 64), 0);
-    case IK_MERIT2:
-      if (row) return go(RTG_ROW_MERIT2, (unsigned)a.batch, 0);
-      return fail(ALTRO_HIP_ERR_UNSUPPORTED, "the two-trial pass has no run-time compiled kernel for this model");
-    case IK_MERIT:
-      if (row) return go(RTG_ROW_MERIT, (unsigned)((a.batch + 1) / 2), 0);
-      return go(RTG_MERIT, (unsigned)a.batch, a.al.enabled ? (unsigned)(GEN_AL_JV * sizeof(double)) : 0u);
-    default: return fail(ALTRO_HIP_ERR_UNSUPPORTED, "operation %d has no run-time compiled kernel on this plan", which);
-  }
-}
-// The kernels of plan GENERIC's loop that evaluate constraint blocks, from the handle's run-time module: a handle with a block from the
-// source (altro_hip_add_user_constraint).  IK_EXPAND is the whole AL expansion (the cost's terms included); the caller adds the dynamics'.
-int rtc_gen_al_launch(altro_hip_batch* h, int which, const IlqrGenArgs<double>& a) {
-  if (h->rtc_source.empty() || !h->rtc) return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_set_model_source has not been called");
-  const RtcModule* mod = (const RtcModule*)h->rtc;
-  if (!mod->al) return fail(ALTRO_HIP_ERR_NOT_SET, "the model source defines no constraint blocks (altro_user_constraint / _jacobian)");
-  auto go = [&](int w, unsigned gx) {   // (the grids of ilqr_launch_generic.hip; no dynamic LDS)
-    return rtc_go(h, mod->fn[w], gx, 1, 64, 0, a, "launch of the run-time compiled constraint kernel %d of plan GENERIC's loop failed: %s", w);
-  };
-  const unsigned waves_k = (unsigned)((int64_t)a.batch * (a.N + 1));   // one wave per (problem, knot point)
-  switch (which) {
-    case IK_STATIONARITY: return go(RTG_STATIONARITY, (unsigned)a.batch);
-    case IK_EXPAND: return go(RTG_EXPAND_AL, waves_k);
-    case IK_DUAL: return go(RTG_DUAL, waves_k);
-    default: return fail(ALTRO_HIP_ERR_UNSUPPORTED, "operation %d has no run-time compiled constraint kernel on this plan", which);
-  }
-}
-
-// A model kernel of plan MFMA16's loop from the handle's run-time module: the grids of ilqr_launch_mfma16_model.hip.
-// the handle's tile module for the tables `a` carries: blocks, a dense cost, a third slot or a slot from the source came or went since
-// the module was built -- the instantiations for this combination (compiled once per key and process)
-static int rtc_tile_current(altro_hip_batch* h, const IlqrWaveArgs<double>& a, const RtcModule** out) {
-  if (h->rtc_source.empty()) return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_set_model_source has not been called");
-  const int ck = (a.al.enabled ? 1 : 0) | (a.cost_dense ? 2 : 0) | ((a.al.enabled && a.al.max_ncon > AL_MAXC) ? 4 : 0) |
-                 ((a.al.enabled && h->al_sum.has_user) ? 8 : 0);
-  if (!h->rtc || h->rtc_ck != ck) {
-    RtcModule* m2 = nullptr;
-    if (const int rc = rtc_tile_module(h, ck, &m2)) return rc;
-    h->rtc = m2; h->rtc_ck = ck;
-  }
-  *out = (const RtcModule*)h->rtc;
+// The handle's module for the shape's route (once per operation, before its first step from the module).  Plan MFMA16: blocks, a dense cost, a
+// third slot or a slot from the source came or went since the module was built; plan LANE: the handle's cost changed kind -- the
+// instantiations for this combination (compiled once per key and process).  Plans GENERIC / MFMA32: one module per source.
+int rtc_current(altro_hip_batch* h, const RouteShape& s) {
+  if (h->rtc_source.empty() || (s.plan != ALTRO_HIP_PLAN_MFMA16 && !h->rtc)) return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_set_model_source has not been called");
+  if (s.plan == ALTRO_HIP_PLAN_GENERIC) return 0;
+  const int ck = s.plan == ALTRO_HIP_PLAN_LANE ? (s.cost_dense ? 1 : 0) : route_tile_module_key(s);
+  if (h->rtc && h->rtc_ck == ck) return 0;
+  RtcModule* m2 = nullptr;
+  if (const int rc = s.plan == ALTRO_HIP_PLAN_LANE ? rtc_lane_module(h, h->rtc_source, ck, &m2) : rtc_tile_module(h, ck, &m2)) return rc;
+  h->rtc = m2; h->rtc_ck = ck;
   return 0;
 }
-// The row-layout kernels that evaluate constraint rows outside the merit pass, from the handle's run-time module: a handle of plan
-// MFMA16 with a slot from the source (altro_hip_add_user_constraint).  IK_EXPAND is the whole AL expansion (the cost's terms included);
-// IK_STATIONARITY the feasibility walk alone (the caller has launched the library's residual kernel, which reads no constraint data).
-int rtc_tile_al_launch(altro_hip_batch* h, int which, const IlqrWaveArgs<double>& a) {
-  const RtcModule* mod = nullptr;
-  if (const int rc = rtc_tile_current(h, a, &mod)) return rc;
-  const int w = which == IK_EXPAND ? RTT_EXPAND_AL : which == IK_DUAL ? RTT_DUAL : which == IK_STATIONARITY ? RTT_FEAS : -1;
-  if (w < 0 || !mod->fn[w]) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "operation %d has no run-time compiled constraint kernel on plan MFMA16", which);
-  // four (problem, knot point) pairs per wave: the grids of ilqr_launch_mfma16.hip
-  return rtc_go(h, mod->fn[w], (unsigned)((int64_t)((a.batch + 3) / 4) * (a.N + 1)), 1, 64, 0, a,
-                "launch of the run-time compiled tile constraint kernel %d failed: %s", w);
+// One step of a route (loop_route.h) from the handle's run-time module; args: the kernel's one parameter (only read).  (A constraint kernel is
+// routed here only for a handle with a block from the source, and altro_hip_add_user_constraint refuses one whose source lacks the pair: the slot exists.)
+int rtc_step(altro_hip_batch* h, const RouteStep& st, const void* args) {
+  const RtcModule* mod = (const RtcModule*)h->rtc;
+  const int w = route_rtc_slot(st.id);
+  if (w < 0 || !mod->fn[w]) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "kernel %#x has no run-time compiled instantiation in the handle's module", st.id);
+  void* params[] = {const_cast<void*>(args)};
+  const hipError_t e = hipModuleLaunchKernel(mod->fn[w], st.gx, st.gy, st.gz, st.block, 1, 1, st.lds, h->stream, params, nullptr);
+  return e == hipSuccess ? 0 : fail(ALTRO_HIP_ERR_HIP, "launch of the run-time compiled kernel %d of plan %d failed: %s", w, h->plan, hipGetErrorString(e));
 }
-
-int rtc_tile_launch(altro_hip_batch* h, int which, const IlqrWaveArgs<double>& a) {
-  const RtcModule* mod = nullptr;
-  if (const int rc = rtc_tile_current(h, a, &mod)) return rc;
-  // the merit kernels' dynamic LDS (padded constraint Jacobians; with a slot from the source at least one definition's worth: such a
-  // slot's unused row read lands there when the handle has no block given as data)
-  const unsigned gsh = a.al.enabled ? (unsigned)std::max(a.al.Gpad_count, h->al_sum.has_user ? AL_GP_DEF : 0) * 8u : 0u;
-  auto go = [&](int w, unsigned gx, unsigned gy) {
-    return rtc_go(h, mod->fn[w], gx, gy, 64, (w == RTT_MERIT || w == RTT_MERIT2) ? gsh : 0u, a, "launch of the run-time compiled tile kernel %d failed: %s", w);
-  };
-  const unsigned pairs = (unsigned)mf_grid((a.batch + 1) / 2);
-  switch (which) {
-    case IK_ROLLOUT: return go(RTT_ROLLOUT, (unsigned)((a.batch + 3) / 4), 1);
-    case IK_EXPAND: return go(RTT_EXPAND_DYN, (unsigned)((int64_t)((a.batch + 3) / 4) * a.N), 1);
-    case IK_MERIT: return go(RTT_MERIT, pairs, (unsigned)(((a.spec_trials > 1 ? a.spec_trials : 1) + 1) / 2));
-    case IK_MERIT2: return go(RTT_MERIT2, pairs, 1);
-    default: return fail(ALTRO_HIP_ERR_UNSUPPORTED, "operation %d has no run-time compiled tile kernel", which);
-  }
-}
-
-// One kernel of the launch-sequenced loop from the handle's run-time module: the grids of ilqr_launch_kernel (ilqr_launch_f64.hip).
-template <typename T>
-int rtc_launch(altro_hip_batch* h, int which, const IlqrArgs<T>& a) {
-  if (!h->rtc) return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_set_model_source has not been called");
-  if (h->rtc_ck != a.cost_kind) {   // the handle's cost changed kind since the module was built: the instantiations for this one
-    RtcModule* m2 = nullptr;
-    if (const int rc = rtc_lane_module(h, h->rtc_source, a.cost_kind, &m2)) return rc;
-    h->rtc = m2; h->rtc_ck = a.cost_kind;
-  }
-  RtcModule* mod = (RtcModule*)h->rtc;
-  const unsigned lanes = (unsigned)((a.batch + 63) / 64);
-  const int64_t total = (int64_t)a.batch * (a.N + 1);
-  const unsigned flat = (unsigned)std::min<int64_t>((total + 255) / 256, 1 << 20);
-  const unsigned flat64 = (unsigned)std::min<int64_t>((total + 63) / 64, 1 << 20);
-  const unsigned trials = a.spec_trials > 1 ? a.spec_trials : 1;
-  auto go = [&](int w, unsigned gx, unsigned gy, unsigned bx) { return rtc_go(h, mod->fn[w], gx, gy, bx, 0, a, "launch of %s failed: %s", kKernelExpr[w]); };
-  switch (which) {
-    case IK_ROLLOUT: return go(RTC_ROLLOUT, lanes, 1, 64);
-    case IK_ACCEPT: return go(RTC_ACCEPT, flat, 1, 256);
-    case IK_EXPAND: return go(RTC_EXPAND, flat64, 1, 64);
-    case IK_MERIT:
-      if (a.merit_jk) {
-        int rc = go(RTC_MERIT_ROLL, lanes, trials, 64);
-        if (!rc) rc = go(RTC_MERIT_POINT, flat64, trials, 64);
-        if (!rc) rc = go(RTC_MERIT_SUM, lanes, trials, 64);
-        return rc;
-      }
-      return go(RTC_MERIT, lanes, trials, 64);
-    case IK_SPEC_SELECT: return go(RTC_SPEC_SELECT, flat, 1, 256);
-    case IK_DUAL: return go(RTC_DUAL, flat, 1, 256);
-    case IK_SHIFT: return go(RTC_SHIFT, (unsigned)std::min<int64_t>(((int64_t)a.batch * (h->n + h->m) + 255) / 256, 1 << 20), 1, 256);
-    case IK_STATIONARITY: {
-      int rc = go(RTC_ZERO_RESIDUALS, (unsigned)((a.batch + 255) / 256), 1, 256);
-      if (!rc) rc = go(RTC_STATIONARITY, flat64, 1, 64);
-      return rc;
-    }
-    default: return fail(ALTRO_HIP_ERR_UNSUPPORTED, "operation %d has no run-time compiled kernel", which);
-  }
-}
-template int rtc_launch<double>(altro_hip_batch*, int, const IlqrArgs<double>&);
-template int rtc_launch<float>(altro_hip_batch*, int, const IlqrArgs<float>&);
 
 }  // namespace capi
 }  // namespace altro_hip
@@ -363,7 +247,7 @@ int altro_hip_set_model_source(altro_hip_batch* h, const char* source, float tim
     h->rtc_source = src;
     h->model = ModelParams{MODEL_USER, timestep, 0, 2.7, 1.5};
     RtcModule* gm = nullptr;   // compile now: a source that does not build must fail HERE, with the compiler's log
-    if ((rc = rtc_build(h, rtc_unit_generic(h->n, h->m, tile32_supported(h->n, h->m), src), src, &gm))) { h->rtc_source.clear(); h->model = ModelParams{MODEL_LINEAR, 0.0f, 0, 2.7, 1.5}; return rc; }
+    if ((rc = rtc_build(h, rtc_unit_generic(h->n, h->m, tile32_shape_ok(h->n, h->m), src), src, &gm))) { h->rtc_source.clear(); h->model = ModelParams{MODEL_LINEAR, 0.0f, 0, 2.7, 1.5}; return rc; }
     h->model_set = true; h->rtc_has_constraints = c_val && c_jac;
     h->rtc = gm; h->rtc_row32_ok = gm->row_ok;
     return model_takes_dynamics(h);
@@ -404,6 +288,6 @@ int altro_hip_set_model_source(altro_hip_batch* h, const char* source, float tim
   return 0;
 }
 
-int altro_hip_model_row_layout(const altro_hip_batch* h) { return (h && row32_model_eligible(h)) ? 1 : 0; }
+int altro_hip_model_row_layout(const altro_hip_batch* h) { return (h && row32_model_eligible(route_shape(h))) ? 1 : 0; }
 
 }  // extern "C"

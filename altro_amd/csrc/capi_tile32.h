@@ -9,10 +9,7 @@
 namespace altro_hip {
 namespace capi {
 
-// the shapes plan MFMA32 takes (AUTO's rule: the (12, 4) tile of plan MFMA16 keeps n <= 12, m <= 4) ...
-constexpr bool tile32_shape_ok(int n, int m) {
-  return n >= 5 && n <= T32_MAX_N && m >= 1 && m <= T32_MAX_M && n + m <= 32 && !(n <= 12 && m <= 4);
-}
+// the shapes plan MFMA32 takes: tile32_shape_ok (loop_route.h) ...
 // ... and the shapes a backward kernel is instantiated for: those, plus n = 7 .. 12 with m <= 4 for the single-problem seam
 // (tvlqr_dropin.hip: one problem has no use for the four-problems-per-wave tile of plan MFMA16, and n <= 6, m <= 3 rides a lane)
 constexpr bool tile32_kernel_ok(int n, int m) {

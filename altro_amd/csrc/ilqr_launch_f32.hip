@@ -1,60 +1,44 @@
-// Kernel instantiations of the batched iLQR loop for element type float (see kernels/ilqr_types.h).
+// Kernel instantiations of the batched iLQR loop for element type float (see kernels/ilqr_types.h); which of them runs, and with which grid: loop_route.h.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "kernels/ilqr_lane.hip"
+#include "loop_route.h"
 
 namespace altro_hip {
 
-#define ILQR_MODELS(X)                                                                      \
-  X(MODEL_PENDULUM, 2, 1) X(MODEL_BICYCLE, 4, 2) X(MODEL_DOUBLE_INTEGRATOR, 2, 1)           \
-  X(MODEL_DOUBLE_INTEGRATOR, 4, 2) X(MODEL_DOUBLE_INTEGRATOR, 6, 3)
+using namespace capi;
 
 template <>
-int ilqr_launch_kernel<float>(hipStream_t stream, int which, int kind, int n, int m, const IlqrArgs<float>& a) {
+int ilqr_launch_kernel<float>(hipStream_t stream, const RouteStep& st, int kind, int n, int m, const IlqrArgs<float>& a) {
   using T = float;
-  const dim3 lanes((a.batch + 63) / 64), b64(64), b256(256);
-  const int64_t total = (int64_t)a.batch * (a.N + 1);
-  const dim3 flat((unsigned)std::min<int64_t>((total + 255) / 256, 1 << 20));
-  const dim3 flat64((unsigned)std::min<int64_t>((total + 63) / 64, 1 << 20));
+  const dim3 grid(st.gx, st.gy, st.gz), block(st.block);
   bool done = false;
-#define X(K_, N_, M_)                                                                                         \
-  if (!done && kind == K_ && n == N_ && m == M_) {                                                            \
-    done = true;                                                                                              \
-    const dim3 shift((unsigned)std::min<int64_t>(((int64_t)a.batch * (N_ + M_) + 255) / 256, 1 << 20));       \
-    switch (which) {                                                                                          \
-      case IK_ROLLOUT: hipLaunchKernelGGL((ilqr_rollout_kernel<K_, N_, M_, T>), lanes, b64, 0, stream, a); break;   \
-      case IK_ACCEPT: hipLaunchKernelGGL((ilqr_accept_kernel<N_, M_, T>), flat, b256, 0, stream, a); break;         \
-      case IK_EXPAND:   /* (a.cost_kind: the instantiation for the dense quadratic cost, kernels/ilqr_lane.hip) */  \
-        if (a.cost_kind) hipLaunchKernelGGL((ilqr_expand_kernel<K_, N_, M_, T, 1>), flat64, b64, 0, stream, a);       \
-        else hipLaunchKernelGGL((ilqr_expand_kernel<K_, N_, M_, T>), flat64, b64, 0, stream, a);                      \
-        break;                                                                                                \
-      case IK_MERIT: {                                                                                        \
-        const unsigned trials = a.spec_trials > 1 ? a.spec_trials : 1;                                        \
-        if (a.merit_jk) {   /* rollout | per-knot-point terms on the whole chip | sums and phi' */            \
-          hipLaunchKernelGGL((ilqr_merit_roll_kernel<K_, N_, M_, T>), dim3(lanes.x, trials), b64, 0, stream, a);   \
-          if (a.cost_kind) hipLaunchKernelGGL((ilqr_merit_point_kernel<K_, N_, M_, T, 1>), dim3(flat64.x, trials), b64, 0, stream, a); \
-          else hipLaunchKernelGGL((ilqr_merit_point_kernel<K_, N_, M_, T>), dim3(flat64.x, trials), b64, 0, stream, a); \
-          hipLaunchKernelGGL((ilqr_merit_sum_kernel<K_, N_, M_, T>), dim3(lanes.x, trials), b64, 0, stream, a);    \
-        } else if (a.cost_kind) {                                                                             \
-          hipLaunchKernelGGL((ilqr_merit_kernel<K_, N_, M_, T, 1>), dim3(lanes.x, trials), b64, 0, stream, a); \
-        } else {                                                                                              \
-          hipLaunchKernelGGL((ilqr_merit_kernel<K_, N_, M_, T>), dim3(lanes.x, trials), b64, 0, stream, a);    \
-        }                                                                                                     \
-        break;                                                                                                \
-      }                                                                                                       \
-      case IK_SPEC_SELECT: hipLaunchKernelGGL((ilqr_spec_select_kernel<N_, M_, T>), flat, b256, 0, stream, a); break; \
-      case IK_DUAL: hipLaunchKernelGGL((ilqr_dual_update_kernel<N_, M_, T>), flat, b256, 0, stream, a); break;      \
-      case IK_SHIFT: hipLaunchKernelGGL((ilqr_shift_kernel<N_, M_, T>), shift, b256, 0, stream, a); break;          \
-      default:                                                                                                \
-        hipLaunchKernelGGL(ilqr_zero_residuals_kernel<T>, dim3((a.batch + 255) / 256), b256, 0, stream, a);    \
-        hipLaunchKernelGGL((ilqr_stationarity_kernel<N_, M_, T>), flat64, b64, 0, stream, a);                   \
-        break;                                                                                                \
-    }                                                                                                         \
+#define GO(...) hipLaunchKernelGGL((__VA_ARGS__), grid, block, st.lds, stream, a); break
+#define X(K_, N_, M_)                                                                        \
+  if (!done && kind == K_ && n == N_ && m == M_) {                                           \
+    done = true;                                                                             \
+    switch (st.id) {   /* (dense: the instantiation for the dense quadratic cost, kernels/ilqr_lane.hip) */ \
+      case lane_id(RTC_ROLLOUT): GO(ilqr_rollout_kernel<K_, N_, M_, T>);                     \
+      case lane_id(RTC_ACCEPT): GO(ilqr_accept_kernel<N_, M_, T>);                           \
+      case lane_id(RTC_EXPAND, true): GO(ilqr_expand_kernel<K_, N_, M_, T, 1>);              \
+      case lane_id(RTC_EXPAND): GO(ilqr_expand_kernel<K_, N_, M_, T>);                       \
+      case lane_id(RTC_MERIT_ROLL): GO(ilqr_merit_roll_kernel<K_, N_, M_, T>);               \
+      case lane_id(RTC_MERIT_POINT, true): GO(ilqr_merit_point_kernel<K_, N_, M_, T, 1>);    \
+      case lane_id(RTC_MERIT_POINT): GO(ilqr_merit_point_kernel<K_, N_, M_, T>);             \
+      case lane_id(RTC_MERIT_SUM): GO(ilqr_merit_sum_kernel<K_, N_, M_, T>);                 \
+      case lane_id(RTC_MERIT, true): GO(ilqr_merit_kernel<K_, N_, M_, T, 1>);                \
+      case lane_id(RTC_MERIT): GO(ilqr_merit_kernel<K_, N_, M_, T>);                         \
+      case lane_id(RTC_SPEC_SELECT): GO(ilqr_spec_select_kernel<N_, M_, T>);                 \
+      case lane_id(RTC_DUAL): GO(ilqr_dual_update_kernel<N_, M_, T>);                        \
+      case lane_id(RTC_SHIFT): GO(ilqr_shift_kernel<N_, M_, T>);                             \
+      case lane_id(RTC_ZERO_RESIDUALS): GO(ilqr_zero_residuals_kernel<T>);                   \
+      case lane_id(RTC_STATIONARITY): GO(ilqr_stationarity_kernel<N_, M_, T>);               \
+      default: return 1;                                                                     \
+    }                                                                                        \
   }
-  ILQR_MODELS(X)
+  ILQR_LANE_MODELS(X)
 #undef X
+#undef GO
   if (!done) return 1;
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }

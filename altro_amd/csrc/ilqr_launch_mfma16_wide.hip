@@ -7,76 +7,59 @@
 // the two-trial pass of C1 + input box + state box 2.4-2.5 ms; a four-slot instantiation 1.04 ms)
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "kernels/ilqr_mfma16.hip"
 #include "kernels/ilqr_merit2_dpp.hip"
+#include "loop_route.h"
 
 namespace altro_hip {
 
+using namespace capi;
+
 #define WIDE_MODELS(X) X(MODEL_QUADROTOR)
 
-// 0 ok, 1 = no such kernel, 2 = launch error
 template <>
-int ilqr_wave_launch_wide<double>(hipStream_t stream, int which, const IlqrWaveArgs<double>& a) {
+int ilqr_wave_launch_wide<double>(hipStream_t stream, const RouteStep& st, const IlqrWaveArgs<double>& a) {
   using S = double;
   constexpr int W = AL_TILE_MAXC;
-  const dim3 b64(64);
-  const unsigned gsh = (unsigned)a.al.Gpad_count * 8u;   // the padded constraint Jacobians in dynamic LDS
-  const int trials = a.spec_trials > 1 ? a.spec_trials : 1;
-  const dim3 pairs(mf_grid((a.batch + 1) / 2), which == IK_MERIT ? (trials + 1) / 2 : 1);
-  if (!a.al.enabled) return 1;
-  if (which == IK_EXPAND) {   // four (problem, knot point) pairs per wave
-    const dim3 grid((unsigned)((int64_t)((a.batch + 3) / 4) * (a.N + 1)));
-    if (a.cost_dense) hipLaunchKernelGGL((wave_expand_dpp_kernel<S, true, false, W>), grid, b64, 0, stream, a);
-    else if (a.al.all_sel) hipLaunchKernelGGL((wave_expand_dpp_kernel<S, false, true, W>), grid, b64, 0, stream, a);
-    else hipLaunchKernelGGL((wave_expand_dpp_kernel<S, false, false, W>), grid, b64, 0, stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : 2;
-  }
-  if (which != IK_MERIT && which != IK_MERIT2) return 1;
-  if (a.mp.kind != MODEL_LINEAR) {
+  const dim3 grid(st.gx, st.gy, st.gz), block(st.block);
+#define GO(...) hipLaunchKernelGGL((__VA_ARGS__), grid, block, st.lds, stream, a); break
+  if (st.id & KF_MODEL) {
     bool done = false;
-#define X(K_)                                                                                                                        \
-    if (!done && a.mp.kind == K_) {                                                                                                  \
-      done = true;                                                                                                                   \
-      if (which == IK_MERIT) {                                                                                                       \
-        if (a.cost_dense) hipLaunchKernelGGL((wave_merit_dpp_kernel<S, true, false, true, K_, true, false, W>), pairs, b64, gsh, stream, a);   \
-        else hipLaunchKernelGGL((wave_merit_dpp_kernel<S, true, false, false, K_, true, false, W>), pairs, b64, gsh, stream, a);               \
-      } else {                                                                                                                       \
-        if (a.cost_dense) hipLaunchKernelGGL((wave_merit_dpp_kernel<S, true, true, true, K_, true, false, W>), pairs, b64, gsh, stream, a);    \
-        else hipLaunchKernelGGL((wave_merit_dpp_kernel<S, true, true, false, K_, true, false, W>), pairs, b64, gsh, stream, a);                \
-      }                                                                                                                              \
+#define MERIT(K_, DUAL_, DENSE_) case merit_id(true, DUAL_, DENSE_, true, false, KF_MODEL | KF_WIDE): GO(wave_merit_dpp_kernel<S, true, DUAL_, DENSE_, K_, true, false, W>)
+#define X(K_)                                                                                                           \
+    if (!done && a.mp.kind == K_) {                                                                                     \
+      done = true;                                                                                                      \
+      switch (st.id) {                                                                                                  \
+        MERIT(K_, false, true); MERIT(K_, false, false); MERIT(K_, true, true); MERIT(K_, true, false);                 \
+        default: return 1;                                                                                              \
+      }                                                                                                                 \
     }
     WIDE_MODELS(X)
 #undef X
+#undef MERIT
     if (!done) return 1;
     return hipGetLastError() == hipSuccess ? 0 : 2;
   }
   // (SOC_: the second-order cone's code only for handles that have one -- it costs the kernel ~20 registers)
-#define WIDE_MERIT(DUAL_, DENSE_, AFF_, GRID_)                                                                                              \
-  do {                                                                                                                                       \
-    if (a.al.has_soc) hipLaunchKernelGGL((wave_merit_dpp_kernel<S, true, DUAL_, DENSE_, 0, true, AFF_, W>), GRID_, b64, gsh, stream, a);     \
-    else hipLaunchKernelGGL((wave_merit_dpp_kernel<S, true, DUAL_, DENSE_, 0, false, AFF_, W>), GRID_, b64, gsh, stream, a);                 \
-  } while (0)
-  if (which == IK_MERIT && a.aff) {   // affine trials: a chunk of knot points per wave, then the chunks' shares added up
-    const int chunks = (a.N + MD_AFF_CHUNK - 1) / MD_AFF_CHUNK;
-    const dim3 grid(mf_grid((a.batch + 1) / 2), (trials + 1) / 2, chunks);
-    if (a.cost_dense) WIDE_MERIT(false, true, true, grid);
-    else WIDE_MERIT(false, false, true, grid);
-    const int64_t tot = (int64_t)ILQR_SPEC_TRIALS * a.batch;
-    hipLaunchKernelGGL(wave_aff_reduce_kernel<S>, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, stream, a, chunks);
-  } else if (which == IK_MERIT) {
-    if (a.cost_dense) WIDE_MERIT(false, true, false, pairs);
-    else WIDE_MERIT(false, false, false, pairs);
-  } else {
-    if (a.cost_dense) WIDE_MERIT(true, true, false, pairs);
-    else WIDE_MERIT(true, false, false, pairs);
+#define MERIT(DUAL_, DENSE_, AFF_)                                                                                                                   \
+  case merit_id(true, DUAL_, DENSE_, true, AFF_, KF_WIDE): GO(wave_merit_dpp_kernel<S, true, DUAL_, DENSE_, 0, true, AFF_, W>);                      \
+  case merit_id(true, DUAL_, DENSE_, false, AFF_, KF_WIDE): GO(wave_merit_dpp_kernel<S, true, DUAL_, DENSE_, 0, false, AFF_, W>)
+  switch (st.id) {
+    case K_WAVE_EXPAND_DPP | KF_WIDE | KF_DENSE: GO(wave_expand_dpp_kernel<S, true, false, W>);
+    case K_WAVE_EXPAND_DPP | KF_WIDE | KF_ALLSEL: GO(wave_expand_dpp_kernel<S, false, true, W>);
+    case K_WAVE_EXPAND_DPP | KF_WIDE: GO(wave_expand_dpp_kernel<S, false, false, W>);
+    MERIT(false, true, true); MERIT(false, false, true);
+    case K_WAVE_AFF_REDUCE | KF_WIDE: hipLaunchKernelGGL(wave_aff_reduce_kernel<S>, grid, block, 0, stream, a, st.chunks); break;
+    MERIT(false, true, false); MERIT(false, false, false);
+    MERIT(true, true, false); MERIT(true, false, false);
+    default: return 1;
   }
-#undef WIDE_MERIT
+#undef MERIT
+#undef GO
   return hipGetLastError() == hipSuccess ? 0 : 2;
 }
 // (fp32 records: the wide form is not instantiated -- altro_hip_add_linear_constraint says so when a block would need it)
 template <>
-int ilqr_wave_launch_wide<float>(hipStream_t, int, const IlqrWaveArgs<float>&) { return 1; }
+int ilqr_wave_launch_wide<float>(hipStream_t, const RouteStep&, const IlqrWaveArgs<float>&) { return 1; }
 
 }  // namespace altro_hip

@@ -137,7 +137,7 @@ __device__ __forceinline__ double gen_wave_max(double v) {
 //   jv[c * GEN_MAXP + i] = (J^T z_proj)_i     jd[c * GEN_MAXP + i] = J_ii  (the projection Jacobian of those cones is diagonal)
 // A second-order-cone block of p <= AL_MAXSOC rows is evaluated whole by lane 0 (one of more rows, up to GEN_MAXSOC, lane per row: below): Jm[c * 16 + i * 4 + r] = J_ir, Hm[c * 16 + i * 4 + r] its curvature.
 // xs / us: the point, in LDS (us ignored at the terminal knot point).  Must be called by all lanes; no barrier inside.
-constexpr int GEN_AL_JV = GEN_MAXC * GEN_MAXP, GEN_AL_SOC = GEN_MAXC * AL_MAXSOC * AL_MAXSOC;
+constexpr int GEN_AL_SOC = GEN_MAXC * AL_MAXSOC * AL_MAXSOC;   // (GEN_AL_JV: ilqr_types.h)
 template <typename T>
 __device__ __forceinline__ const AlKnotBig ALTRO_CONST_AS& gen_knot(const AlTable<T>& t, int k, int& zshift) {
   const bool u = t.uniform != 0 && k < t.N;
@@ -465,7 +465,7 @@ __device__ __forceinline__ void gen_put(T* dst, const T (&v)[CAP], const T* src,
   for (int c = 0; c < CAP; ++c) { const int e = lane + 64 * c; if (e < count) dst[e] = v[c]; }
   for (int e = 64 * CAP + lane; e < count; e += 64) dst[e] = src[e];
 }
-inline size_t generic_merit_stage_elems(int n, int m) { return (size_t)3 * n * n + (size_t)3 * n * m + (size_t)m * m; }
+// (generic_merit_stage_elems: ilqr_types.h)
 
 // MK != 0: a compiled-in device model of MN states and MM inputs (models.h) in the place of x+ = A x + B u + f: lane 0 evaluates the
 // continuous model and its Jacobian at (x, u) and at the midpoint, the state rows form their rows of A_k = I + h Am (I + h/2 A0),
@@ -906,8 +906,6 @@ __global__ void generic_shift_kernel(IlqrGenArgs<T> a) {
 #undef GOFF
 #undef GEN_UBASE
 
-template <typename T>
-int ilqr_generic_launch(hipStream_t stream, int which, const IlqrGenArgs<T>& a);   // ilqr_launch_generic.hip
 bool ilqr_generic_model_supported(int kind, int n, int m);                           // compiled-in device models of plans GENERIC / MFMA32
 
 }  // namespace altro_hip

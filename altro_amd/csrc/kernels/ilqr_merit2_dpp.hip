@@ -462,7 +462,7 @@ namespace altro_hip {
 // and leaves its share of phi / phi' in IlqrWaveArgs::aff_part; wave_aff_reduce_kernel adds the shares in chunk order.  A
 // line-search round then costs a chunk's walk (16 knot points) instead of the horizon's (256 for C1: 0.36 ms however few problems
 // search).  The trial points equal the rollout's to rounding (1e-13), not bit for bit -- like everything on this plan.
-constexpr int MD_AFF_CHUNK = 16;                    // even (the image ping-pong is the parity of k)
+// (MD_AFF_CHUNK: ilqr_types.h -- the host's route reads it too)
 // (MD_USER_BLOCKS: the row's LDS image of the slots from the caller's source and `terminal`, to alp_rows / alp_col)
 #ifdef MD_USER_BLOCKS
 #define MD_UARGS(T_) , uimg_row, T_

@@ -707,7 +707,7 @@ __global__ __launch_bounds__(64, 1) void row32_expand_dyn_kernel(IlqrGenArgs<T> 
 // ---- Stationarity and Feasibility (solver.cpp:207-231) of the candidate trajectory in the same layout: generic_stationarity_kernel's
 // values (maxima: no order to keep).  Lane j's product A_k^T y_{k+1} (B_k^T y_{k+1} in the input lanes) runs down COLUMN j of the
 // block -- in global memory a dozen cache lines per load instruction, in the image a conflict-free read at stride one.
-constexpr int R32_STAT_CHUNK = 32;
+// (R32_STAT_CHUNK: ilqr_types.h)
 template <typename T, int NX, int NU, int WPS>
 __global__ __launch_bounds__(64, WPS) void row32_stationarity_kernel(IlqrGenArgs<T> a) {
   constexpr int NN = NX * NX, NM = NX * NU, oA = 0, oB = NN, IMG = (NN + NM + 1) & ~1;
@@ -904,7 +904,7 @@ __global__ __launch_bounds__(64, WPS) void row32_rollout_init_kernel(IlqrGenArgs
   }
 }
 
-constexpr int R32_EXPAND_CHUNK = 16;
+// (R32_EXPAND_CHUNK: ilqr_types.h)
 // ---- the expansion with constraint blocks (generic_expand_al_kernel: one wave per (problem, knot point), every gradient entry a walk
 // over a row in global memory) as a walk of the row layout over a problem's knot points: EXPAND_GRADIENT -- lx, lu with the AL terms
 // (knotpoint_data.cpp:583-595), that kernel's sums ((Q x + q) + H^T u - G^T J^T z_proj) -- and EXPAND_HESSIAN in its diagonal form

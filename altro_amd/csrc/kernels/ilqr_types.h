@@ -71,8 +71,8 @@ struct IlqrArgs {
   int cost_kind = 0;
 };
 constexpr int STAT_NO_FEAS = 32;   // IK_STATIONARITY / IK_DUAL on plan MFMA16: the constraint rows in the DPP form (ilqr_merit2_dpp.hip)
-constexpr int STAT_FEAS_USER = 1024; // IK_STATIONARITY with STAT_NO_FEAS: the launcher leaves out wave_feasibility_dpp_kernel -- a slot comes from the caller's
-                                     // source, and the caller launches the run-time compiled instantiation after it (capi_rtc.hip: rtc_tile_al_launch)
+constexpr int STAT_FEAS_USER = 1024; // IK_STATIONARITY with STAT_NO_FEAS: a slot comes from the caller's source, and wave_feasibility_dpp_kernel is the
+                                     // run-time compiled instantiation instead of the library's (loop_route.h)
 enum { EXPAND_GRADIENT = 1, EXPAND_HESSIAN = 2, EXPAND_LDS = 16 /* plan MFMA16: wave_expand_kernel instead of the DPP form (A/B, tests) */,
        EXPAND_NEXT = 64 /* wave_expand_dpp_kernel at the end of a sweep: the gradient for the problems of the active mask (those whose
                            duals changed), the cost Hessians of the NEXT sweep for every problem still running (IlqrProb::running) */,
@@ -181,17 +181,18 @@ struct IlqrWaveArgs {
 constexpr int ROLLOUT_INIT = 4;   // wave_rollout_kernel also writes the nominal record and the cost gradient (the head of
                                   // Solve for an unconstrained problem: rollout + CopyTrajectory + expansion in one pass)
 
-template <typename S>
-int ilqr_wave_launch_kernel(hipStream_t stream, int which, const IlqrWaveArgs<S>& a);   // ilqr_launch_mfma16.hip
-template <typename S>
-int ilqr_wave_launch_model(hipStream_t stream, int which, const IlqrWaveArgs<S>& a);    // ilqr_launch_mfma16_model.hip (a.mp.kind)
 bool ilqr_tile_model_supported(int kind, int n, int m);                                 // device models of the (12, 4) tile plan
-// the merit passes of a handle with more than AL_MAXC constraint slots at some knot point (al_types.h: AL_TILE_MAXC; fp64 records)
-template <typename S>
-int ilqr_wave_launch_wide(hipStream_t stream, int which, const IlqrWaveArgs<S>& a);     // ilqr_launch_mfma16_wide.hip
+// (the launcher units' entry points: loop_route.h)
 
 // Speculative backtracking: most trials one merit launch evaluates (the host picks 1, 2, 4 or 8 by how idle the chip is)
 constexpr int ILQR_SPEC_TRIALS = 8;
+// plan MFMA16's affine line-search trials (kernels/ilqr_merit2_dpp.hip, AFF): knot points per wave.  Even (the image ping-pong is the parity of k)
+constexpr int MD_AFF_CHUNK = 16;
+// plans GENERIC / MFMA32: the constraint rows' LDS vector of the loop kernels (kernels/ilqr_generic.hip), the knot points per wave of the
+// row layout's stationarity and expansion walks (kernels/ilqr_row32.hip), and the elements generic_merit_kernel<T, true> stages in LDS
+constexpr int GEN_AL_JV = GEN_MAXC * GEN_MAXP;
+constexpr int R32_STAT_CHUNK = 32, R32_EXPAND_CHUNK = 16;
+inline size_t generic_merit_stage_elems(int n, int m) { return (size_t)3 * n * n + (size_t)3 * n * m + (size_t)m * m; }
 enum IlqrKernel { IK_ROLLOUT, IK_ACCEPT, IK_EXPAND, IK_MERIT, IK_STATIONARITY, IK_DUAL, IK_SHIFT, IK_SPEC_SELECT,
                   IK_MERIT2 /* plan MFMA16: phi(0) and the first step in one pass */ };
 enum IlqrLoopKernel { ILK_LOOP_INIT, ILK_LS_BEGIN, ILK_LS_FEED, ILK_FINISH_ITER, ILK_MARK_RUNNING, ILK_SET_PENALTY,
@@ -252,8 +253,6 @@ inline int ilqr_launch_fused(hipStream_t stream, int kind, int n, int m, const I
 }
 
 bool ilqr_supported(int kind, int n, int m);
-template <typename T>
-int ilqr_launch_kernel(hipStream_t stream, int which, int kind, int n, int m, const IlqrArgs<T>& a);
 int ilqr_launch_loop(hipStream_t stream, int which, const IlqrLoopArgs& a);
 int ilqr_launch_results(hipStream_t stream, const IlqrProb* prob, IlqrResult* out, int batch);
 // Straggler compaction of the one-launch solve: `count` problems on a device that holds `resident` workgroups at once -- problems

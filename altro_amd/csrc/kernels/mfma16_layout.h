@@ -43,6 +43,7 @@ static_assert(MF_COST % 8 == 0 && MF_OUT % 8 == 0, "records are whole 64-byte li
 // the [k][b] slab.  Here XCD x takes the contiguous eighth [x * chunk, (x + 1) * chunk) of the batch instead, so each
 // L2 streams one contiguous run per slab (measured on C1: backward 0.83-0.85 -> 0.80 ms, forward 0.63-0.65 -> 0.61 ms).
 // Launch mf_grid(batch) blocks; blocks past the end of a ragged eighth return at once.
+constexpr int T32_MAX_N = 31, T32_MAX_M = 8;   // plan MFMA32 (kernels/tvlqr_tile32.hip): the largest shape of its tile
 constexpr int MF_XCDS = 8;
 __host__ __device__ constexpr int mf_grid(int batch) { return MF_XCDS * ((batch + MF_XCDS - 1) / MF_XCDS); }
 __host__ __device__ constexpr int mf_problem(int block, int batch) {

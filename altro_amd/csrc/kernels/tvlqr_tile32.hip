@@ -35,7 +35,7 @@ namespace altro_hip {
 typedef double t32_f64x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int t32_v2u __attribute__((ext_vector_type(2)));
 
-constexpr int T32_MAX_N = 31, T32_MAX_M = 8;
+// (T32_MAX_N, T32_MAX_M: mfma16_layout.h)
 constexpr unsigned T32_OOB = 0x80000000u;   // a buffer offset past every window: loads return 0, stores are dropped
 constexpr int T32_SLD = 33;                 // row pitch of the [Qux Quu] exchange tile
 

@@ -5,83 +5,52 @@
 
 #include "kernels/ilqr_generic.hip"
 #include "kernels/ilqr_row32.hip"
+#include "loop_route.h"
 
 namespace altro_hip {
 
-// the shapes a kernel is instantiated for: plan MFMA32's (capi_tile32.h: tile32_shape_ok)
-constexpr bool row32_shape_ok(int n, int m) { return n >= 5 && n <= 31 && m >= 1 && m <= 8 && n + m <= 32 && !(n <= 12 && m <= 4); }
+using namespace capi;
+
 // waves per SIMD an instantiation is budgeted for: two while eight waves' images (two problems each) fit a compute unit's LDS
 constexpr int row32_wps(int n, int m) { return r32_image_doubles(n, m) <= 1150 ? 2 : 1; }
 constexpr int row32_wps_dual(int n, int m) { return r32_image_doubles(n, m) <= 2300 ? 2 : 1; }   // (the two-trial pass: one image per wave)
 
+// the kernels of one shape: instantiated for plan MFMA32's shapes (tile32_shape_ok).  0 launched, 1 = not carried, 2 = launch error
 template <int N_, int M_>
-static int row32_expand_static(hipStream_t stream, const IlqrGenArgs<double>& a) {
-  if constexpr (row32_shape_ok(N_, M_)) {
-    hipLaunchKernelGGL((row32_expand_kernel<double, N_, M_, 2>), dim3((unsigned)((a.batch + 1) / 2), (unsigned)((a.N + R32_EXPAND_CHUNK - 1) / R32_EXPAND_CHUNK)),
-                       dim3(64), 0, stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : 2;
-  } else {
-    return 1;
-  }
-}
-template <int N_, int M_>
-static int row32_dual_static(hipStream_t stream, const IlqrGenArgs<double>& a) {
-  if constexpr (row32_shape_ok(N_, M_)) {
-    hipLaunchKernelGGL((row32_merit_kernel<double, N_, M_, row32_wps_dual(N_, M_), true>), dim3((unsigned)a.batch), dim3(64), 0, stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : 2;
-  } else {
-    return 1;
-  }
-}
-template <int N_, int M_>
-static int row32_init_static(hipStream_t stream, const IlqrGenArgs<double>& a) {
-  if constexpr (row32_shape_ok(N_, M_)) {
-    hipLaunchKernelGGL((row32_rollout_init_kernel<double, N_, M_, row32_wps(N_, M_)>), dim3((unsigned)((a.batch + 1) / 2)), dim3(64), 0, stream, a);
-    return hipGetLastError() == hipSuccess ? 0 : 2;
-  } else {
-    return 1;
-  }
-}
-template <int N_, int M_>
-static int row32_stat_static(hipStream_t stream, const IlqrGenArgs<double>& a) {
-  if constexpr (row32_shape_ok(N_, M_)) {
-    const int chunks = a.stat_part ? (a.N + R32_STAT_CHUNK - 1) / R32_STAT_CHUNK : 1;
-    hipLaunchKernelGGL((row32_stationarity_kernel<double, N_, M_, 2>), dim3((unsigned)((a.batch + 1) / 2), (unsigned)chunks), dim3(64), 0, stream, a);
-    if (chunks > 1) hipLaunchKernelGGL(row32_stat_reduce_kernel<double>, dim3((unsigned)((a.batch + 255) / 256)), dim3(256), 0, stream, a, chunks);
-    return hipGetLastError() == hipSuccess ? 0 : 2;
-  } else {
-    return 1;
-  }
-}
-template <int N_, int M_>
-static int row32_merit_static(hipStream_t stream, const IlqrGenArgs<double>& a) {
-  if constexpr (row32_shape_ok(N_, M_)) {
-    hipLaunchKernelGGL((row32_merit_kernel<double, N_, M_, row32_wps(N_, M_)>), dim3((unsigned)((a.batch + 1) / 2)), dim3(64), 0, stream, a);
+static int row32_static(hipStream_t stream, const RouteStep& st, const IlqrGenArgs<double>& a) {
+  if constexpr (tile32_shape_ok(N_, M_)) {
+    const dim3 grid(st.gx, st.gy, st.gz), block(st.block);
+    switch (st.id) {
+      case K_ROW_MERIT: hipLaunchKernelGGL((row32_merit_kernel<double, N_, M_, row32_wps(N_, M_)>), grid, block, st.lds, stream, a); break;
+      case K_ROW_MERIT | KF_DUAL: hipLaunchKernelGGL((row32_merit_kernel<double, N_, M_, row32_wps_dual(N_, M_), true>), grid, block, st.lds, stream, a); break;
+      case K_ROW_INIT: hipLaunchKernelGGL((row32_rollout_init_kernel<double, N_, M_, row32_wps(N_, M_)>), grid, block, st.lds, stream, a); break;
+      case K_ROW_STAT: hipLaunchKernelGGL((row32_stationarity_kernel<double, N_, M_, 2>), grid, block, st.lds, stream, a); break;
+      case K_ROW_STAT_REDUCE: hipLaunchKernelGGL(row32_stat_reduce_kernel<double>, grid, block, st.lds, stream, a, st.chunks); break;
+      case K_ROW_EXPAND: hipLaunchKernelGGL((row32_expand_kernel<double, N_, M_, 2>), grid, block, st.lds, stream, a); break;
+      default: return 1;
+    }
     return hipGetLastError() == hipSuccess ? 0 : 2;
   } else {
     return 1;
   }
 }
 
-#define R32_ROW(N_)                                                                                   \
-  case (N_):                                                                                          \
-    switch (a.m) {                                                                                    \
-      case 1: return kind == 4 ? row32_expand_static<(N_), 1>(stream, a) : kind == 3 ? row32_dual_static<(N_), 1>(stream, a) : kind == 2 ? row32_init_static<(N_), 1>(stream, a) : kind == 1 ? row32_stat_static<(N_), 1>(stream, a) : row32_merit_static<(N_), 1>(stream, a);   \
-      case 2: return kind == 4 ? row32_expand_static<(N_), 2>(stream, a) : kind == 3 ? row32_dual_static<(N_), 2>(stream, a) : kind == 2 ? row32_init_static<(N_), 2>(stream, a) : kind == 1 ? row32_stat_static<(N_), 2>(stream, a) : row32_merit_static<(N_), 2>(stream, a);   \
-      case 3: return kind == 4 ? row32_expand_static<(N_), 3>(stream, a) : kind == 3 ? row32_dual_static<(N_), 3>(stream, a) : kind == 2 ? row32_init_static<(N_), 3>(stream, a) : kind == 1 ? row32_stat_static<(N_), 3>(stream, a) : row32_merit_static<(N_), 3>(stream, a);   \
-      case 4: return kind == 4 ? row32_expand_static<(N_), 4>(stream, a) : kind == 3 ? row32_dual_static<(N_), 4>(stream, a) : kind == 2 ? row32_init_static<(N_), 4>(stream, a) : kind == 1 ? row32_stat_static<(N_), 4>(stream, a) : row32_merit_static<(N_), 4>(stream, a);   \
-      case 5: return kind == 4 ? row32_expand_static<(N_), 5>(stream, a) : kind == 3 ? row32_dual_static<(N_), 5>(stream, a) : kind == 2 ? row32_init_static<(N_), 5>(stream, a) : kind == 1 ? row32_stat_static<(N_), 5>(stream, a) : row32_merit_static<(N_), 5>(stream, a);   \
-      case 6: return kind == 4 ? row32_expand_static<(N_), 6>(stream, a) : kind == 3 ? row32_dual_static<(N_), 6>(stream, a) : kind == 2 ? row32_init_static<(N_), 6>(stream, a) : kind == 1 ? row32_stat_static<(N_), 6>(stream, a) : row32_merit_static<(N_), 6>(stream, a);   \
-      case 7: return kind == 4 ? row32_expand_static<(N_), 7>(stream, a) : kind == 3 ? row32_dual_static<(N_), 7>(stream, a) : kind == 2 ? row32_init_static<(N_), 7>(stream, a) : kind == 1 ? row32_stat_static<(N_), 7>(stream, a) : row32_merit_static<(N_), 7>(stream, a);   \
-      case 8: return kind == 4 ? row32_expand_static<(N_), 8>(stream, a) : kind == 3 ? row32_dual_static<(N_), 8>(stream, a) : kind == 2 ? row32_init_static<(N_), 8>(stream, a) : kind == 1 ? row32_stat_static<(N_), 8>(stream, a) : row32_merit_static<(N_), 8>(stream, a);   \
-      default: break;                                                                                 \
-    }                                                                                                 \
+#define R32_ROW(N_)                                              \
+  case (N_):                                                     \
+    switch (a.m) {                                               \
+      case 1: return row32_static<(N_), 1>(stream, st, a);       \
+      case 2: return row32_static<(N_), 2>(stream, st, a);       \
+      case 3: return row32_static<(N_), 3>(stream, st, a);       \
+      case 4: return row32_static<(N_), 4>(stream, st, a);       \
+      case 5: return row32_static<(N_), 5>(stream, st, a);       \
+      case 6: return row32_static<(N_), 6>(stream, st, a);       \
+      case 7: return row32_static<(N_), 7>(stream, st, a);       \
+      case 8: return row32_static<(N_), 8>(stream, st, a);       \
+      default: break;                                            \
+    }                                                            \
     break;
 
-// kind: 0 the merit kernel, 1 stationarity / feasibility, 2 the head of an unconstrained solve (rollout + copy + first expansion),
-// 3 the two-trial merit pass (IK_MERIT2), 4 the expansion with constraint blocks (gradient, diagonal Hessian form).
-// 0 launched, 1 = no kernel for the shape (the caller runs plan GENERIC's own), 2 = launch error
-int R32_UNIT_FN(hipStream_t stream, const IlqrGenArgs<double>& a, int kind) {
+int R32_UNIT_FN(hipStream_t stream, const RouteStep& st, const IlqrGenArgs<double>& a) {
   switch (a.n) {
     R32_ROW(R32_UNIT + 0 == 0 ? 32 : R32_UNIT)   // (n = 0 does not exist; 32 has no kernel)
     R32_ROW(R32_UNIT + 8)
