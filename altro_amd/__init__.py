@@ -42,7 +42,7 @@ C_ABI_SYMBOLS = [
     "altro_hip_ilqr_solve_async", "altro_hip_ilqr_poll", "altro_hip_ilqr_wait",
     "altro_hip_linesearch_host",
     "altro_hip_add_linear_constraint", "altro_hip_add_user_constraint", "altro_hip_clear_constraints", "altro_hip_reset_duals",
-    "altro_hip_get_duals", "altro_hip_feasibility",
+    "altro_hip_get_duals", "altro_hip_set_duals", "altro_hip_get_penalty", "altro_hip_set_penalty", "altro_hip_shift_duals", "altro_hip_feasibility",
     "altro_hip_shift_trajectory", "altro_hip_update_linear_costs", "altro_hip_get_knot",
     "altro_hip_set_pointer_mode",
 ]
@@ -51,6 +51,7 @@ CONE_EQUALITY, CONE_IDENTITY, CONE_INEQUALITY, CONE_SOC = 0, 1, 2, 3   # Constra
 # altro_hip_solve_options::forms / altro_hip_set_forms (ALTRO_HIP_FORM_*): how a solve is executed.  The C library reads no environment
 # for these any more (version 300); THIS binding still translates the variables the test-suite and the tools set (forms_from_env), so
 # that one process can alternate forms between calls.
+DUAL_TAIL_KEEP, DUAL_TAIL_ZERO = 0, 1   # Batch.shift_duals: what the last knot point of a block's range becomes
 FORM_NO_SPECULATION, FORM_NO_RUNAHEAD, FORM_NO_MERIT2, FORM_MERIT_LDS, FORM_MERIT_DPP_ALWAYS = 0x1, 0x2, 0x4, 0x8, 0x10
 FORM_EXPAND_LDS, FORM_ALROWS_LDS, FORM_ROLLOUT_ROUNDS, FORM_SEQUENCED, FORM_MERIT_ONE_LAUNCH = 0x20, 0x40, 0x80, 0x100, 0x200
 FORM_LANE_QUAD_OFF, FORM_LANE_QUAD_ON, FORM_GENERIC_LATE_Q_OFF, FORM_GENERIC_LATE_Q_ON, FORM_FUSED_CLOCK = 0x400, 0x800, 0x1000, 0x2000, 0x4000
@@ -224,6 +225,10 @@ def lib():
         L.altro_hip_clear_constraints.argtypes = [vp]
         L.altro_hip_reset_duals.argtypes = [vp, d]
         L.altro_hip_get_duals.argtypes = [vp, i, i, vp]
+        L.altro_hip_set_duals.argtypes = [vp, i, i, vp]
+        L.altro_hip_get_penalty.argtypes = [vp, vp]
+        L.altro_hip_set_penalty.argtypes = [vp, vp, i]
+        L.altro_hip_shift_duals.argtypes = [vp, i]
         L.altro_hip_feasibility.argtypes = [vp, vp]
         L.altro_hip_set_pointer_mode.argtypes = [vp, i]
         L.altro_hip_shift_trajectory.argtypes = [vp]
@@ -531,6 +536,31 @@ class Batch:
         out = np.zeros((self.batch, p))
         _check(self.L.altro_hip_get_duals(self.h, int(k), int(slot), out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def set_duals(self, k, slot, z):
+        """The inverse of get_duals: z [batch][p] becomes the duals of block `slot` of knot point k, as given (no projection)."""
+        if z is not None:
+            z = np.ascontiguousarray(z, dtype=np.float64)
+            assert z.ndim == 2 and z.shape[0] == self.batch, "z is [batch][p]"
+        _check(self.L.altro_hip_set_duals(self.h, int(k), int(slot), None if z is None else z.ctypes.data_as(C.c_void_p)))
+
+    def get_penalty(self):
+        out = np.zeros(self.batch)
+        _check(self.L.altro_hip_get_penalty(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def set_penalty(self, rho):
+        """The constraints' penalty: a scalar for every problem, or [batch] values.  Duals are untouched."""
+        rho = np.asarray(rho, dtype=np.float64)
+        scalar = rho.ndim == 0
+        assert scalar or rho.shape == (self.batch,), "rho is a scalar or [batch]"
+        rho = np.ascontiguousarray(rho.reshape(-1))
+        _check(self.L.altro_hip_set_penalty(self.h, rho.ctypes.data_as(C.c_void_p), int(scalar)))
+
+    def shift_duals(self, tail=DUAL_TAIL_KEEP):
+        """The duals' side of shift_trajectory: every block definition's duals move one knot point forward; the last knot point of
+        a definition's range keeps its duals (DUAL_TAIL_KEEP) or gets zeros (DUAL_TAIL_ZERO)."""
+        _check(self.L.altro_hip_shift_duals(self.h, int(tail)))
 
     def feasibility(self):
         self._sync_forms()

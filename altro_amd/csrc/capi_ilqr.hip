@@ -30,9 +30,10 @@ static int al_copy_pool(altro_hip_batch* h, void** dst, const std::vector<double
 // (re)build the device tables of the constraint blocks (al_tables.h decides what they contain); duals restart from zero when the
 // structure changes
 static int al_upload_tables(altro_hip_batch* h) {
-  for (void** p : {(void**)&h->al_d_knots, (void**)&h->al_d_big, (void**)&h->al_d_gsel, (void**)&h->al_d_guser, &h->al_d_G, &h->al_d_Gpad, &h->al_d_g, &h->al_d_z})
+  for (void** p : {(void**)&h->al_d_knots, (void**)&h->al_d_big, (void**)&h->al_d_gsel, (void**)&h->al_d_guser, &h->al_d_G, &h->al_d_Gpad, &h->al_d_g, &h->al_d_z,
+                   (void**)&h->al_d_order, (void**)&h->al_d_start})
     if (*p) { (void)hipFree(*p); *p = nullptr; }
-  h->al_sum = AlSummary{}; h->al_rows = 0;   // (nothing on the device: what a handle without blocks has)
+  h->al_sum = AlSummary{}; h->al_rows = 0; h->al_nchains = 0;   // (nothing on the device: what a handle without blocks has)
   const AlTables t = al_build(al_input(h));
   if (t.error == AL_BUILD_SLOTS)
     return fail(ALTRO_HIP_ERR_UNSUPPORTED, "knot point %d: more constraint rows than the plan's table holds", t.err_k);
@@ -52,6 +53,11 @@ static int al_upload_tables(altro_hip_batch* h) {
   if ((rc = dmalloc(h, &h->al_d_z, zbytes))) return rc;
   // (memsets go on the handle's own stream: it is non-blocking, so a null-stream memset would race the kernels)
   HIP_TRY(hipMemsetAsync(h->al_d_z, 0, zbytes, h->stream));
+  // altro_hip_shift_duals' chains: the rows of one block definition at consecutive knot points, in walking order (al_shift.h)
+  const AlShift sh = al_shift_build(t.big, h->al_defs, t.rows);
+  if ((rc = al_copy(h, (void**)&h->al_d_order, sh.order.data(), sh.order.size() * sizeof(int)))) return rc;
+  if ((rc = al_copy(h, (void**)&h->al_d_start, sh.start.data(), sh.start.size() * sizeof(int)))) return rc;
+  h->al_nchains = (int)sh.heads.size();
   h->al_knots = t.big;
   h->al_sum = t.sum; h->al_rows = t.rows;
   return 0;
@@ -880,6 +886,74 @@ int altro_hip_get_duals(altro_hip_batch* h, int k, int slot, double* z) {
     return 0;
   };
   return h->dtype == ALTRO_HIP_F64 ? fetch(double{}) : fetch(float{});
+}
+int altro_hip_set_duals(altro_hip_batch* h, int k, int slot, const double* z) {
+  // the inverse of altro_hip_get_duals: z [batch][p] into block `slot` of knot point k, in the handle's element type, as given (no
+  // projection onto the dual cone: the reference's SetDual* declarations, altro_solver.hpp:357-362, name none)
+  int rc = loop_entry(h, true);
+  if (rc) return rc;
+  h->expansion_current = false;
+  if ((rc = al_upload(h))) return rc;
+  if (k < 0 || k > h->N || slot < 0 || slot >= h->al_knots[k].ncon || !z)
+    return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "no constraint block %d at knot point %d", slot, k);
+  const AlKnotBig& kn = h->al_knots[k];
+  const int p = h->al_defs[kn.def[slot]].p;
+  const int64_t B = h->batch;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  auto store = [&](auto t) -> int {   // z [batch][p] -> device [p][batch] of the handle's element type
+    std::vector<decltype(t)> v((size_t)p * B);
+    for (int64_t b = 0; b < B; ++b)
+      for (int r = 0; r < p; ++r) v[(size_t)r * B + b] = (decltype(t))z[(size_t)b * p + r];
+    HIP_TRY(hipMemcpy((decltype(t)*)h->al_d_z + (size_t)kn.z_off[slot] * B, v.data(), v.size() * sizeof(t), hipMemcpyHostToDevice));
+    return 0;
+  };
+  return h->dtype == ALTRO_HIP_F64 ? store(double{}) : store(float{});
+}
+int altro_hip_get_penalty(altro_hip_batch* h, double* rho) {
+  // the constraints' penalty of every problem (IlqrProb::rho; KnotPointData::rho_, one value for all blocks of a problem), [batch]
+  int rc = loop_entry(h, true);
+  if (rc) return rc;
+  if ((rc = al_upload(h))) return rc;
+  if (!rho) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "rho is required");
+  const size_t bytes = (size_t)h->batch * sizeof(double);
+  if ((rc = ensure_stage(h, bytes))) return rc;
+  if (al_get_penalty_launch(h->stream, h->i_prob, (double*)h->stage, h->batch)) return fail(ALTRO_HIP_ERR_HIP, "penalty kernel launch failed");
+  HIP_TRY(hipMemcpyAsync(rho, h->stage, bytes, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return 0;
+}
+int altro_hip_set_penalty(altro_hip_batch* h, const double* rho, int batch_stride_zero) {
+  // every problem's penalty to rho[b] (batch_stride_zero: to rho[0]), rho_est with it as altro_hip_reset_duals does; duals stay
+  int rc = loop_entry(h, true);
+  if (rc) return rc;
+  h->expansion_current = false;
+  if ((rc = al_upload(h))) return rc;
+  if (!rho) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "rho is required");
+  const int count = batch_stride_zero ? 1 : h->batch;
+  for (int b = 0; b < count; ++b)
+    if (!(rho[b] > 0.0)) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "penalty must be positive (problem %d)", b);
+  const size_t bytes = (size_t)count * sizeof(double);
+  if ((rc = ensure_stage(h, bytes))) return rc;
+  HIP_TRY(hipMemcpyAsync(h->stage, rho, bytes, hipMemcpyHostToDevice, h->stream));
+  if (al_set_penalty_launch(h->stream, h->i_prob, (const double*)h->stage, batch_stride_zero ? 0 : 1, h->batch))
+    return fail(ALTRO_HIP_ERR_HIP, "penalty kernel launch failed");
+  HIP_TRY(hipStreamSynchronize(h->stream));   // (the caller's array and the staging buffer are free again on return)
+  return 0;
+}
+int altro_hip_shift_duals(altro_hip_batch* h, int tail) {
+  // the duals' side of altro_hip_shift_trajectory: every block definition's duals move one knot point forward (kernels/al_shift.hip)
+  int rc = loop_entry(h, true);
+  if (rc) return rc;
+  if (h->ragged)   // (like the trajectory's shift: knot point k + 1 into k is meaningful between equal dimensions only)
+    return fail(ALTRO_HIP_ERR_UNSUPPORTED, "altro_hip_shift_duals needs uniform dimensions");
+  h->expansion_current = false;
+  if ((rc = al_upload(h))) return rc;
+  if (tail != ALTRO_HIP_DUAL_TAIL_KEEP && tail != ALTRO_HIP_DUAL_TAIL_ZERO)
+    return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "unknown tail %d (ALTRO_HIP_DUAL_TAIL_KEEP = 0, ALTRO_HIP_DUAL_TAIL_ZERO = 1)", tail);
+  if (h->al_defs.empty()) return 0;
+  if (al_shift_duals_launch(h->stream, h->al_d_z, h->dtype == ALTRO_HIP_F64 ? 8 : 4, h->al_d_order, h->al_d_start, h->al_nchains, h->batch, tail))
+    return fail(ALTRO_HIP_ERR_HIP, "dual shift kernel launch failed");
+  return 0;
 }
 
 // per-problem results gathered on the device into the struct's own layout: 56 bytes per problem cross PCIe, through pinned memory

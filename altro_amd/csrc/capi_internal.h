@@ -24,6 +24,7 @@
 #include "kernels/mfma16_layout.h"
 #include "linesearch_sm.h"
 #include "al_tables.h"
+#include "al_shift.h"
 #include "loop_fields.h"
 #include "loop_route.h"
 #include "rtc_unit.h"
@@ -147,6 +148,8 @@ struct altro_hip_batch {
   double* g_stat_part = nullptr; size_t g_stat_part_bytes = 0;   // row32_stationarity_kernel's per-chunk maxima (capi_ilqr.hip: gen_run)
   int* al_d_gsel = nullptr;              // plan GENERIC: AlTable::gsel (bound-type blocks)
   int* al_d_guser = nullptr;             // plan GENERIC: AlTable::guser (blocks from the caller's source), null without such a block
+  int *al_d_order = nullptr, *al_d_start = nullptr;   // altro_hip_shift_duals' chains of dual rows (al_shift.h: AlShift::order, ::start), every plan
+  int al_nchains = 0;
   double expand_penalty_scaling = 10.0, expand_penalty_max = 1e8;   // what EXPAND_DUAL's look-ahead of PenaltyUpdate needs
   const int* bwd_active = nullptr;           // per-problem mask for the backward sweep inside ilqr_solve
   const double* bwd_reg = nullptr;           // per-problem regularisation inside ilqr_solve (retry extension)
@@ -581,6 +584,13 @@ int tile32_launch_backward(altro_hip_batch* h, double reg);
 int tile32_launch_forward(altro_hip_batch* h);
 int launch_forward(altro_hip_batch* h);
 bool mfma16_forward_is_x4(const altro_hip_batch* h);   // the forward sweep runs four problems per wave (pure fp32)
+
+}  // namespace capi
+// al_shift_launch.hip (kernels/al_shift.hip): 0 ok, 2 launch failed
+int al_shift_duals_launch(hipStream_t stream, void* z, int esz, const int* order, const int* start, int nchains, int batch, int tail);
+int al_set_penalty_launch(hipStream_t stream, IlqrProb* prob, const double* rho, int stride, int batch);
+int al_get_penalty_launch(hipStream_t stream, const IlqrProb* prob, double* rho, int batch);
+namespace capi {
 
 }  // namespace capi
 }  // namespace altro_hip

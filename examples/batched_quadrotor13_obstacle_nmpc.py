@@ -5,7 +5,10 @@ path.  The thrust box is a linear constraint block; the sphere, r^2 - |p - c|^2 
 (altro_hip_add_user_constraint): hiprtc compiles it into plan GENERIC's AL kernels, and the ALTRO_HIP_PLAN_AUTO handle runs plan MFMA32
 (the sweeps on matrix-core tiles).  Every MPC step applies u_0, shifts the horizon and re-solves warm-started.
 
-    python examples/batched_quadrotor13_obstacle_nmpc.py [batch] [steps] [--no-obstacle]
+    python examples/batched_quadrotor13_obstacle_nmpc.py [batch] [steps] [--no-obstacle] [--warm-duals]
+
+--warm-duals: after the shift the duals move one knot point forward with the trajectory (shift_duals) and the penalty goes back to the
+solve's penalty_initial (set_penalty), instead of the duals being zeroed (reset_duals).
 
 Prints the ms per NMPC step (median over the warm steps) and the minimum clearance over the batch (the flown states and the last
 plans, less the sphere's radius: negative means inside).
@@ -89,6 +92,7 @@ def main():
     batch = int(argv[0]) if argv else 1024
     steps = int(argv[1]) if len(argv) > 1 else 8
     obstacle = "--no-obstacle" not in sys.argv
+    warm_duals = "--warm-duals" in sys.argv
     rng = np.random.default_rng(5)
     x0 = np.zeros((batch, n))
     x0[:, :3] = np.array([-1.5, 0.0, 0.0]) + 0.05 * rng.standard_normal((batch, 3))
@@ -119,7 +123,11 @@ def main():
         flown.append(x1[:, :3])
         bt.set_initial_state(x1)
         bt.shift_trajectory()
-        bt.reset_duals(opts["penalty_initial"])   # (the duals belong to the previous horizon's knot points)
+        if warm_duals:   # the duals follow their knot points; the penalty starts over
+            bt.shift_duals(altro_amd.DUAL_TAIL_KEEP)
+            bt.set_penalty(opts["penalty_initial"])
+        else:
+            bt.reset_duals(opts["penalty_initial"])   # (the duals belong to the previous horizon's knot points)
         bt.synchronize(); t0 = time.perf_counter()
         res = bt.ilqr_solve(**opts); bt.synchronize()
         ts.append((time.perf_counter() - t0) * 1e3)

@@ -6,7 +6,10 @@ the same source (altro_hip_add_user_constraint).  The handle is created with ALT
 the sphere takes one of the knot points' six slots and is evaluated inside the row-layout kernels.  Every MPC step applies
 u_0, shifts the horizon and re-solves warm-started.
 
-    python examples/batched_quadrotor_obstacle_nmpc.py [batch] [steps] [--plan generic] [--no-obstacle]
+    python examples/batched_quadrotor_obstacle_nmpc.py [batch] [steps] [--plan generic] [--no-obstacle] [--warm-duals]
+
+--warm-duals carries the multipliers from one step to the next: instead of zeroing them after the shift (reset_duals), the duals move one
+knot point forward with the trajectory (shift_duals) and the penalty goes back to the solve's penalty_initial (set_penalty).
 
 --plan generic runs the same problem on plan GENERIC's wave-per-problem kernels (where such a source went before the flag), so that the
 two timings can be put side by side.  Prints the ms per NMPC step (median over the warm steps) with the mean iteration counts, and the
@@ -95,6 +98,7 @@ def main():
     batch = int(argv[0]) if argv else 1024
     steps = int(argv[1]) if len(argv) > 1 else 8
     obstacle = "--no-obstacle" not in args
+    warm_duals = "--warm-duals" in args
     rng = np.random.default_rng(5)
     x0 = np.zeros((batch, n))
     x0[:, :3] = np.array([-1.5, 0.0, 0.0]) + 0.05 * rng.standard_normal((batch, 3))
@@ -128,16 +132,22 @@ def main():
         flown.append(x1[:, :3])
         bt.set_initial_state(x1)
         bt.shift_trajectory()
-        bt.reset_duals(opts["penalty_initial"])   # (the duals belong to the previous horizon's knot points)
+        if warm_duals:   # the duals follow their knot points; the penalty starts over
+            bt.shift_duals(altro_amd.DUAL_TAIL_KEEP)
+            bt.set_penalty(opts["penalty_initial"])
+        else:
+            bt.reset_duals(opts["penalty_initial"])   # (the duals belong to the previous horizon's knot points)
         bt.synchronize(); t0 = time.perf_counter()
         res = bt.ilqr_solve(**opts); bt.synchronize()
         ts.append((time.perf_counter() - t0) * 1e3)
         its.append(float(res["iterations"].mean()))
-        print("step %d: %.2f ms, mean iterations %.2f, %d converged" % (step, ts[-1], its[-1], int((res["status"] == 0).sum())))
+        print("step %d: %.2f ms, mean iterations %.2f, %d converged; %d sweeps, mean dual updates %.2f, worst feasibility %.2e"
+              % (step, ts[-1], its[-1], int((res["status"] == 0).sum()), res["sweeps"], float(res["dual_updates"].mean()), float(res["feasibility"].max())))
     x, _ = bt.get_nominal()
     cl = min(clearance(np.stack(flown, axis=1)).min(), clearance(x[:, :, :3]).min())
     ok = res["status"] == 0
     cl_ok = clearance(x[ok][:, :, :3]).min() if ok.any() else float("nan")
+    print("duals after the shift: %s" % ("shifted with the trajectory (--warm-duals)" if warm_duals else "reset to zero"))
     print("plan %s, %d vehicles: median NMPC step %.2f ms (mean iterations over the warm steps %.2f); minimum clearance over the batch %+.4f, "
           "over the last solve's converged plans %+.4f (sphere radius %.2f)" % (plan, batch, sorted(ts)[len(ts) // 2], float(np.mean(its)), cl, cl_ok, RADIUS))
     bt.close()

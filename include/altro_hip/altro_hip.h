@@ -346,6 +346,31 @@ int altro_hip_add_linear_constraint(altro_hip_batch* h, int k_first, int k_last,
 int altro_hip_clear_constraints(altro_hip_batch* h);
 int altro_hip_reset_duals(altro_hip_batch* h, double penalty);
 int altro_hip_get_duals(altro_hip_batch* h, int k, int slot, double* z /* [batch][p] */);
+/* Warm-started duals for receding-horizon MPC (the setter side the reference declares: SetDualGeneric and its siblings,
+ * altro_solver.hpp:357-362).  Every plan, both element types.
+ *   altro_hip_set_duals    the inverse of altro_hip_get_duals: same (k, slot) addressing, same error for a block that does not exist.
+ *                          Values are converted to the handle's element type and stored as given -- no projection onto the dual cone.
+ *                          A block of more than 8 rows on plan MFMA16 is still one [p] run of rows.
+ *   altro_hip_get_penalty  the constraints' penalty of every problem (one value for all blocks of a problem), [batch].
+ *   altro_hip_set_penalty  ... set per problem from rho [batch], or from rho[0] for all with batch_stride_zero != 0; the penalty the
+ *                          cached projected duals were formed with follows, as in altro_hip_reset_duals.  Duals are untouched.  A
+ *                          value that is not > 0 (a NaN included) is ALTRO_HIP_ERR_BAD_ARGUMENT and nothing is written.
+ *   altro_hip_shift_duals  the companion of altro_hip_shift_trajectory.  For every block DEFINITION (the id altro_hip_add_linear_constraint /
+ *                          _add_user_constraint returned) present at both k and k + 1, the block's duals at k become those it had at
+ *                          k + 1.  At the last knot point of a definition's range they stay (ALTRO_HIP_DUAL_TAIL_KEEP, as
+ *                          ShiftTrajectory leaves its last state duplicated) or become 0 (ALTRO_HIP_DUAL_TAIL_ZERO); a definition
+ *                          present at one knot point only, such as a terminal goal, is untouched by KEEP and zeroed by ZERO.  Blocks
+ *                          registered knot point by knot point as SEPARATE definitions do not shift: register a running constraint
+ *                          as one definition over its range.  A handle without blocks: nothing to do, returns 0.  A handle with
+ *                          per-knot-point dimensions: ALTRO_HIP_ERR_UNSUPPORTED, like altro_hip_shift_trajectory.  An unknown tail:
+ *                          ALTRO_HIP_ERR_BAD_ARGUMENT.
+ * rho and z are host arrays.  The usual MPC step: altro_hip_shift_trajectory, altro_hip_shift_duals(h, KEEP), then
+ * altro_hip_set_penalty back to the solve's penalty_initial -- the multipliers carry over, the penalty does not keep growing.          */
+enum { ALTRO_HIP_DUAL_TAIL_KEEP = 0, ALTRO_HIP_DUAL_TAIL_ZERO = 1 };
+int altro_hip_set_duals(altro_hip_batch* h, int k, int slot, const double* z /* [batch][p] */);
+int altro_hip_get_penalty(altro_hip_batch* h, double* rho /* [batch] */);
+int altro_hip_set_penalty(altro_hip_batch* h, const double* rho, int batch_stride_zero);
+int altro_hip_shift_duals(altro_hip_batch* h, int tail);
 /* SolverImpl::Feasibility (solver.cpp:224-231) of the candidate trajectory, [batch].                  */
 int altro_hip_feasibility(altro_hip_batch* h, double* out);
 

@@ -107,6 +107,14 @@ class BatchSolver {
   }
   void ClearConstraints() { Check(altro_hip_clear_constraints(h_)); }
   void ResetDuals(double penalty = 1.0) { Check(altro_hip_reset_duals(h_, penalty)); }
+  // Warm-started duals for receding-horizon MPC (altro_hip.h: altro_hip_set_duals and its siblings; the reference declares SetDual*,
+  // altro_solver.hpp:357-362): z [batch][p] of block `slot` at knot point k as given, the penalty per problem, and the duals' side of
+  // ShiftTrajectory
+  void SetDuals(int k, int slot, const double* z) { Check(altro_hip_set_duals(h_, k, slot, z)); }
+  void GetPenalty(double* rho) { Check(altro_hip_get_penalty(h_, rho)); }
+  void SetPenalty(const double* rho) { Check(altro_hip_set_penalty(h_, rho, 0)); }   // rho [batch]
+  void SetPenalty(double rho) { Check(altro_hip_set_penalty(h_, &rho, 1)); }          // one value for every problem
+  void ShiftDuals(int tail = ALTRO_HIP_DUAL_TAIL_KEEP) { Check(altro_hip_shift_duals(h_, tail)); }
 
   // ---- solve ------------------------------------------------------------------------------------------------------
   altro_hip_solve_options opts;   // AltroOptions (solver_options.hpp:16-39)
