@@ -767,6 +767,22 @@ double oracle_ilqr_get_penalty(void* h, int k, int block) {
   if (k < 0 || k > s->N || block < 0 || block >= s->cons[k].ncon) return NAN;
   return s->cons[k].con[block].rho;
 }
+/* The setter side (altro_hip_set_duals / altro_hip_set_penalty): z is stored as given, with no projection onto the dual cone;
+ * rho becomes the penalty of every block and the solver's own.  The projected duals are formed again by whatever evaluates the
+ * constraints next (CalcCost, MeritFunction), as after a dual update. */
+int oracle_ilqr_set_duals(void* h, int k, int block, const double* z) {
+  oracle_ilqr* s = (oracle_ilqr*)h;
+  if (k < 0 || k > s->N || block < 0 || block >= s->cons[k].ncon || !z) return -1;
+  oracle_con* c = &s->cons[k].con[block];
+  memcpy(c->z, z, sizeof(double) * c->p);
+  return c->p;
+}
+void oracle_ilqr_set_block_penalties(void* h, double rho) {
+  oracle_ilqr* s = (oracle_ilqr*)h;
+  for (int k = 0; k <= s->N; ++k)
+    for (int j = 0; j < s->cons[k].ncon; ++j) s->cons[k].con[j].rho = rho;
+  s->rho = rho;
+}
 
 int oracle_ilqr_iterations(void* h) { return ((oracle_ilqr*)h)->iterations; }
 int oracle_ilqr_merit_evals(void* h) { return ((oracle_ilqr*)h)->n_merit_evals; }

@@ -115,6 +115,9 @@ def lib():
         L.oracle_ilqr_get_duals.restype = C.c_int
         L.oracle_ilqr_get_penalty.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.oracle_ilqr_get_penalty.restype = C.c_double
+        L.oracle_ilqr_set_duals.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.oracle_ilqr_set_duals.restype = C.c_int
+        L.oracle_ilqr_set_block_penalties.argtypes = [C.c_void_p, C.c_double]
         L.oracle_al_knot_eval.restype = C.c_double
         L.oracle_al_knot_eval.argtypes = [C.c_int] * 4 + [C.c_void_p] * 5 + [C.c_double] + [C.c_void_p] * 7
         L.oracle_cone_projection.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
@@ -285,6 +288,19 @@ class ILQR:
         rho = self.L.oracle_ilqr_get_penalty(self.h, int(k), int(block))
         assert rho == rho, "no constraint block %d at knot point %d" % (block, k)
         return rho
+
+    def set_duals(self, k, block, z):
+        """The inverse of duals(): z [p] becomes the duals of constraint block `block` at knot point k, as given (no projection)."""
+        z = np.ascontiguousarray(z, dtype=np.float64)
+        p = self.L.oracle_ilqr_get_duals(self.h, int(k), int(block), None)
+        assert p >= 0, "no constraint block %d at knot point %d" % (block, k)
+        assert z.shape == (p,), "z is [p]"
+        assert self.L.oracle_ilqr_set_duals(self.h, int(k), int(block), _p(z)) == p
+
+    def set_block_penalty(self, rho):
+        """The penalty of every constraint block, and the solver's own, become rho."""
+        assert rho > 0.0
+        self.L.oracle_ilqr_set_block_penalties(self.h, float(rho))
 
     def solve(self, log_cap=256):
         log = np.zeros((log_cap, 8))   # alpha, phi0, phi, dphi0, stationarity, ls_iters, feasibility, rho

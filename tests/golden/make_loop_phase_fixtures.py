@@ -21,7 +21,24 @@ have chosen otherwise (flips: zero in all seven).
 
 Stored:  sum  checksum of the inputs (loop_scale_cases.inputs through golden_cases.checksum);  tab_<i>  the table of penalty RHOS[i];
 ref_<i>_<quantity>  the results in the old units, batch-shaped, in the layouts of the oracle's getters;  ecpu_<i>  blockerr of the
-oracle against them per quantity (loop_scale_cases.QUANTITIES);  flips_<i>.   Data only."""
+oracle against them per quantity (loop_scale_cases.QUANTITIES);  flips_<i>.   Data only.
+
+    python tests/golden/make_loop_phase_fixtures.py --duals [config ...]
+
+makes tests/golden/loop_phases_duals_<config>.npz instead (the seven files above stay as they are): nonzero duals and the dual update.
+mp_phases takes a STATE (loop_scale_cases: a dual vector per block, one penalty per problem, a guess): ze = z - rho c, and feasibility
+from the value's own projection onto its cone (continuous: no branch).  Two runs per problem, at 60 and 120 digits:
+  s1   the phases above at state S1 (the oracle's duals and raised penalties after a truncated solve, its steered guess), branches from
+       loop_scale_cases.state_class_tables;
+  up   the frozen solve from state S2 at penalty_initial = RHO0: the exact rollout of the input guess, z+ = Pi_K*(z - rho c) with the
+       branches of the fp64 table at S2, rho+ = min(rho scaling, penalty_max), the second sweep's expansion and K, d, P, p at z+ (not
+       rounded) and rho+, and z++ = Pi_K*(z+ - rho+ c), both with the branches of the fp64 table at the oracle's z+.
+The arrays of the two runs are identical except at exact rounding ties (ties_to_even: 11 entries of P in three configurations).
+Stored:  the inputs a GPU test needs to run without the oracle -- s1_* and s2_* (rho, x, u, z_<block>), s2_steered, the class tables
+tab_s1 [3, ..], tab_u1, tab_u2 (int8), ls_mask [2, BATCH] (the problems on which the oracle's sweep with a real line search accepts
+alpha = 1 in every unit system: cubic, backtracking);  sum  checksum of loop_scale_cases.inputs and of all of these;  ref_s1_<quantity>,
+ref_z1_<block>, ref_z2_<block> ([BATCH, knot points of the block, p]), ref_rho1, ref_rho2, ref_sw2_<K, d, P, p>;  ecpu_s1 [QUANTITIES],
+ecpu_z1 / ecpu_z2 [soc, orth, eq], ecpu_sw2 [K, d, P, p]: the oracle's blockerr against them;  flips_s1, flips_up.   Data only."""
 import os
 import sys
 
@@ -38,13 +55,20 @@ from tests.golden_cases import checksum               # noqa: E402
 N, BATCH, RHOS = crc.N, crc.BATCH, crc.RHOS
 
 
-def mp_phases(cfg, b, rho, tab, digits):
+def mp_phases(cfg, b, rho, tab, digits, state=None, update=None):
     """Problem b of `cfg` at penalty rho with the branches of `tab` ([3, blocks, BATCH, N + 1, rows]: the guess, the candidate of
-    alpha = 0, the candidate of alpha_b).  Returns ({quantity: float array in the oracle's layout}, flips)."""
+    alpha = 0, the candidate of alpha_b).  Returns ({quantity: float array in the oracle's layout}, flips).
+    state (loop_scale_cases: dict(z, rho, x, u)): the guess and the duals are the state's, ze = z - rho c (rho: the caller passes the
+    state's penalty of problem b).
+    update = (tab_1, tab_2) ([blocks, BATCH, N + 1, rows] each) instead of the phases: the frozen solve from the state's duals and input
+    guess at penalty_initial = rho.  The trajectory is the exact rollout of the state's u from x0; z+ = Pi(z - rho c) with the branches
+    of tab_1; rho+ = min(rho scaling, penalty_max); the second sweep's expansion and backward sweep at z+ (not rounded) and rho+ with the
+    branches of tab_2; z++ = Pi(z+ - rho+ c) with those branches too.  Returns ({"z1:<block>", "z2:<block>": [knot points, p], "rho1",
+    "rho2", "K", "d", "P", "p"}, flips)."""
     import mpmath as mp
     mp.mp.dps = digits
     n, m, w = cfg.n, cfg.m, cfg.w
-    F = lambda v: mp.mpf(float(v))
+    F = lambda v: v if isinstance(v, mp.mpf) else mp.mpf(float(v))
     V = lambda a: [F(v) for v in a]
     M = lambda a, r, c: [[F(a[i + r * j]) for j in range(c)] for i in range(r)]          # column-major block -> rows
     dot = mp.fdot
@@ -98,9 +122,57 @@ def mp_phases(cfg, b, rho, tab, digits):
             gu = add(add(Ru, r), Hx)
         return J, gx, gu
 
-    def al(k, x, u, cls, hess):
+    def constraint(j, k, x, u):
+        z = x + (u if k < N else [zero] * m)
+        return [dot(Gm[j][i], z) - gm[j][i] for i in range(cfg.blocks[j]["p"])]
+
+    def project(j, ze, t):
+        """ze of block j onto its dual cone with the branches t [rows]."""
+        bl = cfg.blocks[j]
+        pp = bl["p"]
+        if bl["kind"] == "eq":
+            return list(ze)
+        if bl["kind"] == "orth":
+            flips[0] += sum(int(int(t[i]) != (1 if ze[i] <= 0 else 0)) for i in range(pp))
+            return [ze[i] if int(t[i]) else zero for i in range(pp)]
+        v, s = ze[:pp - 1], ze[pp - 1]
+        a = mp.sqrt(dot(v, v))
+        region = int(t[0])
+        flips[0] += int(region != (0 if a <= -s else (1 if a <= s else 2)))
+        if region == 0:
+            return [zero] * pp
+        if region == 1:
+            return list(ze)
+        c = half * (1 + s / a)
+        return [c * e for e in v] + [c * a]
+
+    def violation(j, val):
+        """max |Pi_K(val) - val| of block j (the projection onto the cone itself is continuous: no branch to freeze)."""
+        bl = cfg.blocks[j]
+        pp = bl["p"]
+        if bl["kind"] == "eq":
+            return max(abs(c) for c in val)
+        if bl["kind"] == "orth":
+            return max([zero] + [c for c in val if c > 0])
+        vv, sv = val[:pp - 1], val[pp - 1]
+        av = mp.sqrt(dot(vv, vv))
+        if av <= sv:
+            return zero
+        if av <= -sv:
+            return max(abs(c) for c in val)
+        cv = half * (1 + sv / av)
+        return max([abs(cv * e - e) for e in vv] + [abs(cv * av - sv)])
+
+    duals = {}                                         # (block, knot point) -> the duals, zero where there are none
+    if state is not None:
+        for j, bl in enumerate(cfg.blocks):
+            for k in range(bl["k0"], bl["k1"] + 1):
+                duals[(j, k)] = V(state["z"][bl["name"]][b][k - bl["k0"]])
+
+    def al(k, x, u, cls, hess, zd=None, rho_=rho_):
         """The AL terms at (x, u) of knot point k with the branches cls [blocks, rows]: cost, gradient over [x; u], Hessian (or None),
-        violation."""
+        violation.  zd: the duals {(block, knot point): [p]} (None: the state's, or zero), rho_: the penalty."""
+        zd = duals if zd is None else zd
         z = x + (u if k < N else [zero] * m)
         J, gz, viol = zero, [zero] * w, zero
         W = [[zero] * w for _ in range(w)] if hess else None
@@ -108,7 +180,7 @@ def mp_phases(cfg, b, rho, tab, digits):
             bl, G, g, t = cfg.blocks[j], Gm[j], gm[j], cls[j]
             pp = bl["p"]
             val = [dot(G[i], z) - g[i] for i in range(pp)]
-            ze = [-(rho_ * c) for c in val]
+            ze = [zd[(j, k)][i] - rho_ * val[i] for i in range(pp)] if (j, k) in zd else [-(rho_ * c) for c in val]
             Jd = Jf = Hs = None
             if bl["kind"] == "eq":
                 zp, Jd = ze, [1] * pp
@@ -185,58 +257,87 @@ def mp_phases(cfg, b, rho, tab, digits):
             for e in range(w):
                 for f in range(e):
                     W[f][e] = W[e][f]
+        if state is not None:                          # with duals the branch of ze says nothing about the value: its own projection
+            viol = max([zero] + [violation(j, constraint(j, k, x, u if k < N else None)) for j in cfg.at(k)])
         return J, gz, W, viol
 
-    # ---- the expansion about the guess ----
-    xn = [V(cfg.x[b, k]) for k in range(N + 1)]
-    un = [V(cfg.u[b, k]) for k in range(N)] + [[zero] * m]
-    lx, lu, lxx, luu, lux = [], [], [], [], []
-    for k in range(N + 1):
-        _, gx, gu = stage(k, xn[k], un[k])
-        _, gz, W, _ = al(k, xn[k], un[k], tab[0][:, b, k], True)
-        Q, R, H = cost[k][:3]
-        lx.append(add(gx, gz[:n]))
-        lxx.append([[Q[i][j] + W[i][j] for j in range(n)] for i in range(n)])
-        if k < N:
-            lu.append(add(gu, gz[n:]))
-            luu.append([[R[i][j] + W[n + i][n + j] for j in range(m)] for i in range(m)])
-            lux.append([[H[i][j] + W[n + i][j] for j in range(n)] for i in range(m)])
-    out = dict(lx=lx, lu=lu)
+    # ---- the expansion about a trajectory and the backward sweep (f = 0) ----
+    def sweep(xn, un, cls0, zd=None, rh=rho_):
+        """lx, lu, K, d, P, p (rows) of the expansion about xn, un with the branches cls0 [blocks, BATCH, N + 1, rows], duals zd, penalty rh."""
+        lx, lu, lxx, luu, lux = [], [], [], [], []
+        for k in range(N + 1):
+            _, gx, gu = stage(k, xn[k], un[k])
+            _, gz, W, _ = al(k, xn[k], un[k], cls0[:, b, k], True, zd, rh)
+            Q, R, H = cost[k][:3]
+            lx.append(add(gx, gz[:n]))
+            lxx.append([[Q[i][j] + W[i][j] for j in range(n)] for i in range(n)])
+            if k < N:
+                lu.append(add(gu, gz[n:]))
+                luu.append([[R[i][j] + W[n + i][n + j] for j in range(m)] for i in range(m)])
+                lux.append([[H[i][j] + W[n + i][j] for j in range(n)] for i in range(m)])
+        mx = mp.matrix
+        P, pv, K, d = [None] * (N + 1), [None] * (N + 1), [None] * N, [None] * N
+        P[N], pv[N] = mx(lxx[N]), mx(lx[N])
+        for k in range(N - 1, -1, -1):
+            Ak, Bk = mx(A[k]), mx(B[k])
+            AtP, BtP = Ak.T * P[k + 1], Bk.T * P[k + 1]
+            Qxx, Quu, Qux = mx(lxx[k]) + AtP * Ak, mx(luu[k]) + BtP * Bk, mx(lux[k]) + BtP * Ak
+            Qx, Qu = mx(lx[k]) + Ak.T * pv[k + 1], mx(lu[k]) + Bk.T * pv[k + 1]
+            L = mp.matrix(m, m)
+            for j in range(m):
+                s = Quu[j, j] - mp.fsum(L[j, c] * L[j, c] for c in range(j))
+                assert s > 0, ("the exact recursion is indefinite", cfg.name, b, k, j)
+                L[j, j] = mp.sqrt(s)
+                for i in range(j + 1, m):
+                    L[i, j] = (Quu[i, j] - mp.fsum(L[i, c] * L[j, c] for c in range(j))) / L[j, j]
 
-    # ---- the backward sweep (f = 0) ----
-    mx = mp.matrix
-    P, pv, K, d = [None] * (N + 1), [None] * (N + 1), [None] * N, [None] * N
-    P[N], pv[N] = mx(lxx[N]), mx(lx[N])
-    for k in range(N - 1, -1, -1):
-        Ak, Bk = mx(A[k]), mx(B[k])
-        AtP, BtP = Ak.T * P[k + 1], Bk.T * P[k + 1]
-        Qxx, Quu, Qux = mx(lxx[k]) + AtP * Ak, mx(luu[k]) + BtP * Bk, mx(lux[k]) + BtP * Ak
-        Qx, Qu = mx(lx[k]) + Ak.T * pv[k + 1], mx(lu[k]) + Bk.T * pv[k + 1]
-        L = mp.matrix(m, m)
-        for j in range(m):
-            s = Quu[j, j] - mp.fsum(L[j, c] * L[j, c] for c in range(j))
-            assert s > 0, ("the exact recursion is indefinite", cfg.name, b, k, j)
-            L[j, j] = mp.sqrt(s)
-            for i in range(j + 1, m):
-                L[i, j] = (Quu[i, j] - mp.fsum(L[i, c] * L[j, c] for c in range(j))) / L[j, j]
+            def solve(rhs, cols):
+                X = mp.matrix(m, cols)
+                for c in range(cols):
+                    yv = [None] * m
+                    for i in range(m):
+                        yv[i] = (rhs[i, c] - mp.fsum(L[i, j] * yv[j] for j in range(i))) / L[i, i]
+                    for i in range(m - 1, -1, -1):
+                        X[i, c] = (yv[i] - mp.fsum(L[j, i] * X[j, c] for j in range(i + 1, m))) / L[i, i]
+                return X
+            K[k], d[k] = solve(Qux, n), -solve(Qu, 1)
+            QK, KtQux = Quu * K[k], K[k].T * Qux
+            P[k] = Qxx + QK.T * K[k] - KtQux - KtQux.T
+            pv[k] = Qx - QK.T * d[k] - K[k].T * Qu + Qux.T * d[k]
+        rowsof = lambda X, r, c: [[X[i, j] for j in range(c)] for i in range(r)]
+        Kr, Pr = [rowsof(K[k], m, n) for k in range(N)], [rowsof(P[k], n, n) for k in range(N + 1)]
+        dr, pr = [[d[k][i] for i in range(m)] for k in range(N)], [[pv[k][i] for i in range(n)] for k in range(N + 1)]
+        return lx, lu, Kr, dr, Pr, pr
 
-        def solve(rhs, cols):
-            X = mp.matrix(m, cols)
-            for c in range(cols):
-                yv = [None] * m
-                for i in range(m):
-                    yv[i] = (rhs[i, c] - mp.fsum(L[i, j] * yv[j] for j in range(i))) / L[i, i]
-                for i in range(m - 1, -1, -1):
-                    X[i, c] = (yv[i] - mp.fsum(L[j, i] * X[j, c] for j in range(i + 1, m))) / L[i, i]
-            return X
-        K[k], d[k] = solve(Qux, n), -solve(Qu, 1)
-        QK, KtQux = Quu * K[k], K[k].T * Qux
-        P[k] = Qxx + QK.T * K[k] - KtQux - KtQux.T
-        pv[k] = Qx - QK.T * d[k] - K[k].T * Qu + Qux.T * d[k]
-    rowsof = lambda X, r, c: [[X[i, j] for j in range(c)] for i in range(r)]
-    Kr, Pr = [rowsof(K[k], m, n) for k in range(N)], [rowsof(P[k], n, n) for k in range(N + 1)]
-    dr, pr = [[d[k][i] for i in range(m)] for k in range(N)], [[pv[k][i] for i in range(n)] for k in range(N + 1)]
-    out.update(K=Kr, d=dr, P=Pr, p=pr)
+    fl = lambda rows: np.array([[float(v) for v in r] for r in rows])
+    colmajor = lambda mats: np.array([[float(Mx[i][j]) for j in range(len(Mx[0])) for i in range(len(Mx))] for Mx in mats])
+    x0v = V(cfg.x0[b])
+    if update is not None:                             # ---- the frozen solve: z+, rho+, the second sweep, z++ ----
+        un = [V(state["u"][b, k]) for k in range(N)] + [[zero] * m]
+        xn = [x0v]
+        for k in range(N):
+            xn.append(add(add(mv(A[k], xn[k]), mv(B[k], un[k])), aff[k]))
+        res, zd, rh = {}, duals, rho_
+        for i in (1, 2):
+            zd = {(j, k): project(j, [zd[(j, k)][r] - rh * c for r, c in enumerate(constraint(j, k, xn[k], un[k]))], update[i - 1][j, b, k])
+                  for (j, k) in zd}
+            for j, bl in enumerate(cfg.blocks):
+                res["z%d:%s" % (i, bl["name"])] = fl([zd[(j, k)] for k in range(bl["k0"], bl["k1"] + 1)])
+            rh = min(rh * F(lsc.PENALTY_SCALING), F(lsc.PENALTY_MAX))
+            res["rho%d" % i] = float(rh)
+            if i == 1:
+                _, _, Kr, dr, Pr, pr = sweep(xn, un, update[1], zd, rh)
+                res.update(d=fl(dr), p=fl(pr), K=colmajor(Kr), P=colmajor(Pr))
+        return res, flips[0]
+
+    if state is None:
+        xn = [V(cfg.x[b, k]) for k in range(N + 1)]
+        un = [V(cfg.u[b, k]) for k in range(N)] + [[zero] * m]
+    else:
+        xn = [V(state["x"][b, k]) for k in range(N + 1)]
+        un = [V(state["u"][b, k]) for k in range(N)] + [[zero] * m]
+    lx, lu, Kr, dr, Pr, pr = sweep(xn, un, tab[0])
+    out = dict(lx=lx, lu=lu, K=Kr, d=dr, P=Pr, p=pr)
 
     # ---- the merit function ----
     def merit(alpha, ti):
@@ -307,7 +408,10 @@ def make(name, pool):
         e = lsc.errors(lsc.oracle_phases(cfg, rho), ref)
         arrays["ecpu_%d" % ri] = np.array([e[q] for q in lsc.QUANTITIES])
         print(name, "rho", rho, "flips", int(arrays["flips_%d" % ri]), " ".join("%s %.1e" % (q, e[q]) for q in lsc.QUANTITIES), flush=True)
-    path = lsc.fixture_path(name)
+    write(lsc.fixture_path(name), arrays)
+
+
+def write(path, arrays):
     import zipfile
     with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED) as z:       # np.savez stamps the time of day into the archive: not reproducible
         for k in sorted(arrays):
@@ -316,9 +420,56 @@ def make(name, pool):
     print("%s: %d bytes" % (os.path.relpath(path, ROOT), os.path.getsize(path)), flush=True)
 
 
+# ---- nonzero duals and the dual update: tests/golden/loop_phases_duals_<config>.npz ------------------------------------------------------
+def one_dual(args):
+    name, what, b, digits = args
+    cfg = crc.config(name)
+    d = lsc.dual_inputs(name)
+    if what == "s1":
+        return mp_phases(cfg, b, d["s1"]["rho"][b], d["tab_s1"], digits, state=d["s1"])
+    return mp_phases(cfg, b, lsc.RHO0, None, digits, state=d["s2"], update=(d["tab_u1"], d["tab_u2"]))
+
+
+def ties_to_even(a, a2, what):
+    """The arrays rounded from the 60- and the 120-digit run: identical, except where the exact value lies HALFWAY between two doubles.
+    (A cone of two rows has a piecewise linear projection: outside it rho (J G)^T (J G) couples its two variables by rho g / 2, with
+    rho = 10 a 56-bit number that is a midpoint one time in four, reached here through a division that is not exact.)  There the two
+    runs may give the two neighbours; the one with the even mantissa is taken, as a correctly rounded exact evaluation would."""
+    a, a2 = np.array(a, dtype=np.float64), np.array(a2, dtype=np.float64)
+    i = a != a2
+    if i.any():
+        assert np.array_equal(np.nextafter(a[i], a2[i]), a2[i]), ("60 and 120 digits differ by more than a tie", what)
+        a[i] = np.where(a[i].view(np.int64) & 1 == 0, a[i], a2[i])
+        print("   %s: %d entries at a rounding tie" % ("/".join(what), int(i.sum())), flush=True)
+    return a
+
+
+def make_duals(name, pool):
+    cfg = crc.config(name)
+    d = lsc.dual_inputs(name)
+    arrays = lsc.dual_input_arrays(cfg, d)
+    arrays["sum"] = checksum(dict(lsc.inputs(cfg), **arrays))
+    jobs = [(name, what, b, digits) for what in ("s1", "up") for digits in (60, 120) for b in range(BATCH)]
+    done = dict(zip(jobs, pool.map(one_dual, jobs, chunksize=1)))
+    ref = {}
+    for what in ("s1", "up"):
+        per, per2 = ([done[(name, what, b, digits)] for b in range(BATCH)] for digits in (60, 120))
+        for q in per[0][0]:
+            a, a2 = (np.stack([np.asarray(r[0][q], dtype=np.float64) for r in rs]) for rs in (per, per2))
+            ref[(what, q)] = ties_to_even(a, a2, (name, what, q))
+        arrays["flips_" + what] = np.array(sum(r[1] for r in per), dtype=np.int64)
+    arrays.update(lsc.dual_reference_arrays(cfg, ref))
+    arrays.update(lsc.dual_ecpu(cfg, d, arrays))
+    print(name, "flips", int(arrays["flips_s1"]), int(arrays["flips_up"]), " ".join("%s %s" % (k, np.array2string(v, precision=1))
+                                                                                      for k, v in arrays.items() if k.startswith("ecpu")), flush=True)
+    write(lsc.dual_fixture_path(name), arrays)
+
+
 if __name__ == "__main__":
     import multiprocessing
-    names = sys.argv[1:] or list(crc.CONFIGS)
+    args = sys.argv[1:]
+    duals = "--duals" in args
+    names = [a for a in args if a != "--duals"] or list(crc.CONFIGS)
     with multiprocessing.Pool(min(14, os.cpu_count() or 1)) as pool:
         for nm in names:
-            make(nm, pool)
+            (make_duals if duals else make)(nm, pool)

@@ -17,6 +17,22 @@ The metric: hard_cases.blockerr per (problem, knot point) block -- no floor of 1
 is its own block; a block that is exactly zero in the reference must be exactly zero.  Criterion B judges a result `got` in the
 old units by  blockerr(got, fixture) <= 10 max(e_cpu, 1e-13)  per quantity and penalty, e_cpu the oracle's STORED error against
 the extended-precision fixture (tests/golden/loop_phases_<config>.npz).
+
+Nonzero duals and the dual update (the second half of the module; tests/test_gpu_dual_scales.py, tests/golden/loop_phases_duals_<config>.npz).
+Constraint values are unit-free, so duals map as z~ = s z and penalties as rho~ = s rho; `back` takes z~ / s per block, rho~ / s and
+alpha unchanged; penalty_max -> s penalty_max and tol_meritfun_gradient -> s tol.  A STATE is what a caller writes onto a handle:
+dict(z={block name: [BATCH, knot points of the block, p]}, rho=[BATCH] the penalty the handle holds, x, u the guess).
+  S1 (dual_state)    after a truncated solve: cone_region_cases.nonzero_dual_reference's duals, its one raised penalty per problem and
+                     its steered guess, which puts every cone below, inside and outside at these duals.  The phases are judged there.
+  S2 (update_state)  before a dual update: S1's duals and penalties, S1's u as the input guess, x its rollout from x0.  A FROZEN solve
+                     (tol_meritfun_gradient huge: |phi'(0)| < tol takes alpha = 0; tol_stationarity = 4^200, whose square root is exact,
+                     forces the outer update in every unit system; tol_primal_feasibility = 0 makes the penalty update fire, a huge
+                     one leaves the penalty alone and ends with status 0) then updates z+ = Pi_K*(z - rho0 c(rollout)) and
+                     rho+ = min(10 rho0, penalty_max).  rho0 is the solve's penalty_initial: like the reference, the oracle and the
+                     device form a solve's first gradient with the penalty the handle holds and only then give EVERY problem
+                     penalty_initial, so the update's penalty is one per batch (RHO0 = 3; PENALTY_MAX / 2 to take the clamp) and the
+                     per-problem penalty of the state enters the first expansion only.  Where S1's duals do not put every region
+                     into the update's ze, the last row of every cone's duals is steered (update_state says which).
 """
 import copy
 import os
@@ -135,6 +151,9 @@ def back(res, k, D, E, scale=None):
     s = 4.0 ** k if scale is None else float(scale)
     out = {}
     for key, v in res.items():
+        if key == "z":                         # duals per block: z~ / s
+            out[key] = {name: np.asarray(a, dtype=np.float64) / s for name, a in v.items()}
+            continue
         v = np.asarray(v, dtype=np.float64)
         if key in ("lx", "p"):
             v = v * D / s
@@ -148,10 +167,10 @@ def back(res, k, D, E, scale=None):
             v = (_cm(v, n, n) * D[:, None] * D[None, :] / s).reshape(v.shape)
         elif key == "x":
             v = v / D
-        elif key in ("phi0", "dphi0", "phi", "dphi", "stat"):
+        elif key in ("phi0", "dphi0", "phi", "dphi", "stat", "rho"):
             v = v / s
         else:
-            assert key == "feas", key
+            assert key in ("feas", "alpha", "status", "iterations"), key
         out[key] = v
     return out
 
@@ -268,6 +287,375 @@ def class_table(cfg, rho, x=None, u=None):
     rows = max(bl["p"] for bl in cfg.blocks)
     t = np.full((len(cfg.blocks), BATCH, N + 1, rows), -1, dtype=np.int8)
     for (j, b, k), c in cfg.classes(rho, x, u).items():
+        if cfg.blocks[j]["kind"] == "soc":
+            t[j, b, k, 0] = ("below", "inside", "outside").index(c[0])
+        else:
+            t[j, b, k, :len(c)] = [0 if e == "neg" else 1 for e in c]
+    return t
+
+
+# ---- nonzero duals and the dual update -----------------------------------------------------------------------------------------------
+RHO0 = 3.0                      # penalty_initial of the frozen solves: 10 RHO0 stays far below PENALTY_MAX
+RHO_CLAMP = PENALTY_MAX / 2     # ... and the one at which rho+ = min(10 rho, PENALTY_MAX) takes the clamp
+PENALTY_SCALING = 10.0
+TOL_STAT = 4.0 ** 200           # sqrt is exact: the outer update fires in every unit system
+HUGE = 1e100                    # tol_meritfun_gradient of a frozen sweep (times s: finite for every s here); also "feasible at any violation"
+MARGIN_ZE = 1e-6                # every ze of S2 lies this far (of its own size) from its region's boundary
+KINDS = ("soc", "orth", "eq")
+SWEEP = ("K", "d", "P", "p")
+
+
+def block_arrays(cfg, d):
+    """{(block index, b, k): [p]} as {block name: [BATCH, knot points of the block, p]}."""
+    return {bl["name"]: np.array([[d[(j, b, k)] for k in range(bl["k0"], bl["k1"] + 1)] for b in range(BATCH)]) for j, bl in enumerate(cfg.blocks)}
+
+
+def block_dict(cfg, z):
+    return {(j, b, k): z[bl["name"]][b, k - bl["k0"]] for j, bl in enumerate(cfg.blocks) for (b, k) in cfg.slots(j)}
+
+
+def dual_state(name):
+    """S1 of configuration `name`."""
+    cfg, ref = crc.config(name), crc.nonzero_dual_reference(name)
+    rho = np.zeros(BATCH)
+    for b in range(BATCH):
+        rhos = {ref["rhos"][(j, b, k)] for k in range(N + 1) for j in cfg.at(k)}
+        assert len(rhos) == 1 and max(rhos) > 1.0, (name, b, rhos)       # one penalty per problem, raised by the oracle's penalty updates
+        rho[b] = max(rhos)
+    return dict(z=block_arrays(cfg, ref["duals"]), rho=rho, x=ref["x"], u=ref["u"])
+
+
+def restrict(cfg, st):
+    """State `st` with the duals of the blocks `cfg` (a subset of its configuration) keeps."""
+    return dict(st, z={bl["name"]: st["z"][bl["name"]] for bl in cfg.blocks})
+
+
+def state_classes(cfg, st, rho=None):
+    """cfg.classes at the state's guess and duals; rho None: the state's penalty per problem, else one for all."""
+    duals = block_dict(cfg, st["z"])
+    rhos = {key: (st["rho"][key[1]] if rho is None else rho) for key in duals}
+    return cfg.classes(x=st["x"], u=st["u"], duals=duals, rhos=rhos)
+
+
+def same_classes(was, now, cfg, s):
+    assert was.keys() == now.keys()
+    for key, w in was.items():
+        if cfg.blocks[key[0]]["kind"] == "soc":
+            assert w[:2] == now[key][:2] and w[2] * s == now[key][2], (cfg.name, key, w, now[key])
+        else:
+            assert w == now[key], (cfg.name, key, w, now[key])
+
+
+def transform_state(cfg, out, st, rho0=None):
+    """State `st` of `cfg` in the units of `out` = transform(cfg, ...): duals and penalties times s, the guess times D and E.  Every
+    (problem, knot point, block) keeps its class with ze = z - rho c formed from the mapped values (rho0: also at that one penalty)."""
+    s, (_, D, E) = out.scale, out.units
+    new = dict(z={name: _normal(a * s, "duals of " + name) for name, a in st["z"].items()}, rho=_normal(st["rho"] * s, "rho"),
+               x=_normal(st["x"] * D, "x"), u=_normal(st["u"] * E, "u"))
+    same_classes(state_classes(cfg, st), state_classes(out, new), cfg, s)
+    if rho0 is not None:
+        same_classes(state_classes(cfg, st, rho0), state_classes(out, new, rho0 * s), cfg, s)
+    return new
+
+
+def _handle(cfg, st, b):
+    """The oracle's handle of problem b with the state's duals and penalty written by the setters."""
+    h = crc.make_oracle(cfg, b)
+    for k in range(N + 1):
+        for slot, j in enumerate(cfg.at(k)):
+            bl = cfg.blocks[j]
+            h.set_duals(k, slot, st["z"][bl["name"]][b, k - bl["k0"]])
+    h.set_block_penalty(st["rho"][b])
+    return h
+
+
+def rollout(cfg, u):
+    """The oracle's open-loop rollout of the input guess u from x0, [BATCH, N + 1, n]."""
+    x = np.zeros((BATCH, N + 1, cfg.n))
+    for b in range(BATCH):
+        h = crc.make_oracle(cfg, b)
+        for k in range(N):
+            h.L.oracle_ilqr_set_input(h.h, k, crc._c(u[b, k]))
+        h.L.oracle_ilqr_open_loop_rollout(h.h)
+        x[b] = h.get("x_cand")
+    return x
+
+
+def oracle_dual_phases(cfg, st):
+    """cone_region_cases.phases at state `st` (its duals and penalties kept), stacked over the batch."""
+    per = []
+    for b in range(BATCH):
+        h = _handle(cfg, st, b)
+        crc.set_guess(h, cfg, b, st["x"], st["u"])
+        crc.expand(h)
+        per.append(crc.phases(h, crc.ALPHAS[b]))
+    return {q: np.stack([np.asarray(r[q], dtype=np.float64) for r in per]) for q in QUANTITIES}
+
+
+def solve_options(cfg, feasible, rho0=RHO0, tolg=HUGE):
+    """The options of the frozen solve (tolg = 1e-8: one with a real line search) in the units of `cfg`."""
+    s = getattr(cfg, "scale", 1.0)
+    return dict(tol_stationarity=TOL_STAT, tol_meritfun_gradient=tolg * s, tol_primal_feasibility=HUGE if feasible else 0.0,
+                penalty_initial=rho0 * s, penalty_scaling=PENALTY_SCALING, penalty_max=PENALTY_MAX * s)
+
+
+def oracle_update(cfg, st, feasible, sweeps, rho0=RHO0, tolg=HUGE, backtracking=False):
+    """The oracle's solve of `sweeps` sweeps from state `st` (its u the input guess).  Returns, in the units of `cfg`, dict(z per block,
+    rho [BATCH], alpha [BATCH, sweeps] (NaN for a sweep not taken), status, iterations, x, u the nominal trajectory, K, d, P, p of the
+    last sweep)."""
+    o = solve_options(cfg, feasible, rho0, tolg)
+    out = dict(rho=np.zeros(BATCH), alpha=np.full((BATCH, sweeps), np.nan), status=np.zeros(BATCH), iterations=np.zeros(BATCH))
+    zs, per = {}, {q: [] for q in ("x", "u") + SWEEP}
+    for b in range(BATCH):
+        h = _handle(cfg, st, b)
+        for k in range(N):
+            h.L.oracle_ilqr_set_input(h.h, k, crc._c(st["u"][b, k]))
+        h.set_penalty(o["penalty_initial"], o["penalty_scaling"], o["penalty_max"])
+        h.L.oracle_ilqr_set_options(h.h, sweeps, o["tol_stationarity"], o["tol_primal_feasibility"], o["tol_meritfun_gradient"], int(backtracking))
+        status, iters, log = h.solve()
+        taken = min(iters, sweeps)
+        out["status"][b], out["iterations"][b] = status, iters
+        out["alpha"][b, :taken] = log[:taken, 0]
+        rhos = set()
+        for k in range(N + 1):
+            for slot, j in enumerate(cfg.at(k)):
+                zs[(j, b, k)] = h.duals(k, slot); rhos.add(h.penalty(k, slot))
+        assert len(rhos) == 1
+        out["rho"][b] = rhos.pop()
+        for q in per:
+            per[q].append(h.get(q))
+    out["z"] = block_arrays(cfg, zs)
+    out.update({q: np.stack(v) for q, v in per.items()})
+    return out
+
+
+UPDATE_KEYS = ("rho", "alpha", "status", "iterations", "x", "u")
+
+
+def differing_update(a, ref, sweep=False, problems=None):
+    """The entries of an oracle_update-shaped result on which a and ref are not bit-identical (NaNs of alpha equal), over `problems`
+    (None: all), as {key: largest |a - ref|}."""
+    idx = slice(None) if problems is None else np.asarray(problems)
+    pairs = [(q, a[q], ref[q]) for q in UPDATE_KEYS + (SWEEP if sweep else ())] + [("z:" + nm, a["z"][nm], ref["z"][nm]) for nm in ref["z"]]
+    out = {}
+    for q, x, y in pairs:
+        x, y = np.asarray(x, dtype=np.float64)[idx], np.asarray(y, dtype=np.float64)[idx]
+        if not np.array_equal(x, y, equal_nan=True):
+            out[q] = float(np.nanmax(np.abs(x - y)))
+    return out
+
+
+def dual_errors(cfg, z, ref):
+    """hard_cases.blockerr of the duals per block KIND: one block per (problem, knot point, constraint block), no floor; a reference
+    entry block that is exactly zero must be exactly zero.  {"z_soc": .., "z_orth": .., "z_eq": ..} for the kinds `cfg` has."""
+    out = {}
+    for bl in cfg.blocks:
+        e = hc.blockerr(np.asarray(z[bl["name"]], dtype=np.float64), ref[bl["name"]])
+        out["z_" + bl["kind"]] = max(out.get("z_" + bl["kind"], 0.0), e)
+    return out
+
+
+def ratios(e, e_cpu):
+    """e / max(e_cpu, floor) per key of e."""
+    return {q: e[q] / max(float(e_cpu[q]), FLOOR) for q in e}
+
+
+# ---- S2 -------------------------------------------------------------------------------------------------------------------------------
+def ze_margin(cfg, st, rho):
+    """The smallest distance of a ze = z - rho c of state `st` from its region's boundary, relative to its own size: a cone's
+    |a - |s|| / max(a, |s|), an orthant row's |ze| / max(|z|, |rho c|)."""
+    worst = np.inf
+    for j, bl in enumerate(cfg.blocks):
+        if bl["kind"] == "eq":
+            continue
+        for (b, k) in cfg.slots(j):
+            zd = st["z"][bl["name"]][b, k - bl["k0"]]
+            rc = rho * crc.values(bl["G"], bl["g"], cfg.z(b, k, st["x"], st["u"]))
+            ze = zd - rc
+            if bl["kind"] == "soc":
+                a, s = float(np.sqrt(crc.seq_sum(ze[:-1] * ze[:-1]))), float(ze[-1])
+                worst = min(worst, abs(a - abs(s)) / max(a, abs(s)))
+            else:
+                size = np.maximum(np.abs(zd), np.abs(rc))
+                worst = min(worst, float((np.abs(ze) / size).min()))
+    return worst
+
+
+def coverage(cfg, st, rho):
+    """{block name: the set of regions (cones) / of row activities "active", "inactive" (orthant blocks) ze takes over batch and horizon}."""
+    out = {}
+    for (j, b, k), c in state_classes(cfg, st, rho).items():
+        got = out.setdefault(cfg.blocks[j]["name"], set())
+        if cfg.blocks[j]["kind"] == "soc":
+            got.add(c[0])
+        else:
+            got.update("inactive" if e == "neg" else "active" for e in c)
+    return out
+
+
+def covered(cfg, cov):
+    want = {"soc": {"below", "inside", "outside"}, "orth": {"active", "inactive"}}
+    return all(cov[bl["name"]] == want[bl["kind"]] for bl in cfg.blocks if bl["kind"] != "eq")
+
+
+_states = {}
+
+
+def update_state(name):
+    """S2 of configuration `name`, and whether the cones' duals had to be steered for it."""
+    if name not in _states:
+        cfg, s1 = crc.config(name), dual_state(name)
+        st = dict(z={nm: a.copy() for nm, a in s1["z"].items()}, rho=s1["rho"], u=s1["u"], x=rollout(cfg, s1["u"]))
+        steered = not (covered(cfg, coverage(cfg, st, RHO0)) and ze_margin(cfg, st, RHO0) >= MARGIN_ZE)
+        if steered:     # z_s of every cone block from a scheduled region, the way cone_region_cases.steer_from_duals chooses x[svar]
+            for j, bl in enumerate(cfg.blocks):
+                if bl["kind"] != "soc":
+                    continue
+                for i, (b, k) in enumerate(cfg.slots(j)):
+                    zd = st["z"][bl["name"]][b, k - bl["k0"]]
+                    c = crc.values(bl["G"], bl["g"], cfg.z(b, k, st["x"], st["u"]))
+                    zev = zd[:-1] - RHO0 * c[:-1]
+                    a = float(np.sqrt(crc.seq_sum(zev * zev)))
+                    f = crc.REGION_FACTOR[("below", "inside", "outside")[(i + j) % 3]]
+                    f = f[(i // 3) % 2] if isinstance(f, tuple) else f
+                    zd[-1] = f * a + RHO0 * c[-1]
+        _states[name] = (st, steered)
+    return _states[name]
+
+
+RHO_LS = 1.0
+
+
+def search_state(name):
+    """The state of the sweep with a REAL line search: S1's duals and input guess, with the penalty the handle holds EQUAL to the
+    solve's penalty_initial = RHO_LS.  (From S1's own penalties, 10 .. 1000 against penalty_initial = 3, the first gradient -- formed with
+    the held penalty -- and the Hessian -- formed with penalty_initial -- disagree by that factor and the oracle accepts alpha = 1 on no
+    problem of any configuration; with both at 3 it rejects 3 of 7 on lane_6_3; with both at 1 at most 1 of 7 anywhere.)"""
+    cfg, s1 = crc.config(name), dual_state(name)
+    return dict(s1, rho=np.full(BATCH, RHO_LS), x=rollout(cfg, s1["u"]))
+
+
+def search_mask(name, backtracking):
+    """[BATCH] bool: the problems on which the oracle's one sweep from search_state accepts alpha = 1 in the old units and under
+    every transform of transforms(name)."""
+    cfg, st = crc.config(name), search_state(name)
+    kw = dict(feasible=False, sweeps=1, rho0=RHO_LS, tolg=1e-8, backtracking=backtracking)
+    ok = oracle_update(cfg, st, **kw)["alpha"][:, 0] == 1.0
+    for T in transforms(name):
+        out = transform(cfg, *T)
+        ok &= oracle_update(out, transform_state(cfg, out, st), **kw)["alpha"][:, 0] == 1.0
+    return ok
+
+
+def state_class_tables(cfg, st):
+    """class_tables for a state: the branches at its guess, at the oracle's candidate of alpha = 0 and at that of alpha_b, with the
+    state's duals and penalties, int8 [3, blocks, BATCH, N + 1, max rows]."""
+    xs = np.zeros((2, BATCH, N + 1, cfg.n)); us = np.zeros((2, BATCH, N, cfg.m))
+    for b in range(BATCH):
+        h = _handle(cfg, st, b)
+        crc.set_guess(h, cfg, b, st["x"], st["u"])
+        crc.expand(h)
+        assert h.L.oracle_ilqr_backward_pass(h.h) == -1
+        for i, alpha in enumerate((0.0, crc.ALPHAS[b])):
+            h.merit(alpha)
+            xs[i, b], us[i, b] = h.get("x_cand"), h.get("u_cand")
+    return np.stack([state_class_table(cfg, st)] + [state_class_table(cfg, dict(st, x=xs[i], u=us[i])) for i in range(2)])
+
+
+# ---- the fixtures of the second half -----------------------------------------------------------------------------------------------
+def dual_fixture_path(name):
+    return os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "loop_phases_duals_%s.npz" % name)
+
+
+def load_duals(name):
+    with np.load(dual_fixture_path(name)) as z:
+        return {k: z[k] for k in z.files}
+
+
+def state_arrays(cfg, st, prefix):
+    """A state as flat fixture entries."""
+    d = {prefix + "_rho": st["rho"], prefix + "_x": st["x"], prefix + "_u": st["u"]}
+    d.update({"%s_z_%s" % (prefix, nm): a for nm, a in st["z"].items()})
+    return d
+
+
+def state_of(fx, cfg, prefix):
+    return dict(z={bl["name"]: fx["%s_z_%s" % (prefix, bl["name"])] for bl in cfg.blocks}, rho=fx[prefix + "_rho"], x=fx[prefix + "_x"],
+                u=fx[prefix + "_u"])
+
+
+def blocks_of(fx, cfg, prefix):
+    return {bl["name"]: fx["%s_%s" % (prefix, bl["name"])] for bl in cfg.blocks}
+
+
+_dual_inputs = {}
+
+
+def dual_inputs(name):
+    """What the fixture of the second half is computed from: S1, S2, their class tables (tab_s1 [3, ..] of the phases at S1; tab_u1 of the
+    first update, at S2 with RHO0; tab_u2 of the second sweep and update, at the oracle's z+ with 10 RHO0) and the line-search masks."""
+    if name not in _dual_inputs:
+        cfg = crc.config(name)
+        s1, (s2, steered) = dual_state(name), update_state(name)
+        z1 = oracle_update(cfg, s2, False, 1)["z"]
+        _dual_inputs[name] = dict(s1=s1, s2=s2, steered=steered, tab_s1=state_class_tables(cfg, s1), tab_u1=state_class_table(cfg, s2, RHO0),
+                                  tab_u2=state_class_table(cfg, dict(s2, z=z1), PENALTY_SCALING * RHO0),
+                                  ls_mask=np.stack([search_mask(name, False), search_mask(name, True)]))
+    return _dual_inputs[name]
+
+
+def dual_input_arrays(cfg, d):
+    out = dict(state_arrays(cfg, d["s1"], "s1"), **state_arrays(cfg, d["s2"], "s2"))
+    out.update(s2_steered=np.array(int(d["steered"])), tab_s1=d["tab_s1"], tab_u1=d["tab_u1"], tab_u2=d["tab_u2"], ls_mask=d["ls_mask"])
+    return out
+
+
+def dual_reference_arrays(cfg, ref):
+    """The maker's {(what, key): batch array} under the fixture's names."""
+    out = {"ref_s1_" + q: ref[("s1", q)] for q in QUANTITIES}
+    for bl in cfg.blocks:
+        for i in (1, 2):
+            out["ref_z%d_%s" % (i, bl["name"])] = ref[("up", "z%d:%s" % (i, bl["name"]))]
+    out.update({"ref_rho%d" % i: ref[("up", "rho%d" % i)] for i in (1, 2)})
+    out.update({"ref_sw2_" + q: ref[("up", q)] for q in SWEEP})
+    return out
+
+
+def oracle_of_fixture(cfg, s1, s2):
+    """The oracle's side of everything the fixture holds a reference for."""
+    up1, up2 = oracle_update(cfg, s2, False, 1), oracle_update(cfg, s2, False, 2)
+    return dict(s1=oracle_dual_phases(cfg, s1), z1=up1["z"], rho1=up1["rho"], z2=up2["z"], rho2=up2["rho"], sw2={q: up2[q] for q in SWEEP})
+
+
+def sweep_errors(res, ref):
+    return {q: hc.blockerr(np.asarray(res[q], dtype=np.float64), ref[q]) for q in SWEEP}
+
+
+def dual_ecpu(cfg, d, fx):
+    """The oracle's blockerr against the references of `fx`: ecpu_s1 [QUANTITIES], ecpu_z1 / ecpu_z2 [KINDS] (0 for a kind the
+    configuration has not), ecpu_sw2 [SWEEP]."""
+    o = oracle_of_fixture(cfg, d["s1"], d["s2"])
+    e = errors(o["s1"], {q: fx["ref_s1_" + q] for q in QUANTITIES})
+    out = dict(ecpu_s1=np.array([e[q] for q in QUANTITIES]))
+    for i in (1, 2):
+        ez = dual_errors(cfg, o["z%d" % i], blocks_of(fx, cfg, "ref_z%d" % i))
+        out["ecpu_z%d" % i] = np.array([ez.get("z_" + kind, 0.0) for kind in KINDS])
+    es = sweep_errors(o["sw2"], {q: fx["ref_sw2_" + q] for q in SWEEP})
+    out["ecpu_sw2"] = np.array([es[q] for q in SWEEP])
+    return out
+
+
+def dual_limits(fx, which):
+    """{key: e_cpu} of fixture entry ecpu_<which>."""
+    keys = {"s1": QUANTITIES, "sw2": SWEEP}.get(which, tuple("z_" + kind for kind in KINDS))
+    return dict(zip(keys, fx["ecpu_" + which]))
+
+
+def state_class_table(cfg, st, rho=None):
+    """class_table's int8 layout for a state (rho None: its penalty per problem)."""
+    rows = max(bl["p"] for bl in cfg.blocks)
+    t = np.full((len(cfg.blocks), BATCH, N + 1, rows), -1, dtype=np.int8)
+    for (j, b, k), c in state_classes(cfg, st, rho).items():
         if cfg.blocks[j]["kind"] == "soc":
             t[j, b, k, 0] = ("below", "inside", "outside").index(c[0])
         else:
