@@ -36,7 +36,7 @@ C_ABI_SYMBOLS = [
     "altro_hip_profile_get", "altro_hip_profile_get_range", "altro_hip_profile_dropped", "altro_hip_algorithmic_bytes",
     "altro_hip_set_model", "altro_hip_set_model_source", "altro_hip_model_row_layout", "altro_hip_set_tracking_cost", "altro_hip_set_quadratic_cost",
     "altro_hip_set_input_guess", "altro_hip_set_state_guess",
-    "altro_hip_open_loop_rollout", "altro_hip_accept", "altro_hip_expand", "altro_hip_merit",
+    "altro_hip_open_loop_rollout", "altro_hip_accept", "altro_hip_expand", "altro_hip_merit", "altro_hip_merit_affine",
     "altro_hip_stationarity", "altro_hip_get_nominal", "altro_hip_get_expansion",
     "altro_hip_default_solve_options", "altro_hip_set_forms", "altro_hip_get_forms", "altro_hip_ilqr_solve", "altro_hip_last_solve_counts",
     "altro_hip_ilqr_solve_async", "altro_hip_ilqr_poll", "altro_hip_ilqr_wait",
@@ -217,6 +217,7 @@ def lib():
         for fn in ("open_loop_rollout", "accept", "expand"):
             getattr(L, "altro_hip_" + fn).argtypes = [vp]
         L.altro_hip_merit.argtypes = [vp, vp, i, i, vp, vp]
+        L.altro_hip_merit_affine.argtypes = [vp, vp, vp, i, vp, vp]
         L.altro_hip_stationarity.argtypes = [vp, vp]
         L.altro_hip_get_nominal.argtypes = [vp, vp, vp]
         L.altro_hip_get_expansion.argtypes = [vp, vp, vp, vp, vp]
@@ -463,6 +464,28 @@ class Batch:
         _check(self.L.altro_hip_merit(self.h, a.ctypes.data_as(C.c_void_p), uniform, int(derivative),
                                       phi.ctypes.data_as(C.c_void_p), dphi.ctypes.data_as(C.c_void_p)))
         return phi, (dphi if derivative else None)
+
+    def merit_affine(self, alpha, active=None, trials=1, out=None):
+        """One affine line-search round (altro_hip_merit_affine): phi [trials, batch] ([batch] for trials = 1) and phi' [batch] at the
+        steps alpha [batch]; trial 1 is alpha * 0.5.  active [batch]: the problems that take part (None: all).  out = (phi, dphi):
+        float64 arrays of those shapes that are filled in place -- the entries of a problem that is masked out keep what they held
+        (without `out` they are NaN)."""
+        self._sync_forms()
+        a = np.ascontiguousarray(alpha, dtype=np.float64)
+        if a.shape != (self.batch,):
+            raise ValueError("alpha must have shape (batch,)")
+        if out is None:
+            out = (np.full((trials, self.batch) if trials > 1 else (self.batch,), np.nan), np.full(self.batch, np.nan))
+        phi, dphi = out
+        for v, n in ((phi, max(trials, 1) * self.batch), (dphi, self.batch)):
+            if not (isinstance(v, np.ndarray) and v.dtype == np.float64 and v.flags.c_contiguous and v.size == n):
+                raise ValueError("out = (phi, dphi): contiguous float64 arrays of trials * batch and batch entries")
+        act = None if active is None else np.ascontiguousarray(np.asarray(active) != 0, dtype=np.int32)
+        if act is not None and act.shape != (self.batch,):
+            raise ValueError("active must have shape (batch,)")
+        _check(self.L.altro_hip_merit_affine(self.h, a.ctypes.data_as(C.c_void_p), None if act is None else act.ctypes.data_as(C.c_void_p),
+                                             int(trials), phi.ctypes.data_as(C.c_void_p), dphi.ctypes.data_as(C.c_void_p)))
+        return phi, dphi
 
     def stationarity(self):
         self._sync_forms()

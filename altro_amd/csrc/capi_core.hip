@@ -348,7 +348,7 @@ int altro_hip_set_dynamics(altro_hip_batch* h, const double* A, const double* B,
                            int kz, int bz) {
   int rc = check(h);
   if (rc) return rc;
-  h->expansion_current = false;
+  h->expansion_current = false; h->aff_base = false;
   if (!A || !B) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "A and B are required");
   const int n = h->n, m = h->m, N = h->N;
   h->has_f = f ? 1 : 0;
@@ -506,7 +506,7 @@ int altro_hip_set_host_batch(altro_hip_batch* h, int host_batch) {
 int altro_hip_set_initial_state(altro_hip_batch* h, const double* x0, int bz) {
   int rc = check(h);
   if (rc) return rc;
-  h->expansion_current = false;
+  h->expansion_current = false; h->aff_base = false;
   if (!x0) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "x0 == NULL");
   const int n0 = h->ragged ? h->nxv[0] : h->n;   // (per-knot-point dimensions: x0 has nx[0] entries per problem)
   rc = aos_set(h, h->x0, 0, h->x0_stride, h->x0_stride, x0, n0, 1, 1, bz);

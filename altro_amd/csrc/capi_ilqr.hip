@@ -138,6 +138,38 @@ void merit_split_prepare(altro_hip_batch* h) {
   }
 }
 
+// Affine line-search trials (kernels/ilqr_merit2_dpp.hip, AFF): who may take them, and their buffers -- one place for the solve
+// (capi_solve.hip) and the step-wise entry (altro_hip_merit_affine).
+// plan MFMA16's line-search rounds in the DPP form (a dense cost, a device model: row-layout kernels only)
+bool merit_rounds_dpp(const altro_hip_batch* h) { return !form(h, ALTRO_HIP_FORM_MERIT_LDS) || h->cost_dense || h->model_set; }
+// plan MFMA16, dynamics as data, fp64, the rounds in the DPP form; ALTRO_HIP_FORM_ROLLOUT_ROUNDS keeps every trial a rollout
+bool affine_eligible(const altro_hip_batch* h) {
+  return h->plan == ALTRO_HIP_PLAN_MFMA16 && h->dtype == ALTRO_HIP_F64 && !h->model_set && merit_rounds_dpp(h) &&
+         !form(h, ALTRO_HIP_FORM_ROLLOUT_ROUNDS) && !h->aff_failed;
+}
+// The base trajectory with its sensitivity, the step it was taken at, the chunks' shares and the flags: true when the handle holds them.
+bool affine_buffers(altro_hip_batch* h) {
+  if (h->i_sens && h->i_sens_alpha && h->i_aff_part && h->i_aff_on) return true;
+  // all four buffers or none: a partial allocation is released and remembered, so that no later solve of this handle
+  // finds a null pointer behind a non-null one or retries a multi-gigabyte hipMalloc; the sensitivity buffer (192 B per knot point
+  // and problem) is only taken while it stays below a quarter of what the handle already holds -- an optimisation must not be what
+  // runs a large batch out of memory
+  const size_t B = h->batch, chunks = (h->N + 15) / 16;
+  const size_t sens_bytes = B * (h->N + 1) * 24 * sizeof(double);
+  int rc = sens_bytes > h->device_bytes / 4 + (size_t(64) << 20) ? 1 : 0;
+  if (!rc) rc = dmalloc(h, &h->i_sens, sens_bytes);
+  if (!rc) rc = dmalloc(h, &h->i_sens_alpha, B * sizeof(double));
+  if (!rc) rc = dmalloc(h, &h->i_aff_part, chunks * ILQR_SPEC_TRIALS * B * 2 * sizeof(double));
+  if (!rc) rc = dmalloc(h, &h->i_aff_on, (size_t)ILQR_SPEC_TRIALS * B * sizeof(int));
+  if (!rc && hipMemsetAsync(h->i_aff_on, 0, (size_t)ILQR_SPEC_TRIALS * B * sizeof(int), h->stream) != hipSuccess) rc = 1;
+  if (rc) {   // an optimisation only: this handle's rounds stay rollouts
+    for (void** q : {&h->i_sens, &h->i_sens_alpha, &h->i_aff_part, &h->i_aff_on}) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    h->aff_failed = true;
+    (void)hipGetLastError();
+  }
+  return !rc;
+}
+
 // what the route of a loop operation may depend on (loop_route.h)
 RouteShape route_shape(const altro_hip_batch* h) {
   return RouteShape{h->plan, h->dtype == ALTRO_HIP_F64, h->ragged, h->n, h->m, h->N, h->batch, h->model_set ? h->model.kind : (int)MODEL_LINEAR, h->cost_dense,
@@ -653,6 +685,7 @@ int altro_hip_open_loop_rollout(altro_hip_batch* h) {
 }
 int altro_hip_accept(altro_hip_batch* h) {
   int rc = ilqr_check(h, false);
+  if (h) h->aff_base = false;   // (a new nominal trajectory)
   if (!rc) rc = ilqr_run(h, IK_ACCEPT, false, false, 0, 0.0);
   return rc;
 }
@@ -679,6 +712,70 @@ int altro_hip_merit(altro_hip_batch* h, const double* alpha, int alpha_is_unifor
   HIP_TRY(hipMemcpyAsync(phi, h->i_phi, (size_t)h->batch * 8, hipMemcpyDeviceToHost, h->stream));
   if (want_derivative && dphi)
     HIP_TRY(hipMemcpyAsync(dphi, h->i_dphi, (size_t)h->batch * 8, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return 0;
+}
+// One affine line-search round on its own (kernels/ilqr_merit2_dpp.hip, AFF): what a solve's search_rounds launches, for the caller's
+// steps.  The first call after a backward sweep runs the sweep's phi(0) evaluation first -- first_evaluation's launch without the
+// speculative first step -- which leaves x_k(0) and s_k = dx_k / dalpha behind; later calls reuse that base (altro_hip_batch::aff_base).
+int altro_hip_merit_affine(altro_hip_batch* h, const double* alpha, const int* active, int trials, double* phi, double* dphi) {
+  int rc = ilqr_check(h, false);
+  if (rc) return rc;
+  if (!h->backward_done) return fail(ALTRO_HIP_ERR_NOT_SET, "backward must precede merit_affine");
+  if (!alpha || !phi) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "alpha and phi are required");
+  if (trials != 1 && trials != 2) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "trials must be 1 or 2 (got %d)", trials);
+  if (!affine_eligible(h))
+    return fail(ALTRO_HIP_ERR_UNSUPPORTED, "affine line-search trials need plan MFMA16, fp64 records, dynamics given as data (no device model), the "
+                                           "DPP merit form and no ALTRO_HIP_FORM_ROLLOUT_ROUNDS%s", h->aff_failed ? "; this handle could not allocate their buffers" : "");
+  if (!affine_buffers(h)) return fail(ALTRO_HIP_ERR_OUT_OF_MEMORY, "no memory for the base trajectory and its sensitivity");
+  const size_t B = h->batch;
+  if (trials > 1 && !ensure_spares(h, trials - 1, B * (h->N + 1) * MF_XUY * h->esz))
+    return fail(ALTRO_HIP_ERR_OUT_OF_MEMORY, "no memory for the second trial's candidate trajectory");
+  // whatever path leaves this call: the switches are the solve's, and off outside it
+  struct Off { altro_hip_batch* h; ~Off() { h->aff_enabled = h->aff_round = h->aff_store = false; h->spec_trials = 1; } } off{h};
+  h->aff_enabled = true;
+  const LsOptions ls = ls_default_options();
+  h->spec_beta = ls.beta_decrease; h->spec_max_iters = ls.max_iters;
+  if (!h->aff_base) {
+    h->aff_store = true;
+    rc = ilqr_run(h, IK_MERIT, false, false, 1, 0.0);
+    h->aff_store = false;
+    if (rc) return rc;
+    h->aff_base = true;
+  }
+  HIP_TRY(hipMemcpyAsync(h->i_alpha, alpha, B * 8, hipMemcpyHostToDevice, h->stream));
+  if (active) {   // the kernels store nothing for a problem that is masked out: what the caller passed in phi / dphi comes back for those
+    HIP_TRY(hipMemcpyAsync(h->i_active, active, B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(h->i_phi, phi, (size_t)trials * B * 8, hipMemcpyHostToDevice, h->stream));
+    if (dphi) HIP_TRY(hipMemcpyAsync(h->i_dphi, dphi, B * 8, hipMemcpyHostToDevice, h->stream));
+  }
+  // trial 1 is the next step of the backtracking sequence, alpha beta, which the kernel takes for a problem whose search is in that
+  // stage (IlqrProb::ls): every problem is put there for this launch, and back afterwards
+  const size_t pitch = sizeof(IlqrProb);
+  char* const stage_p = (char*)h->i_prob + offsetof(IlqrProb, ls) + offsetof(LsState, stage);
+  char* const iter_p = (char*)h->i_prob + offsetof(IlqrProb, ls) + offsetof(LsState, bt_iter);
+  std::vector<int> was(2 * B), now(2 * B, 0);
+  if (trials > 1) {
+    for (size_t b = 0; b < B; ++b) now[b] = LS_STAGE_BACKTRACK;
+    HIP_TRY(hipMemcpy2DAsync(was.data(), sizeof(int), stage_p, pitch, sizeof(int), B, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpy2DAsync(was.data() + B, sizeof(int), iter_p, pitch, sizeof(int), B, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(hipMemcpy2DAsync(stage_p, pitch, now.data(), sizeof(int), sizeof(int), B, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpy2DAsync(iter_p, pitch, now.data() + B, sizeof(int), sizeof(int), B, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // (`was` is read below)
+  }
+  h->spec_trials = trials;
+  h->aff_round = true;
+  rc = ilqr_run(h, IK_MERIT, true, active != nullptr, 1, 0.0);
+  h->aff_round = false;
+  h->spec_trials = 1;
+  if (trials > 1) {
+    HIP_TRY(hipMemcpy2DAsync(stage_p, pitch, was.data(), sizeof(int), sizeof(int), B, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(hipMemcpy2DAsync(iter_p, pitch, was.data() + B, sizeof(int), sizeof(int), B, hipMemcpyHostToDevice, h->stream));
+  }
+  if (rc) { (void)hipStreamSynchronize(h->stream); return rc; }
+  h->forward_done = true;
+  HIP_TRY(hipMemcpyAsync(phi, h->i_phi, (size_t)trials * B * 8, hipMemcpyDeviceToHost, h->stream));
+  if (dphi) HIP_TRY(hipMemcpyAsync(dphi, h->i_dphi, B * 8, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return 0;
 }
@@ -713,6 +810,7 @@ int altro_hip_shift_trajectory(altro_hip_batch* h) {
   if (!rc && h->ragged)   // (the reference's ShiftTrajectory copies knot point k + 1 into k: meaningful between equal dimensions only)
     rc = fail(ALTRO_HIP_ERR_UNSUPPORTED, "altro_hip_shift_trajectory needs uniform dimensions");
   if (!rc) rc = ilqr_run(h, IK_SHIFT, false, false, 0, 0.0);
+  if (!rc) h->aff_base = false;
   return rc;
 }
 int altro_hip_update_linear_costs(altro_hip_batch* h, const double* q, const double* r, const double* c,

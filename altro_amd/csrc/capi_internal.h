@@ -73,6 +73,7 @@ struct altro_hip_batch {
   void *i_sens = nullptr, *i_sens_alpha = nullptr, *i_aff_part = nullptr, *i_aff_on = nullptr;
   bool aff_failed = false;                   // the buffers could not be had once: no retry on this handle
   bool aff_enabled = false, aff_round = false, aff_store = false;   // (aff_store: this launch is the sweep's phi(0) evaluation)
+  bool aff_base = false;                     // altro_hip_merit_affine: i_sens holds the base of the CURRENT backward sweep and nominal trajectory
   bool g_tile = false;                       // plan MFMA32: plan GENERIC's arrays, the sweeps of kernels/tvlqr_tile32.hip (capi_tile32.hip)
   bool g_mfma = false;                       // plan GENERIC, fp64: the backward sweep's products on the matrix cores (ALTRO_HIP_GENERIC_MATRIX_CORES)
   bool ragged = false;                       // per-knot-point dimensions (altro_hip_batch_create_dims): plan GENERIC, TVLQR sweeps only
@@ -575,6 +576,9 @@ int ilqr_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int
 template <typename T>
 IlqrArgs<T> ilqr_args(altro_hip_batch* h, bool use_alpha, bool use_active, int want_deriv, double alpha_const);
 int spec_trials_cap(const altro_hip_batch* h);
+bool merit_rounds_dpp(const altro_hip_batch* h);   // affine line-search trials: the predicates and the buffers the solve and
+bool affine_eligible(const altro_hip_batch* h);    // altro_hip_merit_affine share
+bool affine_buffers(altro_hip_batch* h);
 bool ensure_spares(altro_hip_batch* h, int count, size_t bytes_each);
 void merit_split_prepare(altro_hip_batch* h);
 int ilqr_gather_results(altro_hip_batch* h, altro_hip_solve_result* results);

@@ -54,6 +54,7 @@ struct SolveRun {
     h->bwd_active = nullptr; h->bwd_reg = nullptr; h->stat_skip = nullptr;
     h->spec_trials = 1; h->spec_pre = 0;
     h->aff_round = false; h->aff_enabled = false; h->aff_store = false;
+    h->aff_base = false;            // (the sweeps overwrote the base altro_hip_merit_affine keeps)
     h->i_active = active0;
     h->forms = forms0;
   }
@@ -141,7 +142,7 @@ int SolveRun::configure(const altro_hip_solve_options* opts) {
   // speculative backtracking: how much of the chip the searching problems occupy, and how much there is
   spec_all_on = !form(h, ALTRO_HIP_FORM_NO_SPECULATION) && !generic_plan;   // (plan GENERIC evaluates one step per launch)
   spec_on = o.use_backtracking_linesearch != 0 && spec_all_on;
-  merit_rounds_dpp = !form(h, ALTRO_HIP_FORM_MERIT_LDS) || h->cost_dense || h->model_set;   // (a dense cost, a device model: row-layout kernels only)
+  merit_rounds_dpp = capi::merit_rounds_dpp(h);   // (a dense cost, a device model: row-layout kernels only)
   spec_capacity = lane_plan ? 512 : (merit_rounds_dpp ? 2048 : 4096);   // two waves per CU (LANE: latency-bound; more slow each other down) / four per SIMD (MFMA16)
   run_ahead = !form(h, ALTRO_HIP_FORM_NO_RUNAHEAD);
   // Plan MFMA16: phi(0) and the line search's first step from one pass over the records, the candidate's stationarity / feasibility
@@ -157,28 +158,9 @@ int SolveRun::configure(const altro_hip_solve_options* opts) {
   running = h->batch;
   // Affine line-search trials (kernels/ilqr_merit2_dpp.hip, AFF): plan MFMA16, dynamics as data, fp64; the sweep's phi(0) evaluation
   // leaves the base trajectory and its sensitivity behind.  ALTRO_HIP_FORM_ROLLOUT_ROUNDS keeps every trial a rollout.
-  h->aff_enabled = h->plan == ALTRO_HIP_PLAN_MFMA16 && h->dtype == ALTRO_HIP_F64 && !h->model_set && merit_rounds_dpp &&
-                   !form(h, ALTRO_HIP_FORM_ROLLOUT_ROUNDS) && !h->aff_failed;
+  // (who may take them, and the all-four-or-none allocation of their buffers: capi_ilqr.hip, shared with altro_hip_merit_affine)
+  h->aff_enabled = affine_eligible(h) && affine_buffers(h);
   h->aff_round = false; h->aff_store = false;
-  if (h->aff_enabled && !(h->i_sens && h->i_sens_alpha && h->i_aff_part && h->i_aff_on)) {
-    // all four buffers or none: a partial allocation is released and remembered, so that no later solve of this handle
-    // finds a null pointer behind a non-null one or retries a multi-gigabyte hipMalloc; the sensitivity buffer (192 B per knot point
-    // and problem) is only taken while it stays below a quarter of what the handle already holds -- an optimisation must not be what
-    // runs a large batch out of memory
-    const size_t B = h->batch, chunks = (h->N + 15) / 16;
-    const size_t sens_bytes = B * (h->N + 1) * 24 * sizeof(double);
-    int rc = sens_bytes > h->device_bytes / 4 + (size_t(64) << 20) ? 1 : 0;
-    if (!rc) rc = dmalloc(h, &h->i_sens, sens_bytes);
-    if (!rc) rc = dmalloc(h, &h->i_sens_alpha, B * sizeof(double));
-    if (!rc) rc = dmalloc(h, &h->i_aff_part, chunks * ILQR_SPEC_TRIALS * B * 2 * sizeof(double));
-    if (!rc) rc = dmalloc(h, &h->i_aff_on, (size_t)ILQR_SPEC_TRIALS * B * sizeof(int));
-    if (!rc && hipMemsetAsync(h->i_aff_on, 0, (size_t)ILQR_SPEC_TRIALS * B * sizeof(int), h->stream) != hipSuccess) rc = 1;
-    if (rc) {   // an optimisation only: this handle's rounds stay rollouts
-      for (void** q : {&h->i_sens, &h->i_sens_alpha, &h->i_aff_part, &h->i_aff_on}) { if (*q) (void)hipFree(*q); *q = nullptr; }
-      h->aff_enabled = false; h->aff_failed = true;
-      (void)hipGetLastError();
-    }
-  }
   guard_on = h->aff_enabled && o.decision_margin > 0.0;
   la.guard = guard_on ? h->i_guard : nullptr;
   la.active_exact = guard_on ? h->i_active_exact : nullptr;

@@ -171,6 +171,7 @@ namespace capi {
 
 int launch_backward(altro_hip_batch* h, double reg) {
   ProfScope ps(h, 0);
+  h->aff_base = false;   // (new gains: altro_hip_merit_affine's stored base is the last sweep's)
   if (h->plan == ALTRO_HIP_PLAN_MFMA16) {
     const bool sq = (h->flags & ALTRO_HIP_STORE_QBLOCKS) != 0;
     if (h->dtype == ALTRO_HIP_F64) mfma16_launch_backward<double>(h, reg, sq);

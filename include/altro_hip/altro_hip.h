@@ -308,6 +308,20 @@ int altro_hip_expand(altro_hip_batch* h);            /* dynamics + cost expansio
  * phi / dphi [batch] out; get_x/u/y then return the candidate trajectory x_, u_, y_.               */
 int altro_hip_merit(altro_hip_batch* h, const double* alpha, int alpha_is_uniform, int want_derivative,
                     double* phi, double* dphi);
+/* One AFFINE line-search round on its own -- what the rounds after the first step of a solve's line search launch by default on plan
+ * MFMA16 with fp64 records and dynamics given as data (kernels/ilqr_merit2_dpp.hip, AFF): with x+ = A x + B u + f the closed-loop
+ * rollout of MeritFunction is affine in the step, x_k(alpha) = x_k(0) + alpha s_k, so a trial is a sum over independent knot points.
+ * The first call after altro_hip_backward (or _accept, _set_dynamics, _set_initial_state, _shift_trajectory, a solve) first evaluates
+ * phi(0) the way a sweep does, which leaves x_k(0) and s_k behind and the alpha = 0 candidate in x_, u_, y_; later calls reuse that base:
+ * the second round of a search.  Then the round: alpha [batch]; active [batch] (1 = the problem takes part) or NULL for all;
+ * trials = 1, or 2 for the step alpha[b] and, as trial 1, alpha[b] * beta_decrease (0.5: the next step of the backtracking
+ * sequence, linesearch.cpp:385-412, as a solve's round carries it).  phi [trials][batch] and dphi [batch] (trial 0's; may be NULL)
+ * out -- with a mask they are IN / OUT: the entries of a problem that is masked out come back as they were passed, and its candidate
+ * keeps the last round's values.  get_x/u/y return trial 0's candidate.  Every other handle (another plan, fp32 records, a device
+ * model, ALTRO_HIP_FORM_MERIT_LDS with a diagonal cost, ALTRO_HIP_FORM_ROLLOUT_ROUNDS): ALTRO_HIP_ERR_UNSUPPORTED, the handle stays
+ * usable.  Equal to altro_hip_merit at the same steps to rounding (1e-13), not bit for bit.  A step-wise entry like altro_hip_merit:
+ * it synchronises.                                                                                                              */
+int altro_hip_merit_affine(altro_hip_batch* h, const double* alpha, const int* active, int trials, double* phi, double* dphi);
 int altro_hip_stationarity(altro_hip_batch* h, double* stationarity); /* solver.cpp:207-222, [batch]  */
 int altro_hip_get_nominal(altro_hip_batch* h, double* x, double* u);
 int altro_hip_get_expansion(altro_hip_batch* h, double* A, double* B, double* lx, double* lu);

@@ -21,7 +21,8 @@ An orthant block has entries that are multiples of 1/8; at its tie the variables
 there: val[0] == 0 exactly.  At most one block is at a special class (a tie, apex, v == 0) at one (problem, knot point).
 
 Penalties 1 and 50: the ties stay exact (integers times 50).  N = 5 with cones over the states at the terminal knot point, batch 7
-(the tile and the row layout put two problems in a wave: the last wave is ragged).
+(the tile and the row layout put two problems in a wave: the last wave is ragged).  The horizon is a property of a configuration
+(Config.N): HORIZON_CONFIGS are the tile's two at N = 17 and N = 33, nothing else changed.
 """
 import functools
 
@@ -133,8 +134,9 @@ def eq_block(name, k0, k1, w, var, value):
 
 
 class Config:
-    def __init__(self, name, plan, n, m, dyn, dense, blocks, seed):
+    def __init__(self, name, plan, n, m, dyn, dense, blocks, seed, N=N, base=None):
         self.name, self.plan, self.n, self.m, self.dyn, self.dense, self.blocks = name, plan, n, m, dyn, dense, blocks
+        self.N, self.base = N, base or name    # the horizon; the configuration this one differs from by its horizon alone
         self.w = n + m
         if dyn == "data":
             self.p = problems.ilqr12x4_problem(BATCH, N, True, n=n, m=m)
@@ -154,7 +156,7 @@ class Config:
         return [j for j, bl in enumerate(self.blocks) if bl["k0"] <= k <= bl["k1"]]
 
     def _steer(self, seed):
-        n, m, w = self.n, self.m, self.w
+        n, m, w, N = self.n, self.m, self.w, self.N
         z = 0.7 * problems.normal((BATCH, N + 1, w), 300 + seed)
         z[:, N, n:] = 0.0                                                      # (no inputs at the terminal knot point)
         taken = set()
@@ -228,7 +230,7 @@ class Config:
     def z(self, b, k, x=None, u=None):
         x = self.x if x is None else x
         u = self.u if u is None else u
-        return np.concatenate([x[b, k], u[b, k] if k < N else np.zeros(self.m)])
+        return np.concatenate([x[b, k], u[b, k] if k < self.N else np.zeros(self.m)])
 
     def classes(self, rho=1.0, x=None, u=None, duals=None, rhos=None):
         """{(block, b, k): (region, class, a)} for cones, {...: [class per row]} for orthant blocks, from G, g, x, u, z, rho."""
@@ -248,7 +250,7 @@ def _vars(lo, hi, skip=()):
     return [i for i in range(lo, hi) if i not in skip]
 
 
-def _cones_everywhere(n, m, ps, rng, extra_run=(), extra_term=()):
+def _cones_everywhere(n, m, ps, rng, extra_run=(), extra_term=(), N=N):
     """Cones of ps[i] rows with svar = state i: one block over states and inputs at k < N, one over the states at k = N."""
     w = n + m
     sv = list(range(len(ps)))
@@ -271,11 +273,12 @@ def config(name):
                   cone_block("cone4_N", 4, N, N, w, 1, _vars(2, n), 3, rng)]
         return Config(name, "LANE", n, m, "di", False, blocks, 1 if n == 4 else 2)
     if name in ("tile_tracking", "tile_dense"):
-        n, m = 12, 4
-        w = n + m
-        blocks = _cones_everywhere(n, m, (2, 3, 4), rng, extra_run=[box_block("box", 0, N - 1, n, m, 0.375),
-                                                                      dense_orth_block("orth12", 12, 0, N - 1, w, _vars(3, w), rng)])
-        return Config(name, "MFMA16", n, m, "data", name == "tile_dense", blocks, 3)
+        return _tile(name, name, N, rng)
+    if name in HORIZON_CONFIGS:
+        # the tile's two configurations at horizons of two and three chunks of the affine trials (the last chunk one knot point plus the
+        # terminal one): the same blocks from the same draws, so the same special classes and exact ties, spread over more slots
+        base, horizon = name.rsplit("_n", 1)
+        return _tile(name, base, int(horizon), np.random.default_rng(sum(map(ord, base))))
     if name == "generic_14_5":
         n, m = 14, 5
         w = n + m
@@ -297,7 +300,16 @@ def config(name):
     raise KeyError(name)
 
 
+def _tile(name, base, N, rng):
+    n, m = 12, 4
+    w = n + m
+    blocks = _cones_everywhere(n, m, (2, 3, 4), rng, extra_run=[box_block("box", 0, N - 1, n, m, 0.375),
+                                                                  dense_orth_block("orth12", 12, 0, N - 1, w, _vars(3, w), rng)], N=N)
+    return Config(name, "MFMA16", n, m, "data", base == "tile_dense", blocks, 3, N=N, base=base)
+
+
 CONFIGS = ("lane_4_2", "lane_6_3", "tile_tracking", "tile_dense", "generic_14_5", "auto32_cones", "auto32_rows")
+HORIZON_CONFIGS = ("tile_tracking_n17", "tile_dense_n17", "tile_tracking_n33", "tile_dense_n33")     # (not part of CONFIGS: judged on the merit phase)
 
 
 # ---- the oracle's side -----------------------------------------------------------------------------------------------------------
@@ -307,7 +319,7 @@ def _c(a):
 
 def make_oracle(cfg, b, g_of=None):
     """The oracle's handle of problem b: dynamics, cost, x0, the blocks in registration order.  g_of: {block index: g} overrides."""
-    n, m = cfg.n, cfg.m
+    n, m, N = cfg.n, cfg.m, cfg.N
     if cfg.dyn == "di":
         s = oracle.ILQR(N, n, m, H_DI, oracle.DYN_MODEL, oracle.MODEL_DI, model_dim=m, cost_kind=oracle.COST_DIAGONAL)
         for k in range(N + 1):
@@ -335,6 +347,7 @@ def make_oracle(cfg, b, g_of=None):
 def set_guess(s, cfg, b, x=None, u=None):
     x = cfg.x if x is None else x
     u = cfg.u if u is None else u
+    N = cfg.N
     for k in range(N + 1):
         s.L.oracle_ilqr_set_state(s.h, k, _c(x[b, k]))
     for k in range(N):
@@ -420,7 +433,7 @@ REGION_FACTOR = {"below": -2.0, "inside": 2.0, "outside": (0.5, -0.5)}          
 def steer_from_duals(cfg, duals, rhos, seed):
     """A guess that puts ze = z - rho c of every cone block into a scheduled region (below, inside, outside in turn; no ties: a comes
     from dense rows and duals with all their digits).  duals / rhos: {(block, b, k): z / rho}.  Returns x, u, {(block, b, k): region}."""
-    n, m, w = cfg.n, cfg.m, cfg.w
+    n, m, w, N = cfg.n, cfg.m, cfg.w, cfg.N
     z = 0.7 * problems.normal((BATCH, N + 1, w), 500 + seed)
     z[:, N, n:] = 0.0
     want = {}
@@ -445,6 +458,7 @@ def nonzero_dual_reference(name):
     """The oracle's truncated solve of every problem from the rollout of cfg.u_start, its duals and penalties, the guess steered from
     them and the phases there (duals kept).  Returns dict(status, iterations, dual_updates, log, duals, rhos, x, u, want, phases)."""
     cfg = config(name)
+    N = cfg.N
     sweeps = SOLVE_SWEEPS[name]
     out = dict(status=[], iterations=[], dual_updates=[], log=[], duals={}, rhos={}, handles=[])
     for b in range(BATCH):

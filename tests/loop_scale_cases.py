@@ -41,10 +41,13 @@ import numpy as np
 
 from tests import cone_region_cases as crc
 from tests import hard_cases as hc
-from tests.cone_region_cases import BATCH, N, RHOS
+from tests.cone_region_cases import BATCH, RHOS
 
 QUANTITIES = ("lx", "lu", "K", "d", "P", "p", "phi0", "dphi0", "phi", "dphi", "x", "u", "feas", "stat")
 SCALARS = ("phi0", "dphi0", "phi", "dphi", "feas", "stat")
+# what a fixture of the merit phase alone holds a reference for (a horizon at which every quantity would make the file larger than any
+# other under tests/golden): phi(0), phi'(0), phi, phi' and the candidates at ALPHAS, feasibility
+MERIT_QUANTITIES = ("phi0", "dphi0", "phi", "dphi", "x", "u", "feas")
 MARGIN, FLOOR = 10.0, 1e-13
 PENALTY_MAX = 1e8
 TINY = np.finfo(np.float64).tiny
@@ -64,7 +67,7 @@ def transforms(name, fp32=False):
     kk, kmix, dx, du = (8, 3, 4, 3) if fp32 else (20, 5, 10, 6)
     out = [(kk, one_n, one_m), (-kk, one_n, one_m)]
     if cfg.dyn == "data":
-        rng = np.random.default_rng(77 + sum(map(ord, name)))
+        rng = np.random.default_rng(77 + sum(map(ord, cfg.base)))     # (a configuration at another horizon: its base's changes of units)
         for k in (kmix, -kmix):
             out.append((k, 2.0 ** rng.integers(-dx, dx + 1, size=cfg.n), 2.0 ** rng.integers(-du, du + 1, size=cfg.m)))
     return out
@@ -207,6 +210,7 @@ def class_tables(cfg, rho):
     """class_table at the three points the phases evaluate the AL terms at: the guess, the oracle's candidate of alpha = 0 and its
     candidate of alpha_b, as int8 [3, blocks, BATCH, N + 1, max rows]."""
     if (cfg.name, rho) not in _tables:
+        N = cfg.N
         xs = np.zeros((2, BATCH, N + 1, cfg.n)); us = np.zeros((2, BATCH, N, cfg.m))
         for b in range(BATCH):
             h = expanded(cfg, b, rho)
@@ -263,7 +267,8 @@ def load(name):
 
 
 def reference(fx, ri):
-    return {q: fx["ref_%d_%s" % (ri, q)] for q in QUANTITIES}
+    """(a fixture of the merit phase alone -- MERIT_QUANTITIES -- holds no reference for the others)"""
+    return {q: fx["ref_%d_%s" % (ri, q)] for q in QUANTITIES if "ref_%d_%s" % (ri, q) in fx}
 
 
 def inputs(cfg):
@@ -285,7 +290,7 @@ def class_table(cfg, rho, x=None, u=None):
     max rows], from the fp64 classification (cone_region_cases.classify_*): a cone's region in column 0 (0 below, 1 inside, 2 outside),
     an orthant row's activity per row (1: ze <= 0), -1 where there is nothing."""
     rows = max(bl["p"] for bl in cfg.blocks)
-    t = np.full((len(cfg.blocks), BATCH, N + 1, rows), -1, dtype=np.int8)
+    t = np.full((len(cfg.blocks), BATCH, cfg.N + 1, rows), -1, dtype=np.int8)
     for (j, b, k), c in cfg.classes(rho, x, u).items():
         if cfg.blocks[j]["kind"] == "soc":
             t[j, b, k, 0] = ("below", "inside", "outside").index(c[0])
@@ -319,7 +324,7 @@ def dual_state(name):
     cfg, ref = crc.config(name), crc.nonzero_dual_reference(name)
     rho = np.zeros(BATCH)
     for b in range(BATCH):
-        rhos = {ref["rhos"][(j, b, k)] for k in range(N + 1) for j in cfg.at(k)}
+        rhos = {ref["rhos"][(j, b, k)] for k in range(cfg.N + 1) for j in cfg.at(k)}
         assert len(rhos) == 1 and max(rhos) > 1.0, (name, b, rhos)       # one penalty per problem, raised by the oracle's penalty updates
         rho[b] = max(rhos)
     return dict(z=block_arrays(cfg, ref["duals"]), rho=rho, x=ref["x"], u=ref["u"])
@@ -361,7 +366,7 @@ def transform_state(cfg, out, st, rho0=None):
 def _handle(cfg, st, b):
     """The oracle's handle of problem b with the state's duals and penalty written by the setters."""
     h = crc.make_oracle(cfg, b)
-    for k in range(N + 1):
+    for k in range(cfg.N + 1):
         for slot, j in enumerate(cfg.at(k)):
             bl = cfg.blocks[j]
             h.set_duals(k, slot, st["z"][bl["name"]][b, k - bl["k0"]])
@@ -371,6 +376,7 @@ def _handle(cfg, st, b):
 
 def rollout(cfg, u):
     """The oracle's open-loop rollout of the input guess u from x0, [BATCH, N + 1, n]."""
+    N = cfg.N
     x = np.zeros((BATCH, N + 1, cfg.n))
     for b in range(BATCH):
         h = crc.make_oracle(cfg, b)
@@ -404,6 +410,7 @@ def oracle_update(cfg, st, feasible, sweeps, rho0=RHO0, tolg=HUGE, backtracking=
     rho [BATCH], alpha [BATCH, sweeps] (NaN for a sweep not taken), status, iterations, x, u the nominal trajectory, K, d, P, p of the
     last sweep)."""
     o = solve_options(cfg, feasible, rho0, tolg)
+    N = cfg.N
     out = dict(rho=np.zeros(BATCH), alpha=np.full((BATCH, sweeps), np.nan), status=np.zeros(BATCH), iterations=np.zeros(BATCH))
     zs, per = {}, {q: [] for q in ("x", "u") + SWEEP}
     for b in range(BATCH):
@@ -550,6 +557,7 @@ def search_mask(name, backtracking):
 def state_class_tables(cfg, st):
     """class_tables for a state: the branches at its guess, at the oracle's candidate of alpha = 0 and at that of alpha_b, with the
     state's duals and penalties, int8 [3, blocks, BATCH, N + 1, max rows]."""
+    N = cfg.N
     xs = np.zeros((2, BATCH, N + 1, cfg.n)); us = np.zeros((2, BATCH, N, cfg.m))
     for b in range(BATCH):
         h = _handle(cfg, st, b)
@@ -654,7 +662,7 @@ def dual_limits(fx, which):
 def state_class_table(cfg, st, rho=None):
     """class_table's int8 layout for a state (rho None: its penalty per problem)."""
     rows = max(bl["p"] for bl in cfg.blocks)
-    t = np.full((len(cfg.blocks), BATCH, N + 1, rows), -1, dtype=np.int8)
+    t = np.full((len(cfg.blocks), BATCH, cfg.N + 1, rows), -1, dtype=np.int8)
     for (j, b, k), c in state_classes(cfg, st, rho).items():
         if cfg.blocks[j]["kind"] == "soc":
             t[j, b, k, 0] = ("below", "inside", "outside").index(c[0])

@@ -44,7 +44,7 @@ for it in range(cases):
         s.L.oracle_ilqr_set_options(s.h, 60, 1e-4, 1e-4, 1e-8, 1 if backtracking else 0)
         status, iters, _ = s.solve()
         ref.append((status, iters, s.get("x").reshape(N + 1, n).copy()))
-    line = []
+    line, ends = [], {}
     for name, env in (("affine", "1"), ("rollout", "0")):
         os.environ["ALTRO_HIP_AFFINE"] = env
         bt = altro_amd.Batch(N, n, m, batch)
@@ -54,6 +54,7 @@ for it in range(cases):
             bt.add_linear_constraint(k0, k1, cone, G, g)
         res = bt.ilqr_solve(iterations_max=60, penalty_initial=1.0, penalty_scaling=10.0, use_backtracking=backtracking)
         x, _ = bt.get_nominal()
+        ends[name] = (res["status"].copy(), res["iterations"].copy())
         off, worst = 0, 0.0
         for b in range(batch):
             st, its, xr = ref[b]
@@ -65,6 +66,9 @@ for it in range(cases):
         line.append("%s: %d of %d off the oracle, |dx| %.1e" % (name, off, batch, worst))
         bt.close()
     print("case %2d: N = %2d batch = %2d backtracking %d  |  %s" % (it, N, batch, backtracking, "  |  ".join(line)), flush=True)
+    for b in np.nonzero((ends["affine"][0] != ends["rollout"][0]) | (ends["affine"][1] != ends["rollout"][1]))[0]:   # which problems the two forms end differently on
+        print("      problem %d: affine status %d after %d iterations, rollout status %d after %d"
+              % (b, ends["affine"][0][b], ends["affine"][1][b], ends["rollout"][0][b], ends["rollout"][1][b]), flush=True)
 for name in tot:
     print("%s rounds: %d of %d problems end with another status / iteration count than the oracle; converged rest within %.1e" % (
         name, tot[name][1], tot[name][0], tot[name][2]))

@@ -136,12 +136,13 @@ for it in range(cases):
         s.L.oracle_ilqr_set_options(s.h, 60, 1e-4, 1e-4, 1e-8, 0)
         status, iters, _ = s.solve()
         ref.append((status, iters, s.get("x").reshape(N + 1, n).copy()))
-    line = []
+    line, ends = [], {}
     for name, forms in (("affine", 0), ("rollout", altro_amd.FORM_ROLLOUT_ROUNDS)):
         bt = build(p, N, batch, blocks, altro_amd.PLAN_AUTO, dense, forms)
         assert bt.plan == altro_amd.PLAN_MFMA16
         res = bt.ilqr_solve(iterations_max=60, penalty_initial=1.0, penalty_scaling=10.0)
         x, _ = bt.get_nominal()
+        ends[name] = (res["status"].copy(), res["iterations"].copy())
         off, worst = 0, 0.0
         for b in range(batch):
             st, its, xr = ref[b]
@@ -155,6 +156,9 @@ for it in range(cases):
     conv = sum(1 for r in ref if r[0] == 0)
     print("case %2d: N %2d batch %2d %s, %d blocks, most slots %d, oracle converged %2d; kernels vs GENERIC %.1e; %s"
           % (it, N, batch, "dense" if dense else "diag ", len(blocks), most, conv, kd, "; ".join(line)), flush=True)
+    for b in np.nonzero((ends["affine"][0] != ends["rollout"][0]) | (ends["affine"][1] != ends["rollout"][1]))[0]:   # which problems the two forms end differently on
+        print("      problem %d: affine status %d after %d iterations, rollout status %d after %d"
+              % (b, ends["affine"][0][b], ends["affine"][1][b], ends["rollout"][0][b], ends["rollout"][1][b]), flush=True)
 print("slots at the fullest knot point, cases per count:", dict((i, int(c)) for i, c in enumerate(slot_hist) if c))
 print("kernels against plan GENERIC: worst relative difference %.2e" % kern_worst)
 for name in ("affine", "rollout"):

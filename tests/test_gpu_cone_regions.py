@@ -42,7 +42,7 @@ PLAN = {"LANE": altro_amd.PLAN_LANE, "MFMA16": altro_amd.PLAN_MFMA16, "GENERIC":
 
 def make_hip(cfg, dtype=altro_amd.F64, flags=0):
     n, m = cfg.n, cfg.m
-    bt = altro_amd.Batch(N, n, m, BATCH, dtype=dtype, plan=altro_amd.PLAN_GENERIC if cfg.plan == "GENERIC" else altro_amd.PLAN_AUTO, flags=flags)
+    bt = altro_amd.Batch(cfg.N, n, m, BATCH, dtype=dtype, plan=altro_amd.PLAN_GENERIC if cfg.plan == "GENERIC" else altro_amd.PLAN_AUTO, flags=flags)
     bt.set_forms(altro_amd.FORM_ROLLOUT_ROUNDS)
     if cfg.dyn == "di":
         bt.set_model(altro_amd.MODEL_DOUBLE_INTEGRATOR, crc.H_DI)

@@ -31,6 +31,15 @@ def run(script, *args, env=None):
     return r
 
 
+def differing_forms_do_not_both_converge(out):
+    """WHICH problems may differ (not only how many): every problem on which the affine and the rollout form of the line-search rounds end
+    with another status or iteration count -- the scripts name each -- is one that at least one of the two forms does not solve."""
+    assert "problems end with another status / iteration count" in out
+    for a_st, a_it, b_st, b_it in re.findall(r"problem \d+: affine status (\d) after (\d+) iterations, rollout status (\d) after (\d+)", out):
+        assert (a_st, a_it) != (b_st, b_it)
+        assert not (a_st == "0" and b_st == "0"), (a_st, a_it, b_st, b_it)
+
+
 def test_slice_plan_generic_constrained_solves_against_the_oracle():
     """fuzz_generic_al.py: whole AL-iLQR solves on plan GENERIC, random shapes up to (24, 8), constraint blocks in every cone."""
     r = run("tests/soak/fuzz_generic_al.py", 24, 7)
@@ -69,6 +78,7 @@ def test_slice_tile_constrained_solves_against_the_oracle_in_both_forms_of_the_r
     assert set(got) == {"affine", "rollout"}, r.stdout[-2000:] + r.stderr[-2000:]
     assert got["rollout"][0] == 0 and got["affine"][0] <= 1
     assert got["rollout"][1] >= 60 and got["rollout"][2] < 1e-9 and got["affine"][2] < 1e-9
+    differing_forms_do_not_both_converge(r.stdout)
 
 
 def test_slice_affine_rounds_against_rollout_rounds():
@@ -105,6 +115,7 @@ def test_slice_six_slot_tables_against_the_oracle_and_plan_generic():
     assert set(got) == {"affine", "rollout"}, r.stdout[-2000:] + r.stderr[-2000:]
     assert got["rollout"][0] <= 1 and got["affine"][0] <= 1
     assert got["rollout"][1] >= 80 and got["rollout"][2] < 1e-9 and got["affine"][2] < 1e-9
+    differing_forms_do_not_both_converge(r.stdout)
     m = re.search(r"kernels against plan GENERIC: worst relative difference ([0-9.e+-]+)", r.stdout)
     assert m and float(m.group(1)) < 1e-12
 

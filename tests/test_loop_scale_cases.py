@@ -86,6 +86,41 @@ def test_fixtures_are_what_their_inputs_produce(name):
         assert not lsc.rejected(lsc.criterion_b(oracle(name, ri), fx, ri))
 
 
+@pytest.mark.parametrize("name", crc.HORIZON_CONFIGS)
+def test_horizon_fixtures_are_what_their_inputs_produce_and_the_oracle_meets_criterion_b(name):
+    """The tile's two configurations at N = 17 and N = 33 (two and three chunks of the affine trials): the same blocks as at N = 5, the
+    fixture is the one its inputs produce, and the oracle alone meets criterion B on every quantity the fixture holds -- at N = 33 the
+    merit phase's (loop_scale_cases.MERIT_QUANTITIES; the file would otherwise be the largest under tests/golden)."""
+    cfg, base = crc.config(name), crc.config(name.rsplit("_n", 1)[0])
+    assert cfg.N == int(name.rsplit("_n", 1)[1]) and cfg.base == base.name and cfg.dense == base.dense
+    assert cfg.x.shape == (BATCH, cfg.N + 1, 12) and cfg.u.shape == (BATCH, cfg.N, 4)
+    assert [bl["name"] for bl in cfg.blocks] == [bl["name"] for bl in base.blocks]
+    for bl, b0 in zip(cfg.blocks, base.blocks):
+        assert np.array_equal(bl["G"], b0["G"]) and (bl["k0"], bl["k1"]) == ((0, cfg.N - 1) if b0["k0"] == 0 else (cfg.N, cfg.N))
+        assert bl["name"] == "orth12" or np.array_equal(bl["g"], b0["g"])      # (orth12's g[0] is its tie's: set where the tie is scheduled)
+    assert set(cfg.schedule.values()) == set(base.schedule.values())           # every special class and exact tie is still reached
+    assert lsc.transforms(name)[2][0] == lsc.transforms(base.name)[2][0] and np.array_equal(lsc.transforms(name)[2][1], lsc.transforms(base.name)[2][1])
+    fx = lsc.load(name)
+    assert checksum(lsc.inputs(cfg)) == fx["sum"]
+    held = [q for q in lsc.QUANTITIES if "ref_0_" + q in fx]
+    assert held == list(lsc.QUANTITIES if cfg.N == 17 else [q for q in lsc.QUANTITIES if q in lsc.MERIT_QUANTITIES])
+    for ri, rho in enumerate(RHOS):
+        assert np.array_equal(fx["tab_%d" % ri], lsc.class_tables(cfg, rho))
+        assert fx["flips_%d" % ri] == 0
+        got = oracle(name, ri)
+        e = lsc.errors(got, lsc.reference(fx, ri))
+        assert sorted(e) == sorted(held)
+        ecpu = dict(zip(lsc.QUANTITIES, fx["ecpu_%d" % ri]))
+        assert all(e[q] == ecpu[q] for q in held) and all(np.isnan(ecpu[q]) for q in lsc.QUANTITIES if q not in held), (e, ecpu)
+        assert max(e.values()) < 1e-12
+        assert all(np.isfinite(fx["ref_%d_%s" % (ri, q)]).all() for q in held)
+        ratios = lsc.criterion_b(got, fx, ri)
+        print(name, "rho", rho, " ".join("%s %.2g" % (q, r) for q, r in ratios.items()))
+        assert sorted(ratios) == sorted(held) and not lsc.rejected(ratios)
+        spoilt = dict(got, phi=got["phi"] * (1.0 + 1e-9))                      # (the criterion has teeth at these horizons too)
+        assert set(lsc.rejected(lsc.criterion_b(spoilt, fx, ri))) == {"phi"}
+
+
 def _accepted_today(cfg, got, name, ri):
     """Would tests/test_gpu_cone_regions.py's comparison with the oracle have accepted `got`?"""
     ref = crc.zero_dual_reference(name)

@@ -16,7 +16,6 @@ import altro_amd  # noqa: E402
 from tests import problems  # noqa: E402
 
 SWITCHES = ("ALTRO_HIP_MERIT_DPP", "ALTRO_HIP_EXPAND_DPP", "ALTRO_HIP_ALROWS_DPP")
-os.environ["ALTRO_HIP_AFFINE"] = "0"   # the kernel FORMS against each other: every line-search trial a rollout in both (the affine rounds exist in the row layout only)
 KEYS = ("status", "iterations", "dual_updates", "phi", "stationarity", "feasibility", "alpha", "penalty")
 
 
@@ -59,6 +58,10 @@ def solve(p, N, n, m, blocks, dtype, dpp, kw):
 
 
 def main():
+    # the kernel FORMS against each other: every line-search trial a rollout in both (the affine rounds exist in the row layout only).
+    # (Set here, not at import: tests/test_gpu_affine.py and tools/fuzz_affine.py import blocks_for, and a variable left behind by the
+    #  import put every test that ran after it in the same process on FORM_ROLLOUT_ROUNDS.)
+    os.environ["ALTRO_HIP_AFFINE"] = "0"
     cases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
     rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 7)
     bad = 0
