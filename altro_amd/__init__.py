@@ -58,6 +58,7 @@ FORM_LANE_QUAD_OFF, FORM_LANE_QUAD_ON, FORM_GENERIC_LATE_Q_OFF, FORM_GENERIC_LAT
 FORM_AFFINE_EXACT = 0x8000
 FORM_NO_COMPACTION = 0x10000
 FORM_GENERIC_MERIT_LDS = 0x20000
+FORM_FORWARD_WAVE = 0x40000
 
 
 def forms_from_env():

@@ -85,6 +85,7 @@ struct altro_hip_batch {
   void *m_in = nullptr, *m_cin = nullptr, *m_term = nullptr, *m_out = nullptr, *m_outn = nullptr, *m_xuy = nullptr,
        *m_qblk = nullptr, *m_trash = nullptr;   // element type = handle dtype (fp32 storage allowed)
   Mfma16Strides m_st{};
+  bool fwd_group_ready = false;   // mfma16_forward_group_kernel may use its dynamic LDS on this handle's device
   // plan LANE: batch structure-of-arrays ([k][element][batch])
   void *l_in = nullptr, *l_term = nullptr, *l_out = nullptr, *l_outn = nullptr, *l_xuy = nullptr,
        *l_x0 = nullptr;
@@ -587,6 +588,7 @@ bool tile32_supported(int n, int m);                        // capi_tile32.hip: 
 int tile32_launch_backward(altro_hip_batch* h, double reg);
 int tile32_launch_forward(altro_hip_batch* h);
 int launch_forward(altro_hip_batch* h);
+bool mfma16_forward_is_group(const altro_hip_batch* h);   // the fp64 forward sweep runs one workgroup per 16 problems
 bool mfma16_forward_is_x4(const altro_hip_batch* h);   // the forward sweep runs four problems per wave (pure fp32)
 
 }  // namespace capi

@@ -7,6 +7,7 @@
 #include "kernels/tvlqr_mfma16_f32.hip"
 #include "kernels/tvlqr_mfma16_f32x4.hip"
 #include "kernels/tvlqr_mfma16_fwd_f32x4.hip"
+#include "kernels/tvlqr_mfma16_fwd_group.hip"
 
 using namespace altro_hip;
 using namespace altro_hip::capi;
@@ -164,6 +165,23 @@ void mfma16_launch_forward(altro_hip_batch* h, const Mfma16Args<S>& a) {
   PROF_LAUNCH((mfma16_forward_kernel<S, 3>), dim3(mf_grid(h->batch)), dim3(64), 0, h->stream, a);
 }
 
+// fp64, whole groups of 16 problems: one workgroup of 16 waves per group fetches the group's records as contiguous runs
+// (kernels/tvlqr_mfma16_fwd_group.hip).  G = 16 with a register ring two knot points deep is the form tools/membench.hip `group`
+// measured fastest (G = 8 or the LDS-DMA fetch: 4-9 % slower; depth 3: no faster).  136 KB of dynamic LDS: one workgroup per CU,
+// sixteen waves, the occupancy of the wave-per-problem kernel.
+constexpr int kFwdGroup = 16, kFwdGroupDepth = 2;
+int mfma16_launch_forward_group(altro_hip_batch* h, const Mfma16Args<double>& a) {
+  const auto kernel = mfma16_forward_group_kernel<double, kFwdGroup, kFwdGroupDepth>;
+  const size_t lds = Mfma16FwdGroup<kFwdGroup>::lds_bytes(kFwdGroupDepth);
+  if (!h->fwd_group_ready) {   // more than 64 KB of dynamic LDS has to be asked for, once per device: a handle stays on its own
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return fail(ALTRO_HIP_ERR_HIP, "forward group kernel: %s", hipGetErrorString(e));
+    h->fwd_group_ready = true;
+  }
+  PROF_LAUNCH(kernel, dim3(mf_grid(h->batch / kFwdGroup)), dim3(64 * kFwdGroup), lds, h->stream, a);
+  return 0;
+}
+
 }  // namespace
 
 namespace altro_hip {
@@ -241,13 +259,27 @@ bool mfma16_forward_is_x4(const altro_hip_batch* h) {
   return h->plan == ALTRO_HIP_PLAN_MFMA16 && h->dtype == ALTRO_HIP_F32 && (h->flags & ALTRO_HIP_F32_PURE) && h->batch % 4 == 0;
 }
 
+// the fp64 forward sweep in the group form: whole groups of problems in the contiguous [k][b] slabs; ALTRO_HIP_FORM_FORWARD_WAVE keeps
+// the wave-per-problem kernel
+bool mfma16_forward_is_group(const altro_hip_batch* h) {
+  const int64_t B = h->batch;
+  return h->plan == ALTRO_HIP_PLAN_MFMA16 && h->dtype == ALTRO_HIP_F64 && !form(h, ALTRO_HIP_FORM_FORWARD_WAVE) &&
+         h->batch % kFwdGroup == 0 && h->m_st.in_bs == MF_DYN && h->m_st.in_ks == B * MF_DYN && h->m_st.out_bs == MF_OUT &&
+         h->m_st.out_ks == B * MF_OUT;
+}
+
 int launch_forward(altro_hip_batch* h) {
   ProfScope ps(h, 1);
   h->expansion_current = false;   // the sweep writes the candidate trajectory: whatever expansion a merit pass left is not of this point
   if (h->plan == ALTRO_HIP_PLAN_MFMA16) {
     if (h->dtype == ALTRO_HIP_F64) {
       auto a = mfma16_args<double>(h, 0.0);
-      mfma16_launch_forward<double>(h, a);
+      if (mfma16_forward_is_group(h)) {
+        int rc = mfma16_launch_forward_group(h, a);
+        if (rc) return rc;
+      } else {
+        mfma16_launch_forward<double>(h, a);
+      }
     } else {
       auto a = mfma16_args<float>(h, 0.0);
       if (mfma16_forward_is_x4(h)) {   // pure fp32, four problems per wave (kernels/tvlqr_mfma16_fwd_f32x4.hip)

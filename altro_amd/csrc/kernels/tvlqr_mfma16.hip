@@ -465,6 +465,91 @@ __device__ __forceinline__ double readlane_f64(double v, int src_lane) {
   return out.d;
 }
 
+// What a lane does in every step of the forward sweep (the same for every kernel that runs it): which row it owns, where that
+// row's 13 entries sit in the LDS image, and where its result goes inside an XUY record.
+struct Mfma16FwdRole {
+  int row, row_base, out_off;
+  int ra[13];
+  bool is_x, is_u;
+};
+__device__ __forceinline__ Mfma16FwdRole mfma16_fwd_role(int lane) {
+  Mfma16FwdRole ro;
+  const int grp = lane >> 4;
+  const int sub = lane & 15;
+  ro.row = (grp == 1) ? (sub < 4 ? sub : 3) : (sub < 12 ? sub : 11);
+  ro.row_base = (grp == 0) ? MF_FWD_ZLD * ro.row : MF_FWD_OUT0 + 13 * (grp == 1 ? ro.row : 0);
+  // LDS addresses of this lane's row: linear for the rows of Z and Kt; the rows of [P | p] are gathered from the
+  // packed upper triangle (entries left of the diagonal are the transposed ones) and the p block
+#pragma unroll
+  for (int jj = 0; jj < 12; ++jj) ro.ra[jj] = (grp >= 2) ? MF_FWD_OUT0 + MF_OFF_P + mf_sym(ro.row, jj) : ro.row_base + jj;
+  ro.ra[12] = (grp >= 2) ? MF_FWD_OUT0 + MF_OFF_p + ro.row : ro.row_base + 12;
+  ro.out_off = (grp == 0) ? ro.row : ((grp == 1) ? 24 + ro.row : 12 + ro.row);   // x | y | u inside a record
+  ro.is_x = (grp == 0);
+  ro.is_u = (grp == 1);
+  return ro;
+}
+// One knot point of the forward sweep from its staged LDS image: this lane's row, x_k broadcast, the three phases, and the
+// unconditional store of x_k | y_k | u_k into the record `o`.  Returns x_{k+1}[row] (meaningful in group 0).
+template <typename S>
+__device__ __forceinline__ double mfma16_fwd_step(const double* __restrict__ lds, double* __restrict__ xu_lds, const Mfma16FwdRole& ro,
+                                                  int lane, double xcur, S* __restrict__ o) {
+  // this lane's row (16 doubles) and, for the x+ rows, f[row]
+  double rd[16];
+#pragma unroll
+  for (int j = 0; j < 13; ++j) rd[j] = lds[ro.ra[j]];
+#pragma unroll
+  for (int j = 13; j < 16; ++j) rd[j] = lds[ro.row_base + j];   // columns of B: meaningful in the rows of Z only
+  const double fi = lds[MF_FWD_F0 + ro.row];
+  // x_k broadcast from lanes 0..11 through SGPRs
+  double xs[12];
+  if constexpr (sizeof(S) == 4) {
+    if (lane < 12) xu_lds[lane] = xcur;
+    __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): one wave, in-order LDS: the write is visible to the reads below
+#pragma unroll
+    for (int j = 0; j < 12; ++j) xs[j] = xu_lds[j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < 12; ++j) xs[j] = readlane_f64(xcur, j);
+  }
+  // phase A: sum_j row[j] x[j]   (A x | K x | P x depending on the lane's role)
+  double acc = 0.0;
+#pragma unroll
+  for (int j = 0; j < 12; ++j) acc = __builtin_fma(rd[j], xs[j], acc);
+  // phase B: the affine column.  u = -(K x - d) ; y = P x + p
+  const double aff = acc + rd[12];
+  const double uval = -aff;
+  double us[4];
+  if constexpr (sizeof(S) == 4) {
+    if (lane >= 16 && lane < 20) xu_lds[lane - 4] = uval;
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) us[c] = xu_lds[12 + c];
+  } else {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) us[c] = readlane_f64(uval, 16 + c);
+  }
+  // phase C: x+ = A x + B u + f
+  double xn = acc + fi;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) xn = __builtin_fma(rd[12 + c], us[c], xn);
+  // store x_k | y_k | u_k (every lane stores; replicas write identical values)
+  const double sval = ro.is_x ? xcur : (ro.is_u ? uval : aff);
+  o[ro.out_off] = (S)sval;
+  return xn;
+}
+// terminal knot point: x_N, y_N = P_N x_N + p_N (tvlqr.cpp:238-246), u slot zeroed
+template <typename S>
+__device__ __forceinline__ void mfma16_fwd_terminal(const S* __restrict__ on, const Mfma16FwdRole& ro, double xcur, S* __restrict__ o) {
+  double xs[12];
+#pragma unroll
+  for (int j = 0; j < 12; ++j) xs[j] = readlane_f64(xcur, j);
+  double acc = (double)on[ro.row * 13 + 12];
+#pragma unroll
+  for (int j = 0; j < 12; ++j) acc = __builtin_fma((double)on[ro.row * 13 + j], xs[j], acc);
+  const double sval = ro.is_x ? xcur : (ro.is_u ? 0.0 : acc);
+  o[ro.out_off] = (S)sval;
+}
+
 template <typename S, int DEPTH>
 __global__ __launch_bounds__(64) void mfma16_forward_kernel(Mfma16Args<S> a) {
   __shared__ __attribute__((aligned(16))) double lds[MF_FWD_LDS + 4];
@@ -477,21 +562,9 @@ __global__ __launch_bounds__(64) void mfma16_forward_kernel(Mfma16Args<S> a) {
   const S* __restrict__ out = a.out + (size_t)b * a.out_bs;
   S* __restrict__ xuy = a.xuy + (size_t)b * a.xuy_bs;
   S* __restrict__ trash = a.trash + (size_t)b * MF_OUT;
-  // roles
-  const int grp = lane >> 4;
-  const int sub = lane & 15;
-  const int row = (grp == 1) ? (sub < 4 ? sub : 3) : (sub < 12 ? sub : 11);
-  const int row_base = (grp == 0) ? MF_FWD_ZLD * row : MF_FWD_OUT0 + 13 * (grp == 1 ? row : 0);
-  // LDS addresses of this lane's row: linear for the rows of Z and Kt; the rows of [P | p] are gathered from the
-  // packed upper triangle (entries left of the diagonal are the transposed ones) and the p block
-  int ra[13];
-#pragma unroll
-  for (int jj = 0; jj < 12; ++jj) ra[jj] = (grp >= 2) ? MF_FWD_OUT0 + MF_OFF_P + mf_sym(row, jj) : row_base + jj;
-  ra[12] = (grp >= 2) ? MF_FWD_OUT0 + MF_OFF_p + row : row_base + 12;
-  const int out_off = (grp == 0) ? row : ((grp == 1) ? 24 + row : 12 + row);   // x | y | u inside a record
-  const bool is_x = (grp == 0), is_u = (grp == 1);
+  const Mfma16FwdRole ro = mfma16_fwd_role(lane);
 
-  double xcur = (double)a.x0[(size_t)b * 12 + row];   // meaningful in group 0: x_k[row]
+  double xcur = (double)a.x0[(size_t)b * 12 + ro.row];   // meaningful in group 0: x_k[row]
   // Register ring: knot point k + DEPTH is requested while knot point k computes, so DEPTH records
   // (DEPTH x 3.3 KB per wave) are in flight -- the read-dominated sweep needs that to fill HBM.
   typename Mfma16FwdRing<S>::type ring[DEPTH];
@@ -514,67 +587,15 @@ __global__ __launch_bounds__(64) void mfma16_forward_kernel(Mfma16Args<S> a) {
         const int kn = (k + DEPTH < N) ? k + DEPTH : N - 1;
         mfma16_fwd_load(ring[dd], in + (size_t)kn * a.in_ks, out + (size_t)kn * a.out_ks, lane);
       }
-      // this lane's row (16 doubles) and, for the x+ rows, f[row]
-      double rd[16];
-#pragma unroll
-      for (int j = 0; j < 13; ++j) rd[j] = lds[ra[j]];
-#pragma unroll
-      for (int j = 13; j < 16; ++j) rd[j] = lds[row_base + j];   // columns of B: meaningful in the rows of Z only
-      const double fi = lds[MF_FWD_F0 + row];
-      // x_k broadcast from lanes 0..11 through SGPRs
-      double xs[12];
-      if constexpr (sizeof(S) == 4) {
-        if (lane < 12) xu_lds[lane] = xcur;
-        __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): one wave, in-order LDS: the write is visible to the reads below
-#pragma unroll
-        for (int j = 0; j < 12; ++j) xs[j] = xu_lds[j];
-      } else {
-#pragma unroll
-        for (int j = 0; j < 12; ++j) xs[j] = readlane_f64(xcur, j);
-      }
-      // phase A: sum_j row[j] x[j]   (A x | K x | P x depending on the lane's role)
-      double acc = 0.0;
-#pragma unroll
-      for (int j = 0; j < 12; ++j) acc = __builtin_fma(rd[j], xs[j], acc);
-      // phase B: the affine column.  u = -(K x - d) ; y = P x + p
-      const double aff = acc + rd[12];
-      const double uval = -aff;
-      double us[4];
-      if constexpr (sizeof(S) == 4) {
-        if (lane >= 16 && lane < 20) xu_lds[lane - 4] = uval;
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) us[c] = xu_lds[12 + c];
-      } else {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) us[c] = readlane_f64(uval, 16 + c);
-      }
-      // phase C: x+ = A x + B u + f
-      double xn = acc + fi;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) xn = __builtin_fma(rd[12 + c], us[c], xn);
-      // store x_k | y_k | u_k (every lane stores; replicas write identical values)
-      const double sval = is_x ? xcur : (is_u ? uval : aff);
+      S* __restrict__ o = live ? xuy + (size_t)k * a.xuy_ks : trash;
+      const double xn = mfma16_fwd_step<S>(lds, xu_lds, ro, lane, xcur, o);
       __syncthreads();                       // all reads of this knot point's LDS image are done
       mfma16_fwd_stage(ring[(dd + 1) % DEPTH], lds, lane);   // record k+1: requested DEPTH-1 steps ago
-      S* __restrict__ o = live ? xuy + (size_t)k * a.xuy_ks : trash;
-      o[out_off] = (S)sval;
       __syncthreads();
       xcur = live ? xn : xcur;
     }
   }
-  // terminal knot point: x_N, y_N = P_N x_N + p_N (tvlqr.cpp:238-246), u slot zeroed
-  {
-    const S* __restrict__ on = a.outn + (size_t)b * MF_TERM;
-    double xs[12];
-#pragma unroll
-    for (int j = 0; j < 12; ++j) xs[j] = readlane_f64(xcur, j);
-    double acc = (double)on[row * 13 + 12];
-#pragma unroll
-    for (int j = 0; j < 12; ++j) acc = __builtin_fma((double)on[row * 13 + j], xs[j], acc);
-    const double sval = is_x ? xcur : (is_u ? 0.0 : acc);
-    xuy[(size_t)N * a.xuy_ks + out_off] = (S)sval;
-  }
+  mfma16_fwd_terminal<S>(a.outn + (size_t)b * MF_TERM, ro, xcur, xuy + (size_t)N * a.xuy_ks);
 }
 
 // ---- MFMA layout self-test: D = A(16x4) B(4x16) + C with the layout this file assumes ----------

@@ -474,6 +474,8 @@ typedef struct altro_hip_solve_options { /* AltroOptions, solver_options.hpp:16-
                                                     launch (default: chunks of sweeps over the list of still-running problems)              */
 #define ALTRO_HIP_FORM_GENERIC_MERIT_LDS 0x20000u /* plans GENERIC / MFMA32: MeritFunction by the wave-per-problem LDS kernel also where the
                                                     row-layout one runs (uniform n <= 31, m <= 8, n + m <= 32: kernels/ilqr_row32.hip)        */
+#define ALTRO_HIP_FORM_FORWARD_WAVE 0x40000u     /* plan MFMA16, fp64: the wave-per-problem forward sweep also where the batch is whole groups
+                                                    of 16 (kernels/tvlqr_mfma16_fwd_group.hip runs those by default; bit-identical results)  */
 /* forms of a HANDLE: what altro_hip_merit / _expand / _sweep and every solve on it run with (a solve ORs its options' bits in) */
 int altro_hip_set_forms(altro_hip_batch* h, unsigned forms);
 unsigned altro_hip_get_forms(const altro_hip_batch* h);

@@ -1,8 +1,11 @@
 // tools/membench.hip -- HBM streaming probes on MI355X: what bandwidth can the backward sweep's access
 // pattern reach with NO arithmetic?  (Practical roof next to the 8 TB/s datasheet number.)
 //   hipcc --offload-arch=gfx950 -O3 tools/membench.hip -o /tmp/membench && /tmp/membench
+//   /tmp/membench multi    just the problems-per-wave table (profiles/r03g_membench_multi.txt)
+//   /tmp/membench group    just the workgroup-run table: G adjacent problems' records fetched as contiguous runs (profiles/r07a_*)
 #include <hip/hip_runtime.h>
 #include <cstdio>
+#include <cstring>
 #include <vector>
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); return 1; } } while (0)
 
@@ -72,19 +75,23 @@ __global__ __launch_bounds__(64) void stream_records(const double* __restrict__ 
   }
 }
 
-// forward-sweep pattern: per step read two fully-used records (204 + 208 doubles), write 28 doubles
-template <int DEPTH>
+// forward-sweep pattern: per step read two fully-used records (204 + RO doubles: RO = 208 full, 144 packed), write 28 doubles;
+// MAP = 1: the XCD-aware block -> problem mapping
+template <int DEPTH, int RO = 208, int MAP = 0>
 __global__ __launch_bounds__(64) void stream_fwd(const double* __restrict__ dyn, const double* __restrict__ outr, double* __restrict__ xuy, int N, int batch) {
-  const int lane = threadIdx.x, b = blockIdx.x;
+  constexpr int CO = RO / 64;   // whole 64-lane pieces of the second record; its last 16 elements ride with f
+  static_assert(RO == CO * 64 + 16 && CO <= 3, "208 or 144");
+  const int lane = threadIdx.x;
+  const int b = MAP ? (int)((blockIdx.x & 7) * (batch / 8) + (blockIdx.x >> 3)) : (int)blockIdx.x;
   double buf[DEPTH + 1][7];
   auto load = [&](double* r, int k) {
     const double* d = dyn + ((size_t)k * batch + b) * 204;
-    const double* o = outr + ((size_t)k * batch + b) * 208;
+    const double* o = outr + ((size_t)k * batch + b) * RO;
 #pragma unroll
     for (int c = 0; c < 3; ++c) r[c] = d[c * 64 + lane];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) r[3 + c] = o[c * 64 + lane];
-    r[6] = o[192 + (lane & 15)] + d[192 + (lane < 12 ? lane : 11)];
+    for (int c = 0; c < 3; ++c) r[3 + c] = c < CO ? o[c * 64 + lane] : 0.0;
+    r[6] = o[CO * 64 + (lane & 15)] + d[192 + (lane < 12 ? lane : 11)];
   };
 #pragma unroll
   for (int d = 0; d < DEPTH; ++d) load(buf[d], d);
@@ -237,8 +244,152 @@ __global__ __launch_bounds__(64) void stream_multi(const double* __restrict__ in
   }
 }
 
+// ---- workgroup-contiguous runs: one block of G waves owns G adjacent problems -----------------------------------------
+// In the [k][b] slabs the G problems' records of one knot point are one contiguous run per array (G * RA and G * RB doubles).
+// The block's 64 * G threads fetch both runs as consecutive 16-byte chunks (thread t: chunk t, then t + 64 G, ...) into an
+// LDS ring of DEPTH slots, knot point k + DEPTH while knot point k is consumed; wave w then reads its own record out of the
+// slot.  DMA = 1: __builtin_amdgcn_global_load_lds (16 bytes per lane, no VGPR destination), counted vmcnt waits and raw
+// s_barrier, so that DEPTH - 1 knot points stay in flight across the barriers.  DMA = 0: global_load_dwordx4 into a register
+// ring, ds_write_b128 into the slot at the step that consumes it.  OUTRUN = 0: every wave stores WOUT doubles itself (the
+// forward sweep's x | y | u); OUTRUN = 1: the waves put their WOUT-double records into an LDS stage and the block stores the
+// G-problem run as 16-byte chunks (the backward sweep's OUT records).  DIR = 1 walks the horizon backwards.  No arithmetic.
+typedef double mb_f64x2 __attribute__((ext_vector_type(2)));
+template <int NCNT>
+__device__ __forceinline__ void mb_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NCNT) : "memory"); }
+__device__ __forceinline__ void mb_barrier() {   // LDS traffic of this wave retired, then the bare barrier: no vmcnt(0)
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
+// a wave that issues L loads and S stores per step, loads first: the loads of step k have landed when at most the
+// (DEPTH - 1) younger steps' operations and step k - DEPTH's own stores are outstanding; during the first DEPTH steps
+// fewer stores sit in the queue, so the count without them is used
+template <int L, int S, int DEPTH>
+__device__ __forceinline__ void mb_wait_step(bool first) {
+  if (first) mb_wait_vm<(DEPTH - 1) * L>(); else mb_wait_vm<(DEPTH - 1) * (L + S) + S>();
+}
+template <int RA, int RB, int WOUT, int OUTRUN, int DIR, int G, int DEPTH, int DMA>
+__global__ __launch_bounds__(64 * G) void stream_group(const double* __restrict__ ina, const double* __restrict__ inb,
+                                                       double* __restrict__ out, int N, int batch) {
+  constexpr int T = 64 * G;
+  constexpr int CA = RA / 2, CB = RB / 2;             // 16-byte chunks per record
+  constexpr int CIN = G * (CA + CB);                  // chunks per knot point and group: run A, then run B
+  constexpr int ROUNDS = (CIN + T - 1) / T;
+  constexpr int LASTW = (CIN - (ROUNDS - 1) * T + 63) / 64;   // waves that have chunks in the last round
+  constexpr int SLOT = ((CIN + 63) / 64) * 64;        // slot pitch in chunks: whole wave-instructions
+  constexpr int COUT = OUTRUN ? G * WOUT / 2 : 0;     // chunks of the output run
+  constexpr int OROUNDS = OUTRUN ? (COUT + T - 1) / T : 1;
+  constexpr int OLASTW = OUTRUN ? (COUT - (OROUNDS - 1) * T) / 64 : G;
+  static_assert(RA % 2 == 0 && RB % 2 == 0 && (!OUTRUN || COUT % 64 == 0), "16-byte chunks, whole wave-instructions");
+  static_assert(LASTW >= 1 && LASTW <= G && OLASTW >= 1 && OLASTW <= G, "wave classes");
+  static_assert((DEPTH * SLOT + COUT) * 16 <= 160 * 1024, "LDS of one CU");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  mb_f64x2* const ring = (mb_f64x2*)smem;
+  double* const ostage = (double*)(ring + DEPTH * SLOT);
+  const int t = threadIdx.x, lane = t & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int ngrp = batch / G, chunk = ngrp / 8;
+  const int grp = (int)((blockIdx.x & 7) * chunk + (blockIdx.x >> 3));
+  const size_t b0 = (size_t)grp * G;
+  const bool lastw = wv < LASTW, olastw = wv < OLASTW;
+  // this thread's chunk of every round: which run, and where inside it (DMA = 0 clamps past the end: same bytes, same place)
+  const mb_f64x2* src[ROUNDS];
+  size_t sstride[ROUNDS];
+  int dst[ROUNDS];
+#pragma unroll
+  for (int r = 0; r < ROUNDS; ++r) {
+    int c = r * T + t;
+    dst[r] = DMA ? c : (c < CIN ? c : CIN - 1);
+    c = c < CIN ? c : CIN - 1;
+    const bool isa = c < G * CA;
+    src[r] = isa ? (const mb_f64x2*)(ina + b0 * RA) + c : (const mb_f64x2*)(inb + b0 * RB) + (c - G * CA);
+    sstride[r] = (size_t)batch * (isa ? CA : CB);
+  }
+  auto knot = [&](int step) { const int s = step < N ? step : N - 1; return DIR ? N - 1 - s : s; };
+  mb_f64x2 regs[DMA ? 1 : DEPTH][ROUNDS];
+  auto fetch = [&](int d, int step) {
+    const size_t kk = knot(step);
+    if constexpr (DMA) {
+#pragma unroll
+      for (int r = 0; r < ROUNDS; ++r) {
+        if (r < ROUNDS - 1 || LASTW == G || lastw)
+          __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[r] + kk * sstride[r]),
+                                           (__attribute__((address_space(3))) void*)(ring + d * SLOT + r * T + wv * 64), 16, 0, 0);
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < ROUNDS; ++r) regs[d][r] = src[r][kk * sstride[r]];
+    }
+  };
+#pragma unroll
+  for (int d = 0; d < DEPTH; ++d) fetch(d, d);
+  // register ring: drain before the loop -- hipcc merges the pre-header's pending loads into the loop header's count and would
+  // wait vmcnt(0) at the top of every trip (the LDS-DMA form counts for itself and keeps its requests in flight)
+  if constexpr (!DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  double acc = 0.0;
+  for (int k0 = 0; k0 < N; k0 += DEPTH) {
+#pragma unroll
+    for (int d = 0; d < DEPTH; ++d) {
+      const int k = k0 + d;
+      if (k >= N) break;   // the same for every wave of every block
+      const size_t kk = knot(k);
+      if constexpr (DMA) {
+        const bool first = k < DEPTH;
+        if (LASTW == G || lastw) {
+          if (olastw) mb_wait_step<ROUNDS, OROUNDS, DEPTH>(first); else mb_wait_step<ROUNDS, OROUNDS - 1, DEPTH>(first);
+        } else {
+          if (olastw) mb_wait_step<ROUNDS - 1, OROUNDS, DEPTH>(first); else mb_wait_step<ROUNDS - 1, OROUNDS - 1, DEPTH>(first);
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < ROUNDS; ++r) ring[d * SLOT + dst[r]] = regs[d][r];
+      }
+      mb_barrier();                                   // the slot is whole
+      const double* ra = (const double*)(ring + d * SLOT) + wv * RA;
+      const double* rb = (const double*)(ring + d * SLOT) + G * RA + wv * RB;
+      double s = 0;
+#pragma unroll
+      for (int c = 0; c < (RA + 63) / 64; ++c) { const int e = c * 64 + lane; s += ra[e < RA ? e : RA - 1]; }
+#pragma unroll
+      for (int c = 0; c < (RB + 63) / 64; ++c) { const int e = c * 64 + lane; s += rb[e < RB ? e : RB - 1]; }
+      acc += s;
+      if constexpr (OUTRUN) {
+#pragma unroll
+        for (int c = 0; c < (WOUT + 63) / 64; ++c) { const int e = c * 64 + lane; ostage[wv * WOUT + (e < WOUT ? e : WOUT - 1)] = acc + c; }
+      }
+      mb_barrier();                                   // every wave has read the slot: it may be refilled
+      fetch(d, k + DEPTH);
+      if constexpr (OUTRUN) {
+        mb_f64x2* orun = (mb_f64x2*)(out + (kk * batch + b0) * WOUT);
+#pragma unroll
+        for (int r = 0; r < OROUNDS; ++r) {
+          const int c = r * T + t;
+          if constexpr (DMA) { if (r < OROUNDS - 1 || OLASTW == G || olastw) orun[c] = ((const mb_f64x2*)ostage)[c]; }
+          else { const int cc = c < COUT ? c : COUT - 1; orun[cc] = ((const mb_f64x2*)ostage)[cc]; }
+        }
+      } else {
+        out[(kk * batch + b0 + wv) * WOUT + (lane % WOUT)] = acc;
+      }
+    }
+  }
+}
+// the two record sets it is run on: the forward sweep's (DYN 204 + OUT 144 in, x | y | u 28 out per wave) and the backward sweep's
+// (DYN 204 + COST 160 in, the OUT run of 144 out through LDS, last knot point first)
+template <int G, int DEPTH, int DMA>
+constexpr auto stream_fwd_group = stream_group<204, 144, 28, 0, 0, G, DEPTH, DMA>;
+template <int G, int DEPTH, int DMA>
+constexpr auto stream_bwd_group = stream_group<204, 160, 144, 1, 1, G, DEPTH, DMA>;
+template <int RA, int RB, int WOUT, int OUTRUN, int DIR, int G, int DEPTH, int DMA>
+static int stream_group_prepare(size_t* lds_bytes) {
+  constexpr int CIN = G * (RA / 2 + RB / 2), SLOT = ((CIN + 63) / 64) * 64, COUT = OUTRUN ? G * WOUT / 2 : 0;
+  *lds_bytes = (size_t)(DEPTH * SLOT + COUT) * 16;
+  CK(hipFuncSetAttribute((const void*)stream_group<RA, RB, WOUT, OUTRUN, DIR, G, DEPTH, DMA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds_bytes));
+  return 0;
+}
+
 int main(int argc, char** argv) {
-  const bool only_multi = argc > 1;   // any argument: just the problems-per-wave table
+  const bool only_group = argc > 1 && !strcmp(argv[1], "group");   // "group": just the workgroup-run table
+  const bool only_multi = argc > 1 && !only_group;                 // any other argument: just the problems-per-wave table
   const int N = 256, batch = 4096;
   const size_t in_n = (size_t)batch * N * 428, out_n = (size_t)batch * N * 208;
   double *in, *out, *sink;
@@ -251,6 +402,46 @@ int main(int argc, char** argv) {
     float ms; hipEventElapsedTime(&ms, e0, e1); ms /= 10;
     printf("%-44s %8.3f ms  %8.1f GB/s\n", name, ms, bytes / ms / 1e6);
   };
+  if (only_group) {
+    const double* dyn = in;
+    const double* outr = in + (size_t)batch * N * 204;   // the second input array: OUT records (forward) or COST records (backward)
+    printf("# forward-sweep record set (204 + 144 r, 28 w doubles per knot point and problem, 3.15 GB), [k][b] slabs, XCD-aware mapping:\n"
+           "# one block of G waves fetches its G problems' runs as 16-byte chunks into an LDS ring (no arithmetic)\n");
+    for (int rep = 0; rep < 2; ++rep) {
+      auto fwd = [&](const char* name, auto launch) { timeit(name, (double)batch * N * (348 + 28) * 8, launch); };
+      size_t l;
+#define FWD_GROUP(G, DEPTH, DMA, label)                                                                                  \
+      if (stream_group_prepare<204, 144, 28, 0, 0, G, DEPTH, DMA>(&l)) return 1;                                         \
+      fwd(label, [&] { stream_fwd_group<G, DEPTH, DMA><<<batch / G, 64 * G, l>>>(dyn, outr, out, N, batch); });
+      FWD_GROUP(8, 2, 1, "group G = 8,  depth 2, LDS-DMA")
+      FWD_GROUP(8, 3, 1, "group G = 8,  depth 3, LDS-DMA")
+      FWD_GROUP(16, 2, 1, "group G = 16, depth 2, LDS-DMA")
+      FWD_GROUP(16, 3, 1, "group G = 16, depth 3, LDS-DMA")
+      FWD_GROUP(8, 2, 0, "group G = 8,  depth 2, load + ds_write")
+      FWD_GROUP(8, 3, 0, "group G = 8,  depth 3, load + ds_write")
+      FWD_GROUP(16, 2, 0, "group G = 16, depth 2, load + ds_write")
+      FWD_GROUP(16, 3, 0, "group G = 16, depth 3, load + ds_write")
+#undef FWD_GROUP
+      fwd("today: stream_mapped<348, 28> 1/wave depth 1", [&] { stream_mapped<348, 28, 1, 1><<<batch, 64>>>(in, out, N, batch); });
+      fwd("today: stream_fwd packed, mapped, depth 3", [&] { stream_fwd<3, 144, 1><<<batch, 64>>>(dyn, outr, out, N, batch); });
+      fwd("today: stream_fwd packed, mapped, depth 1", [&] { stream_fwd<1, 144, 1><<<batch, 64>>>(dyn, outr, out, N, batch); });
+    }
+    printf("# backward-sweep record set (204 + 160 r, 144 w doubles, 4.26 GB) in the group form: the OUT run leaves through LDS\n");
+    for (int rep = 0; rep < 2; ++rep) {
+      auto bwd = [&](const char* name, auto launch) { timeit(name, (double)batch * N * (364 + 144) * 8, launch); };
+      size_t l;
+#define BWD_GROUP(G, DEPTH, DMA, label)                                                                                  \
+      if (stream_group_prepare<204, 160, 144, 1, 1, G, DEPTH, DMA>(&l)) return 1;                                        \
+      bwd(label, [&] { stream_bwd_group<G, DEPTH, DMA><<<batch / G, 64 * G, l>>>(dyn, outr, out, N, batch); });
+      BWD_GROUP(8, 2, 1, "backward group G = 8,  depth 2, LDS-DMA")
+      BWD_GROUP(16, 2, 1, "backward group G = 16, depth 2, LDS-DMA")
+      BWD_GROUP(16, 3, 1, "backward group G = 16, depth 3, LDS-DMA")
+      BWD_GROUP(16, 2, 0, "backward group G = 16, depth 2, load + ds_write")
+#undef BWD_GROUP
+      bwd("today: stream_mapped<364, 144> 1/wave depth 1", [&] { stream_mapped<364, 144, 1, 1><<<batch, 64>>>(in, out, N, batch); });
+    }
+    return 0;
+  }
   if (only_multi) {
     auto gen = [&](const char* name, auto launch) { timeit(name, (double)batch * N * (364 + 144) * 8, launch); };
     printf("# backward-sweep record set (364 r + 144 w doubles per knot point and problem, 4.26 GB), [k][b] slabs, XCD-aware mapping:\n"
