@@ -81,22 +81,22 @@ AlTable<T> al_table(const altro_hip_batch* h) {
 }
 
 template <typename T>
-IlqrArgs<T> ilqr_args(altro_hip_batch* h, bool use_alpha, bool use_active, int want_deriv, double alpha_const) {
+IlqrArgs<T> ilqr_args(altro_hip_batch* h, const LoopCall& c) {
   IlqrArgs<T> a;
   a.al = al_table<T>(h);
   a.mode = EXPAND_GRADIENT | EXPAND_HESSIAN;
   a.in = (T*)h->l_in; a.term = (T*)h->l_term; a.out = (const T*)h->l_out; a.outn = (const T*)h->l_outn;
   a.nom = (T*)h->l_nom; a.cand = (T*)h->l_xuy; a.x0 = (const T*)h->l_x0;
   a.cost = (const T*)(h->cost_dense ? h->l_costq : h->l_cost); a.cost_kind = h->cost_dense ? 1 : 0;
-  a.alpha = use_alpha ? h->i_alpha : nullptr;
-  a.active = use_active ? h->i_active : nullptr;
+  a.alpha = c.use_alpha ? h->i_alpha : nullptr;
+  a.active = c.active;
   a.phi = h->i_phi; a.dphi = h->i_dphi; a.prob = h->i_prob;
-  a.mp = h->model; a.N = h->N; a.batch = h->batch; a.want_derivative = want_deriv; a.alpha_const = alpha_const;
-  a.cand_spec = (T*)h->i_cand_spec; a.spec_trials = h->i_cand_spec ? h->spec_trials : 1; a.spec_sel = h->i_spec_sel;
-  a.spec_pre = h->i_cand_spec ? h->spec_pre : 0;
+  a.mp = h->model; a.N = h->N; a.batch = h->batch; a.want_derivative = c.want_deriv; a.alpha_const = c.alpha_const;
+  a.cand_spec = (T*)h->i_cand_spec; a.spec_trials = h->i_cand_spec ? c.spec_trials : 1; a.spec_sel = h->i_spec_sel;
+  a.spec_pre = h->i_cand_spec ? c.spec_pre : 0;
   a.spec_flip = 0;
   a.spec_stride = (int64_t)h->batch * (h->N + 1) * lane_sizes(h->n, h->m).e_xuy;
-  a.ls_beta = h->spec_beta; a.ls_max_iters = h->spec_max_iters;
+  a.ls_beta = c.ls_beta; a.ls_max_iters = c.ls_max_iters;
   a.merit_jk = h->merit_split == 1 ? (T*)h->i_merit_jk : nullptr;
   a.spec_jac = (T*)h->i_spec_jac;
   return a;
@@ -217,16 +217,17 @@ static int route_execute(altro_hip_batch* h, const RouteShape& shape, const Rout
   return 0;
 }
 template <typename T>
-int lane_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int want_deriv, double alpha_const, int mode) {
-  const IlqrArgs<T> a = ilqr_args<T>(h, use_alpha, use_active, want_deriv, alpha_const);
+int lane_run(altro_hip_batch* h, const LoopCall& c) {
+  const IlqrArgs<T> a = ilqr_args<T>(h, c);
   const RouteShape shape = route_shape(h);
-  const Route route = loop_route(shape, RouteCall{which, mode, a.spec_trials});
+  const Route route = loop_route(shape, RouteCall{c.which, c.mode, a.spec_trials});
   if (route.error == ROUTE_NO_MODEL) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "no device model for (kind, n, m) = (%d, %d, %d)", h->model.kind, h->n, h->m);
-  if (route.error) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "operation %d is not available on plan LANE", which);
+  if (route.error) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "operation %d is not available on plan LANE", c.which);
   return route_execute(h, shape, route, a);
 }
 template <typename S>
-int wave_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int want_deriv, double alpha_const, int mode) {
+int wave_run(altro_hip_batch* h, const LoopCall& c) {
+  const int which = c.which, mode = c.mode;
   IlqrWaveArgs<S> a;
   a.al = al_table<S>(h);
   a.mode = mode;
@@ -235,7 +236,7 @@ int wave_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int
   if (user_al && (h->forms & (ALTRO_HIP_FORM_MERIT_LDS | ALTRO_HIP_FORM_ALROWS_LDS | ALTRO_HIP_FORM_EXPAND_LDS)))
     return fail(ALTRO_HIP_ERR_UNSUPPORTED, "constraint blocks from source on plan MFMA16 run in the row-layout kernels only: the LDS comparison forms "
                                            "(ALTRO_HIP_FORM_MERIT_LDS, _ALROWS_LDS, _EXPAND_LDS) do not evaluate them");
-  a.penalty_scaling = h->expand_penalty_scaling; a.penalty_max = h->expand_penalty_max;
+  a.penalty_scaling = c.penalty_scaling; a.penalty_max = c.penalty_max;
   a.costd = (const S*)h->m_costd; a.costd_term = (const S*)h->m_costd_term; a.cost_dense = h->cost_dense ? 1 : 0;
   if (h->model_set) a.mp = h->model;
   a.dyn = (const S*)h->m_in; a.dyn_bs = h->m_st.in_bs; a.dyn_ks = h->m_st.in_ks;
@@ -243,19 +244,19 @@ int wave_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int
   a.term = (S*)h->m_term; a.out = (const S*)h->m_out; a.out_bs = h->m_st.out_bs; a.out_ks = h->m_st.out_ks;
   a.outn = (const S*)h->m_outn; a.nom = (S*)h->m_nom; a.cand = (S*)h->m_xuy; a.xuy_bs = h->m_st.xuy_bs;
   a.xuy_ks = h->m_st.xuy_ks; a.costp = (const S*)h->m_costp; a.x0 = (const S*)h->x0;
-  a.alpha = use_alpha ? h->i_alpha : nullptr; a.active = use_active ? h->i_active : nullptr;
+  a.alpha = c.use_alpha ? h->i_alpha : nullptr; a.active = c.active;
   a.phi = h->i_phi; a.dphi = h->i_dphi; a.prob = h->i_prob; a.N = h->N; a.batch = h->batch;
-  a.want_derivative = want_deriv; a.alpha_const = alpha_const;
-  a.cand_spec = (S*)h->i_cand_spec; a.spec_trials = h->i_cand_spec ? h->spec_trials : 1; a.spec_sel = h->i_spec_sel;
-  a.spec_pre = h->i_cand_spec ? h->spec_pre : 0;
+  a.want_derivative = c.want_deriv; a.alpha_const = c.alpha_const;
+  a.cand_spec = (S*)h->i_cand_spec; a.spec_trials = h->i_cand_spec ? c.spec_trials : 1; a.spec_sel = h->i_spec_sel;
+  a.spec_pre = h->i_cand_spec ? c.spec_pre : 0;
   a.spec_stride = (int64_t)h->batch * (h->N + 1) * MF_XUY;
-  a.ls_beta = h->spec_beta; a.ls_max_iters = h->spec_max_iters;
-  a.skip = which == IK_STATIONARITY ? h->stat_skip : nullptr;
-  // affine line-search trials (capi_solve.hip switches them on for a solve): fp64 records, dynamics as data only
-  const bool aff_on = sizeof(S) == 8 && h->aff_enabled && !h->model_set;
-  const bool aff_store = aff_on && h->aff_store && (which == IK_MERIT2 || which == IK_MERIT);   // the sweep's phi(0) evaluation leaves base + sensitivity behind
+  a.ls_beta = c.ls_beta; a.ls_max_iters = c.ls_max_iters;
+  a.skip = which == IK_STATIONARITY ? c.stat_skip : nullptr;
+  // affine line-search trials (the caller says which launches take part: LoopCall::aff): fp64 records, dynamics as data only
+  const bool aff_on = sizeof(S) == 8 && c.aff != AFF_OFF && !h->model_set;
+  const bool aff_store = aff_on && c.aff == AFF_STORE && (which == IK_MERIT2 || which == IK_MERIT);   // the sweep's phi(0) evaluation leaves base + sensitivity behind
   const RouteShape shape = route_shape(h);
-  const Route route = loop_route(shape, RouteCall{which, mode, a.spec_trials, aff_on && !aff_store && which == IK_MERIT && h->aff_round && !a.spec_pre});
+  const Route route = loop_route(shape, RouteCall{which, mode, a.spec_trials, aff_on && !aff_store && which == IK_MERIT && c.aff == AFF_ROUND && !a.spec_pre});
   if (route.error) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "operation %d is not available on plan MFMA16", which);
   if constexpr (sizeof(S) == 8) {
     a.aff = route.count && (route.step[0].id & KF_AFF) ? 1 : 0;
@@ -277,8 +278,8 @@ GenSizes gen_sizes(const altro_hip_batch* h) {
 }
 // plan GENERIC: any (n_k, m_k) up to 64, dynamics as data, quadratic cost, linear constraint blocks (kernels/ilqr_generic.hip)
 template <typename T>
-int gen_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int want_deriv, double alpha_const, int mode) {
-  const int n = h->n, m = h->m, N = h->N;
+int gen_run(altro_hip_batch* h, const LoopCall& c) {
+  const int n = h->n, m = h->m, N = h->N, which = c.which, mode = c.mode;
   IlqrGenArgs<T> a;
   a.A = (const T*)h->g_arr[G_A]; a.A_bs = h->g_bstride[G_A]; a.B = (const T*)h->g_arr[G_B]; a.B_bs = h->g_bstride[G_B];
   a.f = (const T*)h->g_arr[G_f]; a.f_bs = h->g_bstride[G_f];
@@ -293,9 +294,9 @@ int gen_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int 
   a.cQ = (const T*)h->g_cQ; a.cR = (const T*)h->g_cR; a.cH = (const T*)h->g_cH; a.cq = (const T*)h->g_cq; a.cr = (const T*)h->g_cr;
   a.cc = (const T*)h->g_cc;
   a.x0 = (const T*)h->x0; a.x0_stride = h->x0_stride;
-  a.alpha = use_alpha ? h->i_alpha : nullptr; a.active = use_active ? h->i_active : nullptr; a.alpha_const = alpha_const;
+  a.alpha = c.use_alpha ? h->i_alpha : nullptr; a.active = c.active; a.alpha_const = c.alpha_const;
   a.phi = h->i_phi; a.dphi = h->i_dphi; a.prob = h->i_prob;
-  a.N = N; a.n = n; a.m = m; a.batch = h->batch; a.want_derivative = want_deriv; a.mode = mode;
+  a.N = N; a.n = n; a.m = m; a.batch = h->batch; a.want_derivative = c.want_deriv; a.mode = mode;
   a.off = h->g_off; a.nx = h->g_nx; a.nu = h->g_nu;
   const GenSizes gs = gen_sizes(h);
   a.sx = gs.sx; a.su = gs.su; a.sQ = gs.sQ; a.sR = gs.sR; a.sH = gs.sH;
@@ -317,23 +318,20 @@ int gen_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int 
   if (route.error) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "operation %d is not available on plan GENERIC", which);
   return route_execute(h, shape, route, a);
 }
-int ilqr_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int want_deriv, double alpha_const, int mode) {
+int ilqr_run(altro_hip_batch* h, const LoopCall& c) {
+  const int which = c.which;
   int rc = al_upload(h);
   if (rc) return rc;
-  if (h->plan == ALTRO_HIP_PLAN_GENERIC)
-    return h->dtype == ALTRO_HIP_F64 ? gen_run<double>(h, which, use_alpha, use_active, want_deriv, alpha_const, mode)
-                                     : gen_run<float>(h, which, use_alpha, use_active, want_deriv, alpha_const, mode);
+  if (h->plan == ALTRO_HIP_PLAN_GENERIC) return h->dtype == ALTRO_HIP_F64 ? gen_run<double>(h, c) : gen_run<float>(h, c);
   if (h->plan == ALTRO_HIP_PLAN_MFMA16) {   // linear dynamics: "expand" = cost gradient (+ AL Hessian terms when constrained)
-    rc = h->dtype == ALTRO_HIP_F64 ? wave_run<double>(h, which, use_alpha, use_active, want_deriv, alpha_const, mode)
-                                   : wave_run<float>(h, which, use_alpha, use_active, want_deriv, alpha_const, mode);
+    rc = h->dtype == ALTRO_HIP_F64 ? wave_run<double>(h, c) : wave_run<float>(h, c);
     // (altro_hip_batch::expansion_current) who writes the candidate trajectory, and who leaves its expansion behind
-    if (which == IK_MERIT) h->expansion_current = !rc && want_deriv && !use_active && h->spec_trials == 1 && !h->spec_pre && h->al_defs.empty();
+    if (which == IK_MERIT) h->expansion_current = !rc && c.want_deriv && !c.active && c.spec_trials == 1 && !c.spec_pre && h->al_defs.empty();
     else if (which == IK_ROLLOUT || which == IK_SHIFT || which == IK_SPEC_SELECT || which == IK_MERIT2 || which == IK_DUAL) h->expansion_current = false;
     return rc;
   }
   if (which == IK_MERIT) merit_split_prepare(h);
-  return h->dtype == ALTRO_HIP_F64 ? lane_run<double>(h, which, use_alpha, use_active, want_deriv, alpha_const, mode)
-                                   : lane_run<float>(h, which, use_alpha, use_active, want_deriv, alpha_const, mode);
+  return h->dtype == ALTRO_HIP_F64 ? lane_run<double>(h, c) : lane_run<float>(h, c);
 }
 
 struct CostUpload { int field; const double* src; int nk_host; };
@@ -425,8 +423,8 @@ int model_takes_dynamics(altro_hip_batch* h) {
   return 0;
 }
 
-template IlqrArgs<double> ilqr_args<double>(altro_hip_batch*, bool, bool, int, double);
-template IlqrArgs<float> ilqr_args<float>(altro_hip_batch*, bool, bool, int, double);
+template IlqrArgs<double> ilqr_args<double>(altro_hip_batch*, const LoopCall&);
+template IlqrArgs<float> ilqr_args<float>(altro_hip_batch*, const LoopCall&);
 }  // namespace capi
 }  // namespace altro_hip
 
@@ -679,14 +677,14 @@ int altro_hip_set_state_guess(altro_hip_batch* h, const double* x, int kz, int b
 
 int altro_hip_open_loop_rollout(altro_hip_batch* h) {
   int rc = ilqr_check(h, true);
-  if (!rc) rc = ilqr_run(h, IK_ROLLOUT, false, false, 0, 0.0);
+  if (!rc) rc = ilqr_run(h, {IK_ROLLOUT});
   if (!rc) h->forward_done = true;
   return rc;
 }
 int altro_hip_accept(altro_hip_batch* h) {
   int rc = ilqr_check(h, false);
   if (h) h->aff_base = false;   // (a new nominal trajectory)
-  if (!rc) rc = ilqr_run(h, IK_ACCEPT, false, false, 0, 0.0);
+  if (!rc) rc = ilqr_run(h, {IK_ACCEPT});
   return rc;
 }
 int altro_hip_expand(altro_hip_batch* h) {
@@ -696,7 +694,7 @@ int altro_hip_expand(altro_hip_batch* h) {
   // lx, lu (A, B for a device model) of this very candidate, and the cost's Hessian blocks are the constants the setter stored
   // (knotpoint_data.cpp:691-705 copies them afresh each sweep) -- nothing to launch
   if (h->plan == ALTRO_HIP_PLAN_MFMA16 && h->expansion_current && h->al_defs.empty()) return 0;
-  return ilqr_run(h, IK_EXPAND, false, false, 0, 0.0);
+  return ilqr_run(h, {IK_EXPAND});
 }
 int altro_hip_merit(altro_hip_batch* h, const double* alpha, int alpha_is_uniform, int want_derivative,
                     double* phi, double* dphi) {
@@ -706,7 +704,9 @@ int altro_hip_merit(altro_hip_batch* h, const double* alpha, int alpha_is_unifor
   if (!alpha || !phi) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "alpha and phi are required");
   if (!alpha_is_uniform)
     HIP_TRY(hipMemcpyAsync(h->i_alpha, alpha, (size_t)h->batch * 8, hipMemcpyHostToDevice, h->stream));
-  rc = ilqr_run(h, IK_MERIT, !alpha_is_uniform, false, want_derivative, alpha[0]);
+  LoopCall c{IK_MERIT};
+  c.want_deriv = want_derivative; c.use_alpha = !alpha_is_uniform; c.alpha_const = alpha[0];
+  rc = ilqr_run(h, c);
   if (rc) return rc;
   h->forward_done = true;
   HIP_TRY(hipMemcpyAsync(phi, h->i_phi, (size_t)h->batch * 8, hipMemcpyDeviceToHost, h->stream));
@@ -731,16 +731,11 @@ int altro_hip_merit_affine(altro_hip_batch* h, const double* alpha, const int* a
   const size_t B = h->batch;
   if (trials > 1 && !ensure_spares(h, trials - 1, B * (h->N + 1) * MF_XUY * h->esz))
     return fail(ALTRO_HIP_ERR_OUT_OF_MEMORY, "no memory for the second trial's candidate trajectory");
-  // whatever path leaves this call: the switches are the solve's, and off outside it
-  struct Off { altro_hip_batch* h; ~Off() { h->aff_enabled = h->aff_round = h->aff_store = false; h->spec_trials = 1; } } off{h};
-  h->aff_enabled = true;
-  const LsOptions ls = ls_default_options();
-  h->spec_beta = ls.beta_decrease; h->spec_max_iters = ls.max_iters;
+  LoopCall c{IK_MERIT};   // (the default search's beta_decrease / max_iters)
+  c.want_deriv = 1;
   if (!h->aff_base) {
-    h->aff_store = true;
-    rc = ilqr_run(h, IK_MERIT, false, false, 1, 0.0);
-    h->aff_store = false;
-    if (rc) return rc;
+    c.aff = AFF_STORE;
+    if ((rc = ilqr_run(h, c))) return rc;
     h->aff_base = true;
   }
   HIP_TRY(hipMemcpyAsync(h->i_alpha, alpha, B * 8, hipMemcpyHostToDevice, h->stream));
@@ -763,11 +758,8 @@ int altro_hip_merit_affine(altro_hip_batch* h, const double* alpha, const int* a
     HIP_TRY(hipMemcpy2DAsync(iter_p, pitch, now.data() + B, sizeof(int), sizeof(int), B, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));   // (`was` is read below)
   }
-  h->spec_trials = trials;
-  h->aff_round = true;
-  rc = ilqr_run(h, IK_MERIT, true, active != nullptr, 1, 0.0);
-  h->aff_round = false;
-  h->spec_trials = 1;
+  c.aff = AFF_ROUND; c.use_alpha = true; c.active = active ? h->i_active : nullptr; c.spec_trials = trials;
+  rc = ilqr_run(h, c);
   if (trials > 1) {
     HIP_TRY(hipMemcpy2DAsync(stage_p, pitch, was.data(), sizeof(int), sizeof(int), B, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipMemcpy2DAsync(iter_p, pitch, was.data() + B, sizeof(int), sizeof(int), B, hipMemcpyHostToDevice, h->stream));
@@ -782,7 +774,7 @@ int altro_hip_merit_affine(altro_hip_batch* h, const double* alpha, const int* a
 int altro_hip_stationarity(altro_hip_batch* h, double* out) {
   int rc = ilqr_check(h, false);
   if (rc) return rc;
-  rc = ilqr_run(h, IK_STATIONARITY, false, false, 0, 0.0);
+  rc = ilqr_run(h, {IK_STATIONARITY});
   if (rc) return rc;
   std::vector<IlqrProb> pr(h->batch);
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -795,7 +787,7 @@ int altro_hip_feasibility(altro_hip_batch* h, double* out) {
   int rc = ilqr_check(h, false);
   if (rc) return rc;
   if (!out) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "out == NULL");
-  rc = ilqr_run(h, IK_STATIONARITY, false, false, 0, 0.0);
+  rc = ilqr_run(h, {IK_STATIONARITY});
   if (rc) return rc;
   std::vector<IlqrProb> pr(h->batch);
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -809,7 +801,7 @@ int altro_hip_shift_trajectory(altro_hip_batch* h) {
   int rc = ilqr_check(h, true);
   if (!rc && h->ragged)   // (the reference's ShiftTrajectory copies knot point k + 1 into k: meaningful between equal dimensions only)
     rc = fail(ALTRO_HIP_ERR_UNSUPPORTED, "altro_hip_shift_trajectory needs uniform dimensions");
-  if (!rc) rc = ilqr_run(h, IK_SHIFT, false, false, 0, 0.0);
+  if (!rc) rc = ilqr_run(h, {IK_SHIFT});
   if (!rc) h->aff_base = false;
   return rc;
 }

@@ -68,11 +68,10 @@ struct altro_hip_batch {
   // plan GENERIC: reference layout on the device
   void* g_arr[G_NUM] = {};
   int64_t g_bstride[G_NUM] = {};
-  // affine line-search trials (plan MFMA16, dynamics as data, fp64: kernels/ilqr_merit2_dpp.hip AFF): buffers, and the two switches the
-  // solve loop sets -- on for this solve / this launch is a line-search round
+  // affine line-search trials (plan MFMA16, dynamics as data, fp64: kernels/ilqr_merit2_dpp.hip AFF): buffers (which launch stores
+  // the base and which is a round is said per launch: capi::LoopCall::aff)
   void *i_sens = nullptr, *i_sens_alpha = nullptr, *i_aff_part = nullptr, *i_aff_on = nullptr;
   bool aff_failed = false;                   // the buffers could not be had once: no retry on this handle
-  bool aff_enabled = false, aff_round = false, aff_store = false;   // (aff_store: this launch is the sweep's phi(0) evaluation)
   bool aff_base = false;                     // altro_hip_merit_affine: i_sens holds the base of the CURRENT backward sweep and nominal trajectory
   bool g_tile = false;                       // plan MFMA32: plan GENERIC's arrays, the sweeps of kernels/tvlqr_tile32.hip (capi_tile32.hip)
   bool g_mfma = false;                       // plan GENERIC, fp64: the backward sweep's products on the matrix cores (ALTRO_HIP_GENERIC_MATRIX_CORES)
@@ -115,7 +114,6 @@ struct altro_hip_batch {
   int fused_resident = 0;        // workgroups of the one-launch kernel the device holds at once (0: not asked yet)
   int *i_guard = nullptr, *i_active_exact = nullptr;   // the decision guard of the affine rounds (IlqrLoopArgs::guard, ::active_exact)
   int* i_stat_done = nullptr;     // plan MFMA16's dual merit evaluation (IlqrLoopArgs::stat_done)
-  const int* stat_skip = nullptr; // set while a solve's IK_STATIONARITY launches may skip those problems
   // MeritFunction in three launches (plan LANE, kernels/ilqr_lane.hip): per-knot-point costs of every trial and the
   // spare A | B | lx | lu block; allocated on the first merit evaluation, merit_split = 0 keeps the one-launch kernel
   void *i_merit_jk = nullptr, *i_spec_jac = nullptr;
@@ -124,11 +122,7 @@ struct altro_hip_batch {
   void* g_ws = nullptr;           // plan GENERIC, blocks beyond 64 KB of LDS: the backward sweep's per-problem work blocks (first use)
   bool fwd_quad = false;          // the last LANE forward sweep ran four lanes per problem
   bool bwd_quad = false;          // the last LANE backward sweep ran four lanes per problem (kernels/tvlqr_quad_body.inc)
-  int spec_trials = 1;            // trials per merit launch of the CURRENT launch (1 = no speculation)
-  int spec_pre = 0;               // the current launch is phi(0) fused with the first trial step
   bool spec_no_memory = false;    // the spare trajectories could not be allocated: no speculation on this handle
-  double spec_beta = 0.5;         // the running solve's LsOptions::beta_decrease / max_iters (what the merit kernels
-  int spec_max_iters = 25;        // need to reproduce the state machine's step sequence)
   ModelParams model{MODEL_LINEAR, 0.0f, 0, 2.7, 1.5};
   bool model_set = false, lqr_cost_set = false, guess_set = false;
   std::vector<double> x0_host;    // the initial state as given, while the handle may still move to another plan (replan_empty_handle)
@@ -152,9 +146,6 @@ struct altro_hip_batch {
   int* al_d_guser = nullptr;             // plan GENERIC: AlTable::guser (blocks from the caller's source), null without such a block
   int *al_d_order = nullptr, *al_d_start = nullptr;   // altro_hip_shift_duals' chains of dual rows (al_shift.h: AlShift::order, ::start), every plan
   int al_nchains = 0;
-  double expand_penalty_scaling = 10.0, expand_penalty_max = 1e8;   // what EXPAND_DUAL's look-ahead of PenaltyUpdate needs
-  const int* bwd_active = nullptr;           // per-problem mask for the backward sweep inside ilqr_solve
-  const double* bwd_reg = nullptr;           // per-problem regularisation inside ilqr_solve (retry extension)
   // iLQR loop on plan MFMA16 (dynamics given as data): nominal trajectory + cost parameters, allocated by
   // altro_hip_set_tracking_cost; ilqr_linear = the backward sweep ignores the affine term (knotpoint_data.cpp:416)
   void *m_nom = nullptr, *m_costp = nullptr;
@@ -572,10 +563,32 @@ int replan_empty_handle(altro_hip_batch* h, int plan);   // capi_core.hip
 int al_upload(altro_hip_batch* h);
 int model_takes_dynamics(altro_hip_batch* h);   // a device model (compiled in or from source) owns the dynamics arrays from now on
 int ilqr_check(altro_hip_batch* h, bool need_guess);
-int ilqr_run(altro_hip_batch* h, int which, bool use_alpha, bool use_active, int want_deriv, double alpha_const,
-             int mode = EXPAND_GRADIENT | EXPAND_HESSIAN);
+// Everything ONE launch of the iLQR loop is told.  The handle holds state (buffers, what has been set, aff_base, expansion_current ...);
+// nothing that describes a single launch lives on it, so nothing has to be put back after one.  `which` and `mode` come first: the
+// common call is ilqr_run(h, {IK_ACCEPT}) or ilqr_run(h, {IK_EXPAND, EXPAND_GRADIENT, mask}).
+enum LoopAff { AFF_OFF = 0,    // no affine trials in this launch (the only value off plan MFMA16's dynamics-as-data fp64 handles)
+               AFF_STORE,      // the sweep's phi(0) evaluation: leaves the base trajectory and its sensitivity behind
+               AFF_ROUND };    // a line-search round: its trials are sums over independent knot points from that base
+struct LoopCall {
+  int which;                                     // IK_*
+  int mode = EXPAND_GRADIENT | EXPAND_HESSIAN;   // EXPAND_* / ROLLOUT_* / IK_MERIT2's form
+  const int* active = nullptr;                   // the mask the launch runs under (i_active, i_spec_refresh, i_active_exact); null: every problem
+  int want_deriv = 0;
+  bool use_alpha = false;                        // steps per problem (i_alpha), or alpha_const for all
+  double alpha_const = 0.0;
+  int spec_trials = 1;                           // trials the merit launch evaluates (1 = no speculation)
+  int spec_pre = 0;                              // the launch is phi(0) with the search's first step riding along
+  LoopAff aff = AFF_OFF;
+  const int* stat_skip = nullptr;                // IK_STATIONARITY: problems the launch may skip
+  double penalty_scaling = 10.0, penalty_max = 1e8;   // what EXPAND_DUAL's look-ahead of PenaltyUpdate needs
+  double ls_beta = ls_default_options().beta_decrease;   // LsOptions::beta_decrease / max_iters of the search the launch serves (what the
+  int ls_max_iters = ls_default_options().max_iters;     // merit kernels need to reproduce the state machine's step sequence)
+};
+// The backward sweep's per-problem mask and regularisation: a solve's (capi_solve.hip); every other caller passes the empty pair.
+struct BackwardMask { const int* active = nullptr; const double* reg_pp = nullptr; };
+int ilqr_run(altro_hip_batch* h, const LoopCall& c);
 template <typename T>
-IlqrArgs<T> ilqr_args(altro_hip_batch* h, bool use_alpha, bool use_active, int want_deriv, double alpha_const);
+IlqrArgs<T> ilqr_args(altro_hip_batch* h, const LoopCall& c);
 int spec_trials_cap(const altro_hip_batch* h);
 bool merit_rounds_dpp(const altro_hip_batch* h);   // affine line-search trials: the predicates and the buffers the solve and
 bool affine_eligible(const altro_hip_batch* h);    // altro_hip_merit_affine share
@@ -583,9 +596,9 @@ bool affine_buffers(altro_hip_batch* h);
 bool ensure_spares(altro_hip_batch* h, int count, size_t bytes_each);
 void merit_split_prepare(altro_hip_batch* h);
 int ilqr_gather_results(altro_hip_batch* h, altro_hip_solve_result* results);
-int launch_backward(altro_hip_batch* h, double reg);
+int launch_backward(altro_hip_batch* h, double reg, const BackwardMask& pp);
 bool tile32_supported(int n, int m);                        // capi_tile32.hip: plan MFMA32
-int tile32_launch_backward(altro_hip_batch* h, double reg);
+int tile32_launch_backward(altro_hip_batch* h, double reg, const BackwardMask& pp);
 int tile32_launch_forward(altro_hip_batch* h);
 int launch_forward(altro_hip_batch* h);
 bool mfma16_forward_is_group(const altro_hip_batch* h);   // the fp64 forward sweep runs one workgroup per 16 problems

@@ -12,6 +12,9 @@
 //   finish_sweep     expansion of steps taken from a speculative trial, stationarity, accept, convergence test   (solver.cpp:459-469)
 //   outer_update     DualUpdate, PenaltyUpdate, refreshed gradients, the next sweep's Hessians  (solver.cpp:470-489)
 //   sequenced_loop   the sweeps, with the host running AHEAD of the device's verdicts
+// What belongs to one solve -- its options, whether its rounds are affine, the backward sweep's mask -- is a member of the SolveRun, and
+// every launch is told what it needs as a LoopCall built from those (capi_internal.h): the handle carries no per-launch switch, so the
+// destructor puts back the handle's own forms, drops the affine base the sweeps overwrote, and nothing else.
 // (Round 5: this was one 470-line function inside capi_ilqr.hip; the forms that lost their A/B comparisons -- the matrix-core and the
 //  LDS form of the two-trial pass, the tile-free expansion's off switch -- went with the split.)
 #include "capi_internal.h"
@@ -34,6 +37,7 @@ struct SolveRun {
   bool fused = false, fused_prologue = false;
   bool dual = false;              // plan MFMA16: phi(0) and the first step in one pass (IK_MERIT2)
   bool spec_all_on = false, spec_on = false, merit_rounds_dpp = true, run_ahead = true;
+  bool aff_enabled = false;       // this solve's line-search rounds are affine trials (plan MFMA16, dynamics as data, fp64)
   bool guard_on = false;          // affine rounds with the decision guard (altro_hip_solve_options::decision_margin > 0)
   int guarded_total = 0;          // trials the guard sent back for a rollout evaluation
   size_t spare_each = 0;
@@ -46,19 +50,26 @@ struct SolveRun {
   bool hessians_ready = false;    // the previous sweep's last expansion left the cost Hessians of this one
   bool hessian_stored = false;
   int diag_mode = 0;
-  int* active0 = nullptr;
+  BackwardMask bwd;               // the backward sweep skips problems that have stopped; their own reg with the retry schedule on
   unsigned forms0 = 0;            // the handle's own forms (the solve's are OR-ed in for its duration)
 
-  explicit SolveRun(altro_hip_batch* h_) : h(h_), active0(h_->i_active), forms0(h_->forms) {}
-  ~SolveRun() {   // whatever path leaves the solve: no speculation state, mask or swapped pointer survives it
-    h->bwd_active = nullptr; h->bwd_reg = nullptr; h->stat_skip = nullptr;
-    h->spec_trials = 1; h->spec_pre = 0;
-    h->aff_round = false; h->aff_enabled = false; h->aff_store = false;
+  explicit SolveRun(altro_hip_batch* h_) : h(h_), forms0(h_->forms) {}
+  ~SolveRun() {
     h->aff_base = false;            // (the sweeps overwrote the base altro_hip_merit_affine keeps)
-    h->i_active = active0;
     h->forms = forms0;
   }
 
+  // a launch of this solve; a merit evaluation of its line search (per-problem steps, with derivative, on the running problems or `mask`)
+  LoopCall call(int which, int mode = EXPAND_GRADIENT | EXPAND_HESSIAN, const int* mask = nullptr) const {
+    LoopCall c{which, mode, mask};
+    c.ls_beta = la.ls.beta_decrease; c.ls_max_iters = la.ls.max_iters;
+    return c;
+  }
+  LoopCall merit(int which, const int* mask, int trials = 1, LoopAff aff = AFF_OFF) const {
+    LoopCall c = call(which, which == IK_MERIT2 ? 2 : EXPAND_GRADIENT | EXPAND_HESSIAN, mask);
+    c.want_deriv = 1; c.use_alpha = true; c.spec_trials = trials; c.aff = aff_enabled ? aff : AFF_OFF;
+    return c;
+  }
   int loop(int which) {
     if (ilqr_launch_loop(h->stream, which, la)) return fail(ALTRO_HIP_ERR_HIP, "iLQR loop kernel launch failed");
     return 0;
@@ -133,7 +144,6 @@ int SolveRun::configure(const altro_hip_solve_options* opts) {
   la.ls = ls_default_options();
   la.ls.try_cubic_first = 1;                                   // solver.cpp:248
   la.ls.use_backtracking = o.use_backtracking_linesearch;      // solver.cpp:417
-  h->spec_beta = la.ls.beta_decrease; h->spec_max_iters = la.ls.max_iters;
   lane_plan = h->plan == ALTRO_HIP_PLAN_LANE;
   generic_plan = h->plan == ALTRO_HIP_PLAN_GENERIC;   // (constraint rows in their one-wave-per-knot-point form: no merged end pass)
   const int64_t cand_elems = (int64_t)h->batch * (h->N + 1) * (lane_plan ? lane_sizes(h->n, h->m).e_xuy : MF_XUY);
@@ -159,14 +169,14 @@ int SolveRun::configure(const altro_hip_solve_options* opts) {
   // Affine line-search trials (kernels/ilqr_merit2_dpp.hip, AFF): plan MFMA16, dynamics as data, fp64; the sweep's phi(0) evaluation
   // leaves the base trajectory and its sensitivity behind.  ALTRO_HIP_FORM_ROLLOUT_ROUNDS keeps every trial a rollout.
   // (who may take them, and the all-four-or-none allocation of their buffers: capi_ilqr.hip, shared with altro_hip_merit_affine)
-  h->aff_enabled = affine_eligible(h) && affine_buffers(h);
-  h->aff_round = false; h->aff_store = false;
-  guard_on = h->aff_enabled && o.decision_margin > 0.0;
+  aff_enabled = affine_eligible(h) && affine_buffers(h);
+  guard_on = aff_enabled && o.decision_margin > 0.0;
   la.guard = guard_on ? h->i_guard : nullptr;
   la.active_exact = guard_on ? h->i_active_exact : nullptr;
   la.decision_margin = guard_on ? o.decision_margin : 0.0;
   la.aff_fed = 0;
   la.aff_exact = (guard_on && form(h, ALTRO_HIP_FORM_AFFINE_EXACT)) ? 1 : 0;
+  bwd = BackwardMask{h->i_active, reg_on ? h->i_reg : nullptr};
   return 0;
 }
 
@@ -233,13 +243,13 @@ int SolveRun::prologue() {
   int rc = loop(ILK_LOOP_INIT);
   if (rc) return rc;
   if (route_rollout_head(route_shape(h))) {   // rollout, CopyTrajectory and the first expansion in one pass (loop_route.h)
-    rc = ilqr_run(h, IK_ROLLOUT, false, false, 0, 0.0, ROLLOUT_INIT);
+    rc = ilqr_run(h, call(IK_ROLLOUT, ROLLOUT_INIT));
   } else {
-    rc = ilqr_run(h, IK_ROLLOUT, false, false, 0, 0.0);
-    if (!rc) rc = ilqr_run(h, IK_ACCEPT, false, false, 0, 0.0);
+    rc = ilqr_run(h, call(IK_ROLLOUT));
+    if (!rc) rc = ilqr_run(h, call(IK_ACCEPT));
     // without constraints the cost Hessian is constant and is written once, here; with them the gradient is formed with the
     // penalty the constraints carry so far and SetPenalty comes after it (solver.cpp:424-430)
-    if (!rc) rc = ilqr_run(h, IK_EXPAND, false, false, 0, 0.0, al ? EXPAND_GRADIENT : (EXPAND_GRADIENT | EXPAND_HESSIAN));
+    if (!rc) rc = ilqr_run(h, call(IK_EXPAND, al ? EXPAND_GRADIENT : (EXPAND_GRADIENT | EXPAND_HESSIAN)));
   }
   if (rc) return rc;
   return al ? loop(ILK_SET_PENALTY) : 0;
@@ -312,6 +322,8 @@ int SolveRun::run_fused() {
     const size_t bytes = (size_t)clk_groups * ILQR_FUSED_PHASES * sizeof(unsigned long long);
     if (hipMalloc((void**)&clk, bytes) == hipSuccess) { (void)hipMemsetAsync(clk, 0, bytes, h->stream); fa.clk = clk; }
   }
+  LoopCall mc = call(IK_MERIT);   // (the kernel's own merit evaluations: one trial, the solve's search options)
+  mc.want_deriv = 1;
   int done = 0, slots = h->batch, groups = groups_of(h->batch), pp = 0;
   sweeps = 0;
   for (;;) {
@@ -330,12 +342,12 @@ int SolveRun::run_fused() {
       LaneArgs<double> ba{(const double*)h->l_in, (const double*)h->l_term, (double*)h->l_out, (double*)h->l_outn,
                           (const double*)h->l_x0, (double*)h->l_xuy, (double*)h->delta_V, h->status, h->N, h->batch, 0.0,
                           nullptr, nullptr};
-      frc = ilqr_launch_fused<double>(h->stream, h->model.kind, h->n, h->m, ilqr_args<double>(h, false, false, 1, 0.0), la, ba, fa);
+      frc = ilqr_launch_fused<double>(h->stream, h->model.kind, h->n, h->m, ilqr_args<double>(h, mc), la, ba, fa);
     } else {
       LaneArgs<float> ba{(const float*)h->l_in, (const float*)h->l_term, (float*)h->l_out, (float*)h->l_outn,
                          (const float*)h->l_x0, (float*)h->l_xuy, (float*)h->delta_V, h->status, h->N, h->batch, 0.0f,
                          nullptr, nullptr};
-      frc = ilqr_launch_fused<float>(h->stream, h->model.kind, h->n, h->m, ilqr_args<float>(h, false, false, 1, 0.0), la, ba, fa);
+      frc = ilqr_launch_fused<float>(h->stream, h->model.kind, h->n, h->m, ilqr_args<float>(h, mc), la, ba, fa);
     }
     if (frc) { if (clk) (void)hipFree(clk); return fail(ALTRO_HIP_ERR_HIP, "fused iLQR kernel launch failed"); }
     h->backward_done = true;
@@ -377,11 +389,11 @@ int SolveRun::sweep_head(int iter) {
   int rc = loop(ILK_MARK_RUNNING);
   if (rc) return rc;
   if (al && !hessians_ready) {
-    rc = ilqr_run(h, IK_EXPAND, false, true, 0, 0.0, EXPAND_HESSIAN | (hessian_stored ? diag_mode : 0));
+    rc = ilqr_run(h, call(IK_EXPAND, EXPAND_HESSIAN | (hessian_stored ? diag_mode : 0), h->i_active));
     if (rc) return rc;
     hessian_stored = true;
   }
-  if ((rc = launch_backward(h, 0.0))) return rc;
+  if ((rc = launch_backward(h, 0.0, bwd))) return rc;
   h->backward_done = true;
   for (int attempt = 0; attempt < o.reg_retry_max; ++attempt) {
     const int sr = counted(ILK_REG_RETRY);
@@ -390,7 +402,7 @@ int SolveRun::sweep_head(int iter) {
     if ((rc = verdict(sr, 2, &again))) return rc;
     if (again == 0) break;
     total_reg_retries += again;
-    if ((rc = launch_backward(h, 0.0))) return rc;
+    if ((rc = launch_backward(h, 0.0, bwd))) return rc;
   }
   return o.reg_retry_max > 0 ? loop(ILK_MARK_RUNNING) : 0;
 }
@@ -404,13 +416,11 @@ int SolveRun::first_evaluation(int* prev_slot, int* begin_slot, int* launches, b
     h->spec_no_memory = true;
     pre = false;
   }
-  h->spec_trials = pre ? 2 : 1; h->spec_pre = pre ? 1 : 0;
   // (IK_MERIT2, mode 2: the two-trial evaluation with the broadcasts on the VALU's DPP path and two problems per wave,
   //  kernels/ilqr_merit2_dpp.hip -- with or without constraint blocks)
-  h->aff_store = true;                               // (phi(0): the base of the sweep's affine trials)
-  int rc = dual ? ilqr_run(h, IK_MERIT2, true, true, 1, 0.0, 2) : ilqr_run(h, IK_MERIT, true, true, 1, 0.0);
-  h->aff_store = false;
-  h->spec_trials = 1; h->spec_pre = 0;
+  LoopCall phi0 = merit(dual ? IK_MERIT2 : IK_MERIT, h->i_active, pre ? 2 : 1, AFF_STORE);   // (phi(0): the base of the sweep's affine trials)
+  phi0.spec_pre = pre ? 1 : 0;
+  int rc = ilqr_run(h, phi0);
   if (rc) return rc;
   *launches = 1;
   la.spec_pre = (pre || dual) ? 1 : 0;
@@ -423,19 +433,15 @@ int SolveRun::first_evaluation(int* prev_slot, int* begin_slot, int* launches, b
     // searches that ended WITHOUT the first step (phi' too small, not a descent direction): their candidate is the alpha = 0
     // evaluation's, redone by the single-step kernel for them alone -- launched on their mask whether or not there are any
     // (counted only when there were: the verdict is read with the first round's)
-    int* keep = h->i_active;
-    h->i_active = h->i_spec_refresh;
-    rc = ilqr_run(h, IK_MERIT, true, true, 1, 0.0);
-    h->i_active = keep;
-    if (rc) return rc;
+    if ((rc = ilqr_run(h, merit(IK_MERIT, h->i_spec_refresh)))) return rc;
   } else if (pre) {
-    if ((rc = ilqr_run(h, IK_SPEC_SELECT, false, false, 0, 0.0))) return rc;
+    if ((rc = ilqr_run(h, call(IK_SPEC_SELECT)))) return rc;
     *refreshed = true;
   } else {
     // The first trial step is launched without asking the device whether any problem needs it: the masks make it a no-op when
     // none does, and it saves one host read-back per sweep (these loops are latency-bound).
     // (a rollout like the two-trial pass's second row: the first step is the same bits whichever way the sweep's head runs)
-    if ((rc = ilqr_run(h, IK_MERIT, true, true, 1, 0.0))) return rc;
+    if ((rc = ilqr_run(h, merit(IK_MERIT, h->i_active)))) return rc;
     ++*launches;
     prev = counted(ILK_LS_FEED);
     if (prev < 0) return ALTRO_HIP_ERR_HIP;
@@ -472,28 +478,22 @@ int SolveRun::search_rounds(int* prev_slot, int rounds_last, int* rounds_out, in
       if (trials == 1 && h->spare_count == 0) h->spec_no_memory = true;
     }
     const bool spec = trials > 1;
-    h->spec_trials = trials;
-    la.spec_trials = h->spec_trials;
-    h->aff_round = true;                             // (dynamics as data: the trials of a round are sums over independent knot points)
-    rc = ilqr_run(h, IK_MERIT, true, true, 1, 0.0);
-    h->aff_round = false;
-    if (rc) return rc;
+    la.spec_trials = trials;
+    // (dynamics as data: the trials of a round are sums over independent knot points)
+    if ((rc = ilqr_run(h, merit(IK_MERIT, h->i_active, trials, AFF_ROUND)))) return rc;
     // The decision guard: the trials the last feed would not decide on affine values (IlqrLoopArgs::guard) are evaluated as rollouts,
     // on their own mask.  Not launched when the last verdict read says there are none (the first round of a sweep never has any);
     // launched blind when the host runs ahead of the verdicts -- an empty mask makes it a no-op.
-    if (guard_on && rounds > 0 && (ahead || guarded_last != 0)) {
-      int* keep = h->i_active;
-      h->i_active = h->i_active_exact;
-      rc = ilqr_run(h, IK_MERIT, true, true, 1, 0.0);
-      h->i_active = keep;
-      if (rc) return rc;
-    }
-    la.aff_fed = h->aff_enabled ? 1 : 0;
+    if (guard_on && rounds > 0 && (ahead || guarded_last != 0) && (rc = ilqr_run(h, merit(IK_MERIT, h->i_active_exact, trials)))) return rc;
+    la.aff_fed = aff_enabled ? 1 : 0;
     const int sf = counted(ILK_LS_FEED);
     la.aff_fed = 0;
     if (sf < 0) return ALTRO_HIP_ERR_HIP;
-    if (spec && (rc = ilqr_run(h, IK_SPEC_SELECT, false, false, 0, 0.0))) return rc;
-    h->spec_trials = 1;
+    if (spec) {
+      LoopCall sel = call(IK_SPEC_SELECT);
+      sel.spec_trials = trials;
+      if ((rc = ilqr_run(h, sel))) return rc;
+    }
     la.spec_trials = 1;
     if (ahead) {
       if ((rc = verdict(prev, 0, &searching))) return rc;
@@ -513,19 +513,13 @@ int SolveRun::search_rounds(int* prev_slot, int rounds_last, int* rounds_out, in
 // would have left behind); then the convergence criteria on the accepted candidate, and make it the nominal (solver.cpp:459-469)
 int SolveRun::finish_sweep(bool refreshed, int* fin_slot) {
   int rc = 0;
-  if (refreshed) {
-    int* keep = h->i_active;
-    h->i_active = h->i_spec_refresh;
-    rc = ilqr_run(h, IK_EXPAND, false, true, 0, 0.0, EXPAND_GRADIENT);
-    h->i_active = keep;
-    if (rc) return rc;
-  }
+  if (refreshed && (rc = ilqr_run(h, call(IK_EXPAND, EXPAND_GRADIENT, h->i_spec_refresh)))) return rc;
   if ((rc = loop(ILK_MARK_RUNNING))) return rc;
   // (dual: only the problems whose step was not the one the two-trial pass evaluated -- the skip mask; most waves leave at once)
-  h->stat_skip = dual ? h->i_stat_done : nullptr;
-  rc = ilqr_run(h, IK_STATIONARITY, false, true, 0, 0.0);
-  h->stat_skip = nullptr;
-  if (!rc) rc = ilqr_run(h, IK_ACCEPT, false, true, 0, 0.0);
+  LoopCall stat = call(IK_STATIONARITY, EXPAND_GRADIENT | EXPAND_HESSIAN, h->i_active);
+  stat.stat_skip = dual ? h->i_stat_done : nullptr;
+  rc = ilqr_run(h, stat);
+  if (!rc) rc = ilqr_run(h, call(IK_ACCEPT, EXPAND_GRADIENT | EXPAND_HESSIAN, h->i_active));
   if (rc) return rc;
   *fin_slot = counted(ILK_FINISH_ITER);
   return *fin_slot < 0 ? ALTRO_HIP_ERR_HIP : 0;
@@ -539,20 +533,20 @@ int SolveRun::outer_update() {
   const bool expand_dpp = !form(h, ALTRO_HIP_FORM_EXPAND_LDS), alrows_dpp = !form(h, ALTRO_HIP_FORM_ALROWS_LDS);
   int rc;
   if (tile && expand_dpp && alrows_dpp) {
-    h->expand_penalty_scaling = o.penalty_scaling; h->expand_penalty_max = o.penalty_max;
-    rc = ilqr_run(h, IK_EXPAND, false, true, 0, 0.0, EXPAND_GRADIENT | EXPAND_HESSIAN | EXPAND_NEXT | EXPAND_DUAL | (hessian_stored ? diag_mode : 0));
-    if (rc) return rc;
+    LoopCall c = call(IK_EXPAND, EXPAND_GRADIENT | EXPAND_HESSIAN | EXPAND_NEXT | EXPAND_DUAL | (hessian_stored ? diag_mode : 0), h->i_active);
+    c.penalty_scaling = o.penalty_scaling; c.penalty_max = o.penalty_max;
+    if ((rc = ilqr_run(h, c))) return rc;
     if ((rc = loop(ILK_PENALTY_UPDATE))) return rc;
     hessians_ready = true;
     return 0;
   }
-  if ((rc = ilqr_run(h, IK_DUAL, false, false, 0, 0.0))) return rc;
+  if ((rc = ilqr_run(h, call(IK_DUAL)))) return rc;
   if ((rc = loop(ILK_PENALTY_UPDATE))) return rc;
   // ... and, in the same pass over the constraint rows, the cost Hessians the NEXT sweep's CalcExpansions would form: nothing they
   // depend on (trajectory, duals, penalties) changes between here and there (plan MFMA16, DPP form: gradient for the problems whose
   // duals changed, Hessians for every problem still running)
   const bool merged = tile && expand_dpp;
-  rc = ilqr_run(h, IK_EXPAND, false, true, 0, 0.0, merged ? (EXPAND_GRADIENT | EXPAND_HESSIAN | EXPAND_NEXT | (hessian_stored ? diag_mode : 0)) : EXPAND_GRADIENT);
+  rc = ilqr_run(h, call(IK_EXPAND, merged ? (EXPAND_GRADIENT | EXPAND_HESSIAN | EXPAND_NEXT | (hessian_stored ? diag_mode : 0)) : EXPAND_GRADIENT, h->i_active));
   if (rc) return rc;
   hessians_ready = merged;
   return 0;
@@ -636,9 +630,6 @@ extern "C" int altro_hip_ilqr_solve(altro_hip_batch* h, const altro_hip_solve_op
     h->async_pending = false;
   }
   if ((rc = run.configure(opts)) || (rc = run.ensure_counters()) || (rc = run.choose_path()) || (rc = run.prologue())) return rc;
-  h->spec_trials = 1;
-  h->bwd_active = h->i_active;      // the backward sweep skips problems that have stopped, only inside this call (~SolveRun)
-  h->bwd_reg = run.reg_on ? h->i_reg : nullptr;
   if (run.fused) {
     if ((rc = run.run_fused())) return rc;
     if (run.async) return 0;

@@ -10,7 +10,7 @@ using namespace altro_hip::capi;
 
 namespace {
 
-Tile32Args tile32_args(altro_hip_batch* h, double reg) {
+Tile32Args tile32_args(altro_hip_batch* h, double reg, const BackwardMask& pp) {
   Tile32Args a{};
   auto P = [&](int arr) { return (double*)h->g_arr[arr]; };
   a.A = P(G_A); a.B = P(G_B); a.f = P(G_f); a.Q = P(G_Q); a.R = P(G_R); a.H = P(G_H); a.q = P(G_q); a.r = P(G_r);
@@ -25,7 +25,7 @@ Tile32Args tile32_args(altro_hip_batch* h, double reg) {
   a.N = h->N; a.batch = h->batch; a.n = h->n; a.m = h->m;
   a.reg = reg;
   a.no_f = (h->ilqr_linear || !h->has_f) ? 1 : 0;
-  a.active = h->bwd_active; a.reg_pp = h->bwd_reg;
+  a.active = pp.active; a.reg_pp = pp.reg_pp;
   a.L = tile32_lds_layout(h->n, h->m);
   return a;
 }
@@ -58,12 +58,12 @@ int tile32_backward_dispatch(const Tile32Launch& at, const Tile32Args& a) {
   }
 }
 
-int tile32_launch_backward(altro_hip_batch* h, double reg) {
-  return tile32_backward_dispatch(Tile32Launch{h->stream, h->launch_ev0, h->launch_ev1}, tile32_args(h, reg));
+int tile32_launch_backward(altro_hip_batch* h, double reg, const BackwardMask& pp) {
+  return tile32_backward_dispatch(Tile32Launch{h->stream, h->launch_ev0, h->launch_ev1}, tile32_args(h, reg, pp));
 }
 
 int tile32_launch_forward(altro_hip_batch* h) {
-  const Tile32Args a = tile32_args(h, 0.0);
+  const Tile32Args a = tile32_args(h, 0.0, {});
   const int kc = (h->n + 3) / 4, mc = (h->m + 3) / 4;
 #define T32_CASE(KC_, MC_) if (kc == KC_ && mc == MC_) return forward_launch<KC_, MC_>(h, a);
   T32_CASE(2, 2) T32_CASE(3, 2) T32_CASE(4, 1) T32_CASE(4, 2) T32_CASE(5, 1) T32_CASE(5, 2) T32_CASE(6, 1) T32_CASE(6, 2)

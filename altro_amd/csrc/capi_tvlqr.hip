@@ -19,10 +19,10 @@ using namespace altro_hip::capi;
 namespace {
 
 template <typename T>
-int lane_launch(altro_hip_batch* h, bool backward, double reg) {
+int lane_launch(altro_hip_batch* h, bool backward, double reg, const BackwardMask& pp) {
   LaneArgs<T> a{(const T*)h->l_in, (const T*)h->l_term, (T*)h->l_out, (T*)h->l_outn, (const T*)h->l_x0,
-                (T*)h->l_xuy, (T*)h->delta_V, h->status, h->N, h->batch, (T)reg, backward ? h->bwd_active : nullptr,
-                backward ? h->bwd_reg : nullptr};
+                (T*)h->l_xuy, (T*)h->delta_V, h->status, h->N, h->batch, (T)reg, backward ? pp.active : nullptr,
+                backward ? pp.reg_pp : nullptr};
   const dim3 grid(8 * (((h->batch + 63) / 64 + 7) / 8)), block(64);
   const bool fused = (h->flags & ALTRO_HIP_LANE_FUSED) != 0;
   // (4, 2) and (2, 1): four lanes per problem (kernels/tvlqr_quad_body.inc, tvlqr_quad2_body.inc), same records, bit-identical
@@ -69,7 +69,7 @@ int lane_launch(altro_hip_batch* h, bool backward, double reg) {
 }
 
 template <typename T>
-GenericArgs<T> generic_args(altro_hip_batch* h, double reg) {
+GenericArgs<T> generic_args(altro_hip_batch* h, double reg, const BackwardMask& pp) {
   GenericArgs<T> a;
   for (int i = 0; i < G_NUM; ++i) {
     a.base[i] = (T*)h->g_arr[i];
@@ -91,10 +91,10 @@ GenericArgs<T> generic_args(altro_hip_batch* h, double reg) {
   a.store_q = (h->flags & ALTRO_HIP_STORE_QBLOCKS) ? 1 : 0;
   a.want_y = 1;
   a.no_f = h->ilqr_linear ? 1 : 0;
-  // A solve with the regularisation schedule on (bwd_reg is set for it alone): per-problem reg, and only the problems the mask names --
+  // A solve with the regularisation schedule on (it alone passes reg_pp): per-problem reg, and only the problems the mask names --
   // the running ones at the head of a sweep, the failed ones in a retry (a problem that succeeded has relaxed its reg already and must
   // not be swept with it).  Any other launch is the one it always was: every problem, including those a solve has stopped.
-  if (h->bwd_reg) { a.active = h->bwd_active; a.reg_pp = h->bwd_reg; }
+  if (pp.reg_pp) { a.active = pp.active; a.reg_pp = pp.reg_pp; }
   return a;
 }
 
@@ -136,7 +136,7 @@ struct ProfScope {
 
 
 template <typename S>
-Mfma16Args<S> mfma16_args(altro_hip_batch* h, double reg) {
+Mfma16Args<S> mfma16_args(altro_hip_batch* h, double reg, const BackwardMask& pp) {
   Mfma16Args<S> a;
   a.in = (const S*)h->m_in;
   a.cin = (const S*)h->m_cin;
@@ -146,12 +146,12 @@ Mfma16Args<S> mfma16_args(altro_hip_batch* h, double reg) {
   a.term = (const S*)h->m_term; a.out = (S*)h->m_out; a.outn = (S*)h->m_outn; a.qblk = (S*)h->m_qblk;
   a.trash = (S*)h->m_trash; a.x0 = (const S*)h->x0; a.xuy = (S*)h->m_xuy; a.delta_V = (S*)h->delta_V;
   a.status = h->status; a.N = h->N; a.batch = h->batch; a.reg = reg; a.has_f = h->has_f && !h->ilqr_linear;
-  a.active = h->bwd_active; a.reg_pp = h->bwd_reg;   // set only inside altro_hip_ilqr_solve
+  a.active = pp.active; a.reg_pp = pp.reg_pp;   // (a solve's backward sweep; the forward sweeps pass none)
   return a;
 }
 template <typename S>
-void mfma16_launch_backward(altro_hip_batch* h, double reg, bool sq) {
-  auto a = mfma16_args<S>(h, reg);
+void mfma16_launch_backward(altro_hip_batch* h, double reg, const BackwardMask& pp, bool sq) {
+  auto a = mfma16_args<S>(h, reg, pp);
   const dim3 grid(mf_grid(h->batch)), block(64);
   if (sq && a.has_f) PROF_LAUNCH((mfma16_backward_kernel<true, true, S>), grid, block, 0, h->stream, a);
   else if (sq) PROF_LAUNCH((mfma16_backward_kernel<true, false, S>), grid, block, 0, h->stream, a);
@@ -187,15 +187,15 @@ int mfma16_launch_forward_group(altro_hip_batch* h, const Mfma16Args<double>& a)
 namespace altro_hip {
 namespace capi {
 
-int launch_backward(altro_hip_batch* h, double reg) {
+int launch_backward(altro_hip_batch* h, double reg, const BackwardMask& pp) {
   ProfScope ps(h, 0);
   h->aff_base = false;   // (new gains: altro_hip_merit_affine's stored base is the last sweep's)
   if (h->plan == ALTRO_HIP_PLAN_MFMA16) {
     const bool sq = (h->flags & ALTRO_HIP_STORE_QBLOCKS) != 0;
-    if (h->dtype == ALTRO_HIP_F64) mfma16_launch_backward<double>(h, reg, sq);
-    else if (sq || !(h->flags & ALTRO_HIP_F32_PURE)) mfma16_launch_backward<float>(h, reg, sq);   // fp32 storage, fp64 tiles
+    if (h->dtype == ALTRO_HIP_F64) mfma16_launch_backward<double>(h, reg, pp, sq);
+    else if (sq || !(h->flags & ALTRO_HIP_F32_PURE)) mfma16_launch_backward<float>(h, reg, pp, sq);   // fp32 storage, fp64 tiles
     else {   // opt-in: pure fp32 on v_mfma_f32_16x16x4_f32
-      auto a = mfma16_args<float>(h, reg);
+      auto a = mfma16_args<float>(h, reg, pp);
       // four problems per wave (kernels/tvlqr_mfma16_f32x4.hip) whenever the batch allows it; the one-problem kernel stays for
       // batches that are not whole quads.  Ring depth 2, two waves per SIMD: measured on C4 against (1,2) (1,3) (3,1) (3,2) (4,1) --
       // 3.40 ms against 4.1-4.4 (profiles/r02g_c4_quad_variants.txt); the other instantiations left with round 5's clean-up
@@ -207,9 +207,9 @@ int launch_backward(altro_hip_batch* h, double reg) {
       else PROF_LAUNCH((mfma16_backward_f32_kernel<false, 3>), dim3(mf_grid(h->batch)), dim3(64), 0, h->stream, a);
     }
   } else if (h->plan == ALTRO_HIP_PLAN_LANE) {
-    return h->dtype == ALTRO_HIP_F64 ? lane_launch<double>(h, true, reg) : lane_launch<float>(h, true, reg);
+    return h->dtype == ALTRO_HIP_F64 ? lane_launch<double>(h, true, reg, pp) : lane_launch<float>(h, true, reg, pp);
   } else if (h->g_tile && !h->is_diag) {   // plan MFMA32 (a diagonal cost keeps its diagonals packed: plan GENERIC's own kernel reads those)
-    int rc = tile32_launch_backward(h, reg);
+    int rc = tile32_launch_backward(h, reg, pp);
     if (rc) return rc;
   } else {
     // the knot point's blocks in LDS while they fit; the form without a block for Qxx ("late Q", 3 n^2 instead of 4 n^2 elements) where
@@ -231,7 +231,7 @@ int launch_backward(altro_hip_batch* h, double reg) {
       if (rc) return rc;
     }
     if (f64) {
-      auto a = generic_args<double>(h, reg);
+      auto a = generic_args<double>(h, reg, pp);
       a.ws = (double*)h->g_ws; a.ws_stride = (int64_t)((lds + 15) / 16 * 16 / sizeof(double));
       const dim3 grid(h->batch), blk(64);
       if (h->g_mfma) {   // the products on the matrix cores (ALTRO_HIP_GENERIC_MATRIX_CORES)
@@ -242,7 +242,7 @@ int launch_backward(altro_hip_batch* h, double reg) {
       else if (late_q) PROF_LAUNCH((generic_backward_kernel<double, false, false, true>), grid, blk, lds, h->stream, a);
       else PROF_LAUNCH((generic_backward_kernel<double, false>), grid, blk, lds, h->stream, a);
     } else {
-      auto a = generic_args<float>(h, reg);
+      auto a = generic_args<float>(h, reg, pp);
       a.ws = (float*)h->g_ws; a.ws_stride = (int64_t)((lds + 15) / 16 * 16 / sizeof(float));
       if (big) PROF_LAUNCH((generic_backward_kernel<float, true>), dim3(h->batch), dim3(64), 0, h->stream, a);
       else if (late_q) PROF_LAUNCH((generic_backward_kernel<float, false, false, true>), dim3(h->batch), dim3(64), lds, h->stream, a);
@@ -273,7 +273,7 @@ int launch_forward(altro_hip_batch* h) {
   h->expansion_current = false;   // the sweep writes the candidate trajectory: whatever expansion a merit pass left is not of this point
   if (h->plan == ALTRO_HIP_PLAN_MFMA16) {
     if (h->dtype == ALTRO_HIP_F64) {
-      auto a = mfma16_args<double>(h, 0.0);
+      auto a = mfma16_args<double>(h, 0.0, {});
       if (mfma16_forward_is_group(h)) {
         int rc = mfma16_launch_forward_group(h, a);
         if (rc) return rc;
@@ -281,7 +281,7 @@ int launch_forward(altro_hip_batch* h) {
         mfma16_launch_forward<double>(h, a);
       }
     } else {
-      auto a = mfma16_args<float>(h, 0.0);
+      auto a = mfma16_args<float>(h, 0.0, {});
       if (mfma16_forward_is_x4(h)) {   // pure fp32, four problems per wave (kernels/tvlqr_mfma16_fwd_f32x4.hip)
         const dim3 grid(mf_grid(h->batch / 4));
         // ring depth 2, two waves per SIMD: measured on C4 on two boxes against seven other (depth, waves) pairs and the one-problem
@@ -292,19 +292,19 @@ int launch_forward(altro_hip_batch* h) {
       }
     }
   } else if (h->plan == ALTRO_HIP_PLAN_LANE) {
-    return h->dtype == ALTRO_HIP_F64 ? lane_launch<double>(h, false, 0.0) : lane_launch<float>(h, false, 0.0);
+    return h->dtype == ALTRO_HIP_F64 ? lane_launch<double>(h, false, 0.0, {}) : lane_launch<float>(h, false, 0.0, {});
   } else if (h->g_tile) {
     int rc = tile32_launch_forward(h);
     if (rc) return rc;
   } else if (h->dtype == ALTRO_HIP_F64) {
     // the knot point's blocks staged in LDS and fetched a knot point ahead while sixteen waves still fit a CU (10 KB each: measured at
     // 4096 problems, (13, 4) 1.53 -> 1.21 ms, (16, 4) 1.62 -> 1.27, but (24, 8) at 13 KB 2.37 -> 3.58); else rows from global memory
-    auto a = generic_args<double>(h, 0.0);
+    auto a = generic_args<double>(h, 0.0, {});
     const size_t staged = generic_forward_lds_bytes(h->n, h->m, a.want_y, sizeof(double));
     if (staged <= kGenericForwardStageLimit) PROF_LAUNCH((generic_forward_kernel<double, true>), dim3(h->batch), dim3(64), staged, h->stream, a);
     else PROF_LAUNCH((generic_forward_kernel<double, false>), dim3(h->batch), dim3(64), (size_t)(2 * h->n + h->m) * sizeof(double) + 64, h->stream, a);
   } else {
-    auto a = generic_args<float>(h, 0.0);
+    auto a = generic_args<float>(h, 0.0, {});
     const size_t staged = generic_forward_lds_bytes(h->n, h->m, a.want_y, sizeof(float));
     if (staged <= kGenericForwardStageLimit) PROF_LAUNCH((generic_forward_kernel<float, true>), dim3(h->batch), dim3(64), staged, h->stream, a);
     else PROF_LAUNCH((generic_forward_kernel<float, false>), dim3(h->batch), dim3(64), (size_t)(2 * h->n + h->m) * sizeof(float) + 64, h->stream, a);
@@ -323,7 +323,7 @@ int altro_hip_backward(altro_hip_batch* h, double reg) {
   int rc = check(h);
   if (rc) return rc;
   if (!h->dyn_set || !h->cost_set) return fail(ALTRO_HIP_ERR_NOT_SET, "set_dynamics and set_cost must precede backward");
-  rc = launch_backward(h, reg);
+  rc = launch_backward(h, reg, {});
   if (!rc) h->backward_done = true;
   return rc;
 }
