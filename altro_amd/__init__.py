@@ -33,7 +33,7 @@ C_ABI_SYMBOLS = [
     "altro_hip_stats_reduce", "altro_hip_comm_unique_id", "altro_hip_comm_create", "altro_hip_comm_create_all",
     "altro_hip_comm_destroy", "altro_hip_comm_rank", "altro_hip_comm_world", "altro_hip_comm_device", "altro_hip_stats_allreduce", "altro_hip_stats_allreduce_multi",
     "altro_hip_profile_enable", "altro_hip_profile_reset",
-    "altro_hip_profile_get", "altro_hip_profile_get_range", "altro_hip_profile_dropped", "altro_hip_algorithmic_bytes",
+    "altro_hip_profile_get", "altro_hip_profile_get_range", "altro_hip_profile_dropped", "altro_hip_sweep_variant", "altro_hip_algorithmic_bytes",
     "altro_hip_set_model", "altro_hip_set_model_source", "altro_hip_model_row_layout", "altro_hip_set_tracking_cost", "altro_hip_set_quadratic_cost",
     "altro_hip_set_input_guess", "altro_hip_set_state_guess",
     "altro_hip_open_loop_rollout", "altro_hip_accept", "altro_hip_expand", "altro_hip_merit", "altro_hip_merit_affine",
@@ -59,6 +59,8 @@ FORM_AFFINE_EXACT = 0x8000
 FORM_NO_COMPACTION = 0x10000
 FORM_GENERIC_MERIT_LDS = 0x20000
 FORM_FORWARD_WAVE = 0x40000
+# altro_hip_sweep_variant (ALTRO_HIP_SWEEP_*): which instantiation of plan GENERIC's sweep kernels the last launch was
+SWEEP_LATE_Q, SWEEP_GLOBAL_WORKSPACE, SWEEP_MATRIX_CORES, SWEEP_FORWARD_STAGED = 0x1, 0x2, 0x4, 0x8
 
 
 def forms_from_env():
@@ -205,6 +207,7 @@ def lib():
         L.altro_hip_profile_reset.argtypes = [vp]
         L.altro_hip_profile_get.argtypes = [vp, i, C.POINTER(i), C.POINTER(d), C.POINTER(C.c_char_p)]
         L.altro_hip_profile_get_range.argtypes = [vp, i, C.POINTER(d), C.POINTER(d)]
+        L.altro_hip_sweep_variant.argtypes = [vp, i, C.POINTER(i)]
         L.altro_hip_profile_dropped.argtypes = [vp, i]
         L.altro_hip_algorithmic_bytes.argtypes = [vp, i]
         L.altro_hip_algorithmic_bytes.restype = d
@@ -404,6 +407,12 @@ class Batch:
         n, ms, name = C.c_int(), C.c_double(), C.c_char_p()
         _check(self.L.altro_hip_profile_get(self.h, slot, C.byref(n), C.byref(ms), C.byref(name)))
         return n.value, ms.value, name.value.decode()
+
+    def sweep_variant(self, slot):
+        """altro_hip_sweep_variant: SWEEP_* bits of the instantiation the last backward (slot 0) / forward (slot 1) launch was."""
+        bits = C.c_int()
+        _check(self.L.altro_hip_sweep_variant(self.h, slot, C.byref(bits)))
+        return bits.value
 
     def algorithmic_bytes(self, slot):
         return self.L.altro_hip_algorithmic_bytes(self.h, slot)

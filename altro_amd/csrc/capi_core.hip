@@ -685,6 +685,11 @@ int altro_hip_profile_get(altro_hip_batch* h, int slot, int* launches, double* t
   }
   return 0;
 }
+int altro_hip_sweep_variant(const altro_hip_batch* h, int slot, int* bits) {
+  if (!h || !bits || slot < 0 || slot > 1) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "bad handle, slot or result pointer");
+  *bits = h->sweep_variant[slot];
+  return 0;
+}
 int altro_hip_profile_dropped(altro_hip_batch* h, int slot) {
   if (!h || slot < 0 || slot > 1) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "bad handle or slot");
   return h->prof_dropped[slot];

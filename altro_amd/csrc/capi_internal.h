@@ -122,6 +122,7 @@ struct altro_hip_batch {
   void* g_ws = nullptr;           // plan GENERIC, blocks beyond 64 KB of LDS: the backward sweep's per-problem work blocks (first use)
   bool fwd_quad = false;          // the last LANE forward sweep ran four lanes per problem
   bool bwd_quad = false;          // the last LANE backward sweep ran four lanes per problem (kernels/tvlqr_quad_body.inc)
+  int sweep_variant[2] = {0, 0};  // ALTRO_HIP_SWEEP_* bits of the last backward / forward launch (altro_hip_sweep_variant; sweep_route.h)
   bool spec_no_memory = false;    // the spare trajectories could not be allocated: no speculation on this handle
   ModelParams model{MODEL_LINEAR, 0.0f, 0, 2.7, 1.5};
   bool model_set = false, lqr_cost_set = false, guess_set = false;

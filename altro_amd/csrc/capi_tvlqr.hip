@@ -189,6 +189,7 @@ namespace capi {
 
 int launch_backward(altro_hip_batch* h, double reg, const BackwardMask& pp) {
   ProfScope ps(h, 0);
+  h->sweep_variant[0] = 0;   // (plan GENERIC's own kernel sets its bits below)
   h->aff_base = false;   // (new gains: altro_hip_merit_affine's stored base is the last sweep's)
   if (h->plan == ALTRO_HIP_PLAN_MFMA16) {
     const bool sq = (h->flags & ALTRO_HIP_STORE_QBLOCKS) != 0;
@@ -216,16 +217,10 @@ int launch_backward(altro_hip_batch* h, double reg, const BackwardMask& pp) {
     // that keeps more problems on a CU than the batch otherwise gets, or keeps the blocks in LDS at all; past that the same kernel on a
     // per-problem work block in global memory (n, m beyond ~37 in fp64)
     const bool f64 = h->dtype == ALTRO_HIP_F64;
-    const size_t lds4 = f64 ? generic_backward_lds_bytes<double>(h->n, h->m) : generic_backward_lds_bytes<float>(h->n, h->m);
-    const size_t lds3 = f64 ? generic_backward_lds_bytes<double>(h->n, h->m, true) : generic_backward_lds_bytes<float>(h->n, h->m, true);
-    const auto per_cu = [](size_t lds) { return (int)std::min<size_t>(16, (160 * 1024) / std::max<size_t>(lds, 1)); };   // (16: four waves per SIMD by registers)
-    const int cus = 256;
-    bool late_q = lds4 > kGenericLdsLimit ? lds3 <= kGenericLdsLimit
-                                          : (per_cu(lds3) > per_cu(lds4) && (int64_t)h->batch > (int64_t)cus * per_cu(lds4));
-    if (form(h, ALTRO_HIP_FORM_GENERIC_LATE_Q_ON)) late_q = lds3 <= kGenericLdsLimit;
-    else if (form(h, ALTRO_HIP_FORM_GENERIC_LATE_Q_OFF)) late_q = false;
-    const size_t lds = late_q ? lds3 : lds4;
-    const bool big = lds > kGenericLdsLimit;
+    const GenericBackwardRoute rt = generic_backward_route(h->n, h->m, f64 ? sizeof(double) : sizeof(float), h->batch, h->forms);   // (sweep_route.h)
+    const bool late_q = rt.late_q, big = rt.big;
+    const size_t lds = rt.bytes;
+    h->sweep_variant[0] = rt.variant() | ((f64 && h->g_mfma) ? ALTRO_HIP_SWEEP_MATRIX_CORES : 0);
     if (big && !h->g_ws) {
       int rc = dmalloc(h, &h->g_ws, (size_t)h->batch * ((lds + 15) / 16 * 16));
       if (rc) return rc;
@@ -270,6 +265,7 @@ bool mfma16_forward_is_group(const altro_hip_batch* h) {
 
 int launch_forward(altro_hip_batch* h) {
   ProfScope ps(h, 1);
+  h->sweep_variant[1] = 0;
   h->expansion_current = false;   // the sweep writes the candidate trajectory: whatever expansion a merit pass left is not of this point
   if (h->plan == ALTRO_HIP_PLAN_MFMA16) {
     if (h->dtype == ALTRO_HIP_F64) {
@@ -300,14 +296,16 @@ int launch_forward(altro_hip_batch* h) {
     // the knot point's blocks staged in LDS and fetched a knot point ahead while sixteen waves still fit a CU (10 KB each: measured at
     // 4096 problems, (13, 4) 1.53 -> 1.21 ms, (16, 4) 1.62 -> 1.27, but (24, 8) at 13 KB 2.37 -> 3.58); else rows from global memory
     auto a = generic_args<double>(h, 0.0, {});
-    const size_t staged = generic_forward_lds_bytes(h->n, h->m, a.want_y, sizeof(double));
-    if (staged <= kGenericForwardStageLimit) PROF_LAUNCH((generic_forward_kernel<double, true>), dim3(h->batch), dim3(64), staged, h->stream, a);
-    else PROF_LAUNCH((generic_forward_kernel<double, false>), dim3(h->batch), dim3(64), (size_t)(2 * h->n + h->m) * sizeof(double) + 64, h->stream, a);
+    const GenericForwardRoute rt = generic_forward_route(h->n, h->m, a.want_y, sizeof(double), kGenericForwardStageLimit);   // (sweep_route.h)
+    h->sweep_variant[1] = rt.variant();
+    if (rt.staged) PROF_LAUNCH((generic_forward_kernel<double, true>), dim3(h->batch), dim3(64), rt.bytes, h->stream, a);
+    else PROF_LAUNCH((generic_forward_kernel<double, false>), dim3(h->batch), dim3(64), rt.bytes, h->stream, a);
   } else {
     auto a = generic_args<float>(h, 0.0, {});
-    const size_t staged = generic_forward_lds_bytes(h->n, h->m, a.want_y, sizeof(float));
-    if (staged <= kGenericForwardStageLimit) PROF_LAUNCH((generic_forward_kernel<float, true>), dim3(h->batch), dim3(64), staged, h->stream, a);
-    else PROF_LAUNCH((generic_forward_kernel<float, false>), dim3(h->batch), dim3(64), (size_t)(2 * h->n + h->m) * sizeof(float) + 64, h->stream, a);
+    const GenericForwardRoute rt = generic_forward_route(h->n, h->m, a.want_y, sizeof(float), kGenericForwardStageLimit);
+    h->sweep_variant[1] = rt.variant();
+    if (rt.staged) PROF_LAUNCH((generic_forward_kernel<float, true>), dim3(h->batch), dim3(64), rt.bytes, h->stream, a);
+    else PROF_LAUNCH((generic_forward_kernel<float, false>), dim3(h->batch), dim3(64), rt.bytes, h->stream, a);
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(ALTRO_HIP_ERR_HIP, "forward launch: %s", hipGetErrorString(e));

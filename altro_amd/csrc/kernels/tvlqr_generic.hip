@@ -18,14 +18,14 @@
 #include <stdint.h>
 
 #include "generic_arrays.h"
+#include "../sweep_route.h"
 
 namespace altro_hip {
 
 // Bit-parity with the CPU oracle: no a*b+c -> fma fusion anywhere in this file.
 ALTRO_FP_REGION_OFF
 
-constexpr size_t kGenericLdsLimit = 64 * 1024;   // dynamic LDS a launch gets without asking for more; beyond it plan GENERIC works in global memory
-constexpr size_t kGenericForwardStageLimit = 10 * 1024;   // batched forward sweep: stage the knot point in LDS up to this much per problem (sixteen waves per CU)
+// (kGenericLdsLimit, kGenericForwardStageLimit, the carve sizes and the choice of instantiation: sweep_route.h)
 constexpr int kGenericMaxDim = 256;              // n, m accepted by plan GENERIC (a bound on the work blocks, not of the algorithm)
 
 // (enum GArr: kernels/generic_arrays.h)
@@ -50,7 +50,7 @@ struct GenericArgs {
   int want_y;
   int no_f = 0;              // backward sweep: treat f as zero (altro_hip_batch::ilqr_linear: the expansion of the iLQR loop)
   T* ws = nullptr;           // generic_backward_kernel<T, true>: per-problem work blocks in global memory instead of LDS
-  int64_t ws_stride = 0;     // elements between consecutive problems' work blocks (>= generic_backward_lds_bytes / sizeof(T))
+  int64_t ws_stride = 0;     // elements between consecutive problems' work blocks (>= generic_backward_lds_bytes / sizeof(T), sweep_route.h)
   // backward sweep inside altro_hip_ilqr_solve with the regularisation schedule on (as Mfma16Args / Tile32Args have them); null: every
   // problem, `reg` for all
   const int* active = nullptr;      // [batch] per-problem mask: a problem whose entry is 0 is left exactly as it is
@@ -602,12 +602,6 @@ __global__ __launch_bounds__(64, BIG ? 1 : 4) void generic_backward_kernel(Gener
   }
 }
 
-template <typename T>
-inline size_t generic_backward_lds_bytes(int nm, int mm, bool late_q = false) {
-  size_t el = (size_t)(late_q ? 3 : 4) * nm * nm + (size_t)4 * nm * mm + (size_t)2 * mm * mm + (size_t)5 * nm + (size_t)3 * mm;   // (the carve of generic_backward_kernel)
-  return el * sizeof(T) + 64;
-}
-
 // sum_j M[i + j ld] v[j], j = 0 .. cnt-1, in index order; four matrix entries (global memory) and vector entries (LDS) fetched at a time
 template <typename T>
 __device__ __forceinline__ T gen_row_dot(const T* M, int ld, const T* v, int cnt) {
@@ -623,11 +617,6 @@ __device__ __forceinline__ T gen_row_dot(const T* M, int ld, const T* v, int cnt
   }
   for (; j < cnt; ++j) s += M[j * ld] * v[j];
   return s;
-}
-
-inline size_t generic_forward_lds_bytes(int nm, int mm, int want_y, size_t esz) {   // STAGE = true
-  size_t el = (size_t)3 * nm + mm + (size_t)nm * nm + (size_t)2 * nm * mm + nm + mm + (want_y ? (size_t)nm * nm + nm : 0);
-  return el * esz + 64;
 }
 
 // tvlqr_ForwardPass (tvlqr.cpp:197-248): x_0 = x0; u = d - K x; x+ = f + A x + B u; y = P x + p.

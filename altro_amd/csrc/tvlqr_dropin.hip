@@ -662,12 +662,13 @@ int tvlqr_BackwardPass(const int* nx, const int* nu, int num_horizon, const lqr_
   }
   if (hipMemcpyAsync(w.dev, hs, (size_t)L.group_end[1] * sizeof(double), hipMemcpyHostToDevice, w.stream) != hipSuccess) return TVLQR_NO_DEVICE;
   GenericArgs<double> a = make_args(w, L, reg, is_diag, 0, L.group_end[1]);
-  const size_t lds4 = generic_backward_lds_bytes<double>(a.nmax, a.mmax), lds3 = generic_backward_lds_bytes<double>(a.nmax, a.mmax, true);
-  const bool late_q = lds4 > kGenericLdsLimit && lds3 <= kGenericLdsLimit;   // (the form without a block for Qxx keeps n up to ~37 in LDS)
-  const size_t lds = late_q ? lds3 : lds4;
+  // (the form without a block for Qxx keeps n up to ~37 in LDS: sweep_route.h's rule at a batch of one, no forms)
+  const GenericBackwardRoute rt = generic_backward_route(a.nmax, a.mmax, sizeof(double), 1, 0u);
+  const bool late_q = rt.late_q;
+  const size_t lds = rt.bytes;
   if (late_q) {
     hipLaunchKernelGGL((generic_backward_kernel<double, false, false, true>), dim3(1), dim3(64), lds, w.stream, a);
-  } else if (lds > kGenericLdsLimit) {
+  } else if (rt.big) {
     if (w.big_bytes < lds) {
       if (w.big) (void)hipFree(w.big);
       w.big = nullptr; w.big_bytes = 0;
@@ -786,9 +787,9 @@ int tvlqr_ForwardPass(const int* nx, const int* nu, int num_horizon, const lqr_f
   memcpy(hs + L.total - 4 - L.xstage, x0, sizeof(double) * nx[0]);
   if (hipMemcpyAsync(w.dev, hs, (size_t)L.group_end[2] * sizeof(double), hipMemcpyHostToDevice, w.stream) != hipSuccess) return TVLQR_NO_DEVICE;
   GenericArgs<double> a = make_args(w, L, 0.0, false, y ? 1 : 0, L.group_end[2]);
-  const size_t staged = generic_forward_lds_bytes(a.nmax, a.mmax, a.want_y, sizeof(double));
-  if (staged <= kGenericLdsLimit) hipLaunchKernelGGL((generic_forward_kernel<double, true>), dim3(1), dim3(64), staged, w.stream, a);
-  else hipLaunchKernelGGL((generic_forward_kernel<double, false>), dim3(1), dim3(64), (size_t)(2 * a.nmax + a.mmax) * sizeof(double) + 64, w.stream, a);
+  const GenericForwardRoute frt = generic_forward_route(a.nmax, a.mmax, a.want_y, sizeof(double), kGenericLdsLimit);   // (one problem: stage whatever fits)
+  if (frt.staged) hipLaunchKernelGGL((generic_forward_kernel<double, true>), dim3(1), dim3(64), frt.bytes, w.stream, a);
+  else hipLaunchKernelGGL((generic_forward_kernel<double, false>), dim3(1), dim3(64), frt.bytes, w.stream, a);
   if (hipGetLastError() != hipSuccess) return TVLQR_NO_DEVICE;
   if (hipStreamSynchronize(w.stream) != hipSuccess) return TVLQR_NO_DEVICE;
   for (int k = 0; k <= N; ++k) {

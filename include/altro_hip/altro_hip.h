@@ -598,6 +598,14 @@ int altro_hip_profile_get_range(altro_hip_batch* h, int slot, double* min_ms, do
 /* enable = 2: launches of the slot's kernel issued after the 4096-launch event window was full since the last reset
  * (they ran, but are not part of the totals above); 0 means the averages cover every launch.                        */
 int altro_hip_profile_dropped(altro_hip_batch* h, int slot);
+/* Which instantiation the handle's LAST launch of the slot's kernel was (slot 0 = backward, 1 = forward; 0 before any launch):
+ * ALTRO_HIP_SWEEP_* bits.  altro_hip_profile_get names the kernel; several launchers choose among instantiations of one kernel by
+ * the batch size, the element type or ALTRO_HIP_FORM_* bits, and this says which one ran.  Read-only, no synchronisation.        */
+#define ALTRO_HIP_SWEEP_LATE_Q 0x1           /* generic_backward_kernel: the form without a block for Qxx (3 n^2 elements of LDS)   */
+#define ALTRO_HIP_SWEEP_GLOBAL_WORKSPACE 0x2 /* generic_backward_kernel: per-problem work blocks in global memory instead of LDS    */
+#define ALTRO_HIP_SWEEP_MATRIX_CORES 0x4     /* generic_backward_kernel: the products on the matrix cores                           */
+#define ALTRO_HIP_SWEEP_FORWARD_STAGED 0x8   /* generic_forward_kernel: the knot point's blocks staged in LDS                       */
+int altro_hip_sweep_variant(const altro_hip_batch* h, int slot, int* bits);
 /* Algorithmic bytes one launch of the slot's kernel must move.             */
 double altro_hip_algorithmic_bytes(const altro_hip_batch* h, int slot);
 

@@ -64,8 +64,8 @@ def test_tvlqr_dropin_dimensions_past_32_match_the_oracle():
 
 
 def test_tvlqr_dropin_dimensions_just_past_32_stay_in_lds():
-    """nx = 30..36 per knot point: the blocks of the largest knot point are past 60 KB of LDS in the usual carve and inside it without a
-    block for Qxx (generic_backward_kernel<double, false, false, true>, "late Q"): the same bits as the oracle, scratch blocks included."""
+    """nx = 30..36 per knot point, just past 32: the blocks of the largest knot point (50608 bytes) stay in LDS: the same bits as the
+    oracle, scratch blocks included.  (The form without a block for Qxx, "late Q", is taken past 64 KB: the uniform (40, 10) case below.)"""
     import os
     from oracle import oracle
     oracle.lib()
@@ -74,6 +74,28 @@ def test_tvlqr_dropin_dimensions_just_past_32_stay_in_lds():
                                  extra_link=["-L" + libdir, "-l:" + os.path.basename(oracle._LIB), "-Wl,-rpath," + libdir])
     print(out)
     assert rc == 0 and out.strip().endswith("OK"), out + err
+    assert out.count("bit-identical") == 4
+
+
+@pytest.mark.parametrize("define,variant", [("UNIFORM_40x6", 0), ("UNIFORM_40x10", 1), ("MID_DIMS", 0)])
+def test_tvlqr_dropin_uniform_dimensions_at_the_late_q_seam(define, variant):
+    """tvlqr_BackwardPass at uniform (40, 6) and (40, 10), N = 4, dense and diagonal cost, bit-identical to the oracle like the drop-in's
+    other tests.  The drop-in asks sweep_route.h's rule with a batch of one: (40, 6) still fits 64 KB with a block for Qxx (61264
+    bytes) and keeps that form, as do the per-knot-point dimensions 30..36 above (50608 bytes); (40, 10) does not (67504) and is the
+    drop-in's late-Q launch (ALTRO_HIP_SWEEP_LATE_Q = 1).  What this observes and what it does not: the seam has no handle to ask, so
+    the program evaluates sweep_route.h's rule itself (batch 1, no forms, the dimensions' maxima -- the call tvlqr_dropin.hip makes) and
+    checks that against `variant`; that pins which case the dimensions ARE, it does not see which kernel tvlqr_BackwardPass launched.
+    The launch itself is held by its results: every output array bit for bit the oracle's."""
+    import os
+    from oracle import oracle
+    oracle.lib()
+    libdir = os.path.dirname(oracle._LIB)
+    rc, out, err = cpp_build.run("tvlqr_dropin_varying_test", defines=[define, "EXPECT_LATE_Q=%d" % variant],
+                                 out_name="tvlqr_dropin_seam_%s_test" % define.lower(), include_dirs=["altro_amd/csrc"],
+                                 extra_link=["-L" + libdir, "-l:" + os.path.basename(oracle._LIB), "-Wl,-rpath," + libdir])
+    print(out)
+    assert rc == 0 and out.strip().endswith("OK"), out + err
+    assert "the rule's variant for the drop-in's backward launch %d" % variant in out
     assert out.count("bit-identical") == 4
 
 

@@ -30,19 +30,29 @@ MARGIN = 10.0
 # is 2^-24 off.  The oracle's forward pass fed with its own gains rounded to fp32 reproduces every measured ratio to two digits (19 /
 # 13 / 30 on (12, 4) collinear, 14 / 80 / 25 on (12, 2)), so the kernel's arithmetic adds nothing to it.
 MARGINS = {("mfma16_f32", fam, q): 100.0 for fam, qs in (("collinear", "xuy"), ("unstable", "uy"), ("cheap", "u")) for q in qs}
-Cfg = collections.namedtuple("Cfg", "name shape plan dtype flags kind")
+Cfg = collections.namedtuple("Cfg", "name shape plan dtype flags kind forms", defaults=(0,))
 G, T16, LN, T32 = altro_amd.PLAN_GENERIC, altro_amd.PLAN_MFMA16, altro_amd.PLAN_LANE, altro_amd.PLAN_MFMA32
 F64, F32 = altro_amd.F64, altro_amd.F32
 _id = lambda c: "%s-%dx%d" % ((c.name,) + c.shape)
+LQ_ON = altro_amd.FORM_GENERIC_LATE_Q_ON
+MC = altro_amd.GENERIC_MATRIX_CORES
+GROUP = 16                                           # problems of one workgroup of mfma16_forward_group_kernel
 
-EXACT = [Cfg("generic", s, G, F64, 0, "exact") for s in hc.SHAPES] + [Cfg("lane", s, LN, F64, 0, "exact") for s in hc.LANE_SHAPES]
+# generic_lq, generic_mc_lq, generic_f32_lq: generic_backward_kernel<.., LQ = true> ("late Q"), which the launcher's rule takes from
+# 769 .. 3073 problems up on these shapes (sweep_route.h), forced here at the batches of this file; mfma16_group: the forward sweep of a
+# batch of whole groups of 16 (the batch is padded with the first problems again).  Each run asserts that the instantiation it means ran.
+EXACT = ([Cfg("generic", s, G, F64, 0, "exact") for s in hc.SHAPES] + [Cfg("lane", s, LN, F64, 0, "exact") for s in hc.LANE_SHAPES]
+         + [Cfg("generic_lq", s, G, F64, 0, "exact", LQ_ON) for s in hc.SHAPES])
 REASSOC = ([Cfg("mfma16", s, T16, F64, 0, "f64") for s in hc.TILE_SHAPES] + [Cfg("mfma32", s, T32, F64, 0, "f64") for s in hc.TILE32_SHAPES]
-           + [Cfg("generic_mc", s, G, F64, altro_amd.GENERIC_MATRIX_CORES, "f64") for s in hc.MC_SHAPES]
+           + [Cfg("mfma16_group", s, T16, F64, 0, "f64") for s in hc.TILE_SHAPES]
+           + [Cfg("generic_mc", s, G, F64, MC, "f64") for s in hc.MC_SHAPES]
+           + [Cfg("generic_mc_lq", s, G, F64, MC, "f64", LQ_ON) for s in hc.MC_SHAPES + ((16, 8), (24, 8))]
            + [Cfg("mfma16_f32", s, T16, F32, 0, "mixed") for s in hc.TILE_SHAPES]
            # the two pure-fp32 kernel pairs: one problem per wave (a batch that is no multiple of four) and four problems per wave
            + [Cfg("mfma16_pure", s, T16, F32, altro_amd.F32_PURE, "pure") for s in hc.TILE_SHAPES]
            + [Cfg("mfma16_pure_x4", s, T16, F32, altro_amd.F32_PURE, "pure") for s in hc.TILE_SHAPES])
-OTHER_F32 = [Cfg("lane_f32", s, LN, F32, 0, "f32") for s in hc.LANE_SHAPES] + [Cfg("generic_f32", s, G, F32, 0, "f32") for s in ((13, 4), (20, 8))]
+OTHER_F32 = ([Cfg("lane_f32", s, LN, F32, 0, "f32") for s in hc.LANE_SHAPES] + [Cfg("generic_f32", s, G, F32, 0, "f32") for s in ((13, 4), (20, 8))]
+             + [Cfg("generic_f32_lq", s, G, F32, 0, "f32", LQ_ON) for s in ((13, 4), (20, 8))])
 OUT = ("K", "d", "P", "p", "dV")
 _fx = {}
 
@@ -57,10 +67,40 @@ def x4(cfg):
     return cfg.name.endswith("_x4")
 
 
+def group(cfg):
+    return cfg.name == "mfma16_group"
+
+
+def pad_to(cfg):
+    """The batch of `cfg` is a multiple of this (the kernel under test takes whole quads / whole groups)."""
+    return 4 if x4(cfg) else GROUP if group(cfg) else 1
+
+
+def padded(cfg, pr):
+    """`pr` with the first problems again up to a whole quad / group."""
+    batch, w = pr["A"].shape[0], pad_to(cfg)
+    if batch % w == 0:
+        return pr
+    extra = [i % batch for i in range(w - batch % w)]
+    return hc.stack([pr, hc.take(pr, extra)])
+
+
+def check_variant(cfg, bt, forward):
+    """The instantiation `cfg` names is the one the handle's last launches were (altro_hip_sweep_variant / profile_get)."""
+    if cfg.plan == G:
+        want = (altro_amd.SWEEP_LATE_Q if cfg.forms & LQ_ON else 0) | (altro_amd.SWEEP_MATRIX_CORES if cfg.flags & MC else 0)
+        assert bt.sweep_variant(0) == want, (_id(cfg), bt.sweep_variant(0), want)
+        assert bt.profile_get(0)[2] == "generic_backward_kernel"
+    if forward and cfg.plan == T16 and cfg.dtype == F64:
+        assert bt.profile_get(1)[2] == ("mfma16_forward_group_kernel" if group(cfg) else "mfma16_forward_kernel"), _id(cfg)
+
+
 def open_batch(cfg, pr):
     batch = pr["A"].shape[0]
     bt = altro_amd.Batch(hc.N, pr["n"], pr["m"], batch, dtype=cfg.dtype, plan=cfg.plan, flags=cfg.flags)
     assert bt.plan == cfg.plan
+    if cfg.forms:
+        bt.set_forms(cfg.forms)
     bt.set_dynamics(pr["A"], pr["B"], pr["f"]); bt.set_cost(pr["Q"], pr["R"], pr["H"], pr["q"], pr["r"])
     bt.set_initial_state(pr["x0"])
     return bt
@@ -76,15 +116,15 @@ def fetch(bt, forward):
 
 
 def run(cfg, pr, forward=True):
-    """Backward (and forward) sweep of `pr` on `cfg`; the four-problems-per-wave kernels get a batch of whole quads (the first
-    problems again), of which the caller sees the problems it gave."""
+    """Backward (and forward) sweep of `pr` on `cfg`; the four-problems-per-wave kernels get a batch of whole quads, the group forward
+    kernel one of whole groups (the first problems again), of which the caller sees the problems it gave."""
     batch = pr["A"].shape[0]
-    if x4(cfg) and batch % 4:
-        pr = hc.stack([pr, hc.take(pr, list(range(4 - batch % 4)))])
+    pr = padded(cfg, pr)
     bt = open_batch(cfg, pr)
     bt.backward()
     if forward:
         bt.forward_ltv()
+    check_variant(cfg, bt, forward)
     out = {k: v[:batch] for k, v in fetch(bt, forward).items()}
     bt.close()
     return out
@@ -173,7 +213,7 @@ def test_cost_scale_invariance(cfg):
     assert not bad, bad
 
 
-@pytest.mark.parametrize("cfg", EXACT + REASSOC, ids=_id)
+@pytest.mark.parametrize("cfg", [c for c in EXACT + REASSOC if not group(c)], ids=_id)   # (mfma16_group's backward sweep is mfma16's)
 def test_failure_index_away_from_the_boundary(cfg):
     """One problem of three made to fail at a chosen knot point, its last pivot far below zero (the fixture holds the margins: below
     -1e-3 |Quu| there, above +1e-6 |Quu| everywhere else; nearer the boundary two sound kernels may disagree).  The status is the
@@ -195,6 +235,7 @@ def test_failure_index_away_from_the_boundary(cfg):
         assert (first["status"] == -1).all(), fam
         bt.set_cost(prf["Q"], prf["R"], prf["H"], prf["q"], prf["r"])
         bt.backward()
+        check_variant(cfg, bt, False)
         out = fetch(bt, False)
         bt.close()
         assert out["status"][:batch].tolist() == [kf if i == b else -1 for i in range(batch)], (fam, out["status"])
@@ -236,17 +277,92 @@ def test_neighbours_do_not_see_each_other(cfg):
     badly scaled one must not see it."""
     n, m = cfg.shape
     pr, failing = nine(n, m, fixture(cfg.shape))
-    together = run(cfg, hc.stack([pr, hc.take(pr, [0, 1, 2])]) if x4(cfg) else pr)
+    w = pad_to(cfg)
+    together = run(cfg, padded(cfg, pr))      # (mfma16_group: the nine and the first seven again are ONE group)
     assert together["status"][:9].tolist() == [hc.FAIL_KNOT if i in failing else -1 for i in range(9)] or cfg.kind == "f32"
     for i in range(9):
-        alone = run(cfg, hc.take(pr, [i] * (4 if x4(cfg) else 1)))
-        assert alone["status"][0] == together["status"][i], i
-        st = int(alone["status"][0])                                   # (what lies below a failing knot point was never written)
-        lo, plo = max(st, 0), st + 1
-        for q in ("K", "d"):
-            assert np.array_equal(alone[q][0, lo:], together[q][i, lo:], equal_nan=True), (i, q)
-        for q in ("P", "p"):
-            assert np.array_equal(alone[q][0, plo:], together[q][i, plo:], equal_nan=True), (i, q)
-        if alone["status"][0] == -1:
-            for q in ("dV", "x", "u", "y"):
-                assert np.array_equal(alone[q][0], together[q][i]), (i, q)
+        alone = run(cfg, hc.take(pr, [i] * w))
+        same_as_alone(alone, 0, together, i)
+
+
+def same_as_alone(alone, j, together, i):
+    assert alone["status"][j] == together["status"][i], i
+    st = int(alone["status"][j])                                   # (what lies below a failing knot point was never written)
+    lo, plo = max(st, 0), st + 1
+    for q in ("K", "d"):
+        assert np.array_equal(alone[q][j, lo:], together[q][i, lo:], equal_nan=True), (i, q)
+    for q in ("P", "p"):
+        assert np.array_equal(alone[q][j, plo:], together[q][i, plo:], equal_nan=True), (i, q)
+    if alone["status"][j] == -1:
+        for q in ("dV", "x", "u", "y"):
+            assert np.array_equal(alone[q][j], together[q][i]), (i, q)
+
+
+def test_group_forward_failing_problems_in_the_first_and_last_wave():
+    """Two groups of mfma16_forward_group_kernel; the failing problems sit in wave 0 and wave 15 of the first group, whose other
+    fourteen waves and the whole second group hold hard and benign problems.  Sixteen waves share one LDS ring and one barrier per
+    step: every problem must come out as it does in the wave-per-problem kernel (ALTRO_HIP_FORM_FORWARD_WAVE), bit for bit, and the
+    healthy ones must meet the criterion of this file against the fixture's extended-precision trajectories."""
+    n, m = 12, 4
+    cfg = Cfg("mfma16_group", (n, m), T16, F64, 0, "f64")
+    fx = fixture((n, m))
+    pr, failing = nine(n, m, fx)
+    healthy = [i for i in range(9) if i not in failing]
+    order = [failing[0]] + [healthy[i % 6] for i in range(14)] + [failing[1]] + [healthy[i % 6] for i in range(15)] + [failing[2]]
+    batch = hc.take(pr, order)
+    assert len(order) == 2 * GROUP
+    out = run(cfg, batch)
+    wave = run(cfg._replace(name="mfma16", forms=altro_amd.FORM_FORWARD_WAVE), batch)
+    assert out["status"].tolist() == [hc.FAIL_KNOT if i in failing else -1 for i in order]
+    for j in range(2 * GROUP):
+        same_as_alone(wave, j, out, j)
+    # problems 0 (unstable) and 1 (benign) of the nine sit next to the failing wave 0 and wave 15 and all over the second group: their
+    # trajectories against the fixture's, e_cpu the oracle's stored error on the same fp32-level inputs, floor 1e-13 (fp64 arithmetic)
+    bad = []
+    for fam, i in (("unstable", 0), ("benign", 1)):
+        ref = hc.unpack(fx["ref_%s_s" % fam], n, m)
+        lim = dict(zip(hc.QUANTITIES, np.maximum(fx["e64_%s_s" % fam], 1e-13)))
+        for j in [j for j, o in enumerate(order) if o == i]:
+            errs = {q: hc.blockerr(out[q][j:j + 1], ref[q][0:1]) for q in ("x", "u", "y")}
+            judge(cfg, fam, errs, lim, "slot %d" % j, bad)
+    assert not bad, bad
+
+
+def _lq_twin(cfg):
+    return cfg._replace(name=cfg.name[:-3], forms=0)
+
+
+@pytest.mark.parametrize("cfg", [c for c in OTHER_F32 if c.name == "generic_f32_lq"], ids=_id)
+def test_late_q_fp32_forms_the_same_sums(cfg):
+    """generic_backward_kernel<float, .., LQ = true> promises the sums of the form with a block for Qxx, in the same order: the same
+    bits on every family (fp32 level), status included; and the project's fp32 tolerance, 2e-4 relative, to the oracle on the benign one."""
+    n, m = cfg.shape
+    for fam in hc.FAMILIES:
+        pr = hc.problem(fam, n, m, "s")
+        out, twin = run(cfg, pr), run(_lq_twin(cfg), pr)
+        assert np.array_equal(out["status"], twin["status"]), fam
+        for q in hc.QUANTITIES:
+            assert np.array_equal(out[q], twin[q], equal_nan=True), (fam, q)
+        if fam == "benign":
+            ref = hc.run_oracle(pr)
+            assert (out["status"] == -1).all()
+            for q in hc.QUANTITIES:
+                err = np.abs(out[q] - ref[q]).max() / max(1.0, np.abs(ref[q]).max())
+                print("%-16s benign %s rel err %.3g" % (_id(cfg), q, err))
+                assert err < 2e-4, (q, err)
+
+
+@pytest.mark.parametrize("cfg", [c for c in REASSOC if c.name == "generic_mc_lq"], ids=_id)
+def test_late_q_matrix_cores_against_its_sibling(cfg):
+    """The late-Q form of the matrix-core kernel against the form with a block for Qxx.  With the products on the matrix cores the
+    paired pass (Qx_tmp += P' f, Quu += Qux_tmp B) is two tile products one after the other in both forms (wave_gemm_pair_sel), so
+    late Q changes where Q_k comes from and nothing about any sum: the same bits, on every family.  Printed for DESIGN section 2."""
+    n, m = cfg.shape
+    for fam in hc.FAMILIES:
+        pr = hc.problem(fam, n, m, "d")
+        out, twin = run(cfg, pr), run(_lq_twin(cfg), pr)
+        assert np.array_equal(out["status"], twin["status"]), fam
+        diff = {q: float(np.abs(out[q] - twin[q]).max() / max(np.abs(twin[q]).max(), 1e-300)) for q in hc.QUANTITIES}
+        print("%-16s %-9s bit-identical to generic_mc: %s  (max rel diff %.2g)" % (_id(cfg), fam, all(v == 0 for v in diff.values()), max(diff.values())))
+        for q in hc.QUANTITIES:
+            assert np.array_equal(out[q], twin[q]), (fam, q)
