@@ -34,7 +34,7 @@ C_ABI_SYMBOLS = [
     "altro_hip_comm_destroy", "altro_hip_comm_rank", "altro_hip_comm_world", "altro_hip_comm_device", "altro_hip_stats_allreduce", "altro_hip_stats_allreduce_multi",
     "altro_hip_profile_enable", "altro_hip_profile_reset",
     "altro_hip_profile_get", "altro_hip_profile_get_range", "altro_hip_profile_dropped", "altro_hip_sweep_variant", "altro_hip_algorithmic_bytes",
-    "altro_hip_set_model", "altro_hip_set_model_source", "altro_hip_model_row_layout", "altro_hip_set_tracking_cost", "altro_hip_set_quadratic_cost",
+    "altro_hip_set_model", "altro_hip_set_model_source", "altro_hip_set_time_steps", "altro_hip_get_time_steps", "altro_hip_model_row_layout", "altro_hip_set_tracking_cost", "altro_hip_set_quadratic_cost",
     "altro_hip_set_input_guess", "altro_hip_set_state_guess",
     "altro_hip_open_loop_rollout", "altro_hip_accept", "altro_hip_expand", "altro_hip_merit", "altro_hip_merit_affine",
     "altro_hip_stationarity", "altro_hip_get_nominal", "altro_hip_get_expansion",
@@ -213,6 +213,8 @@ def lib():
         L.altro_hip_algorithmic_bytes.restype = d
         L.altro_hip_set_model.argtypes = [vp, i, C.c_float, i, d, d]
         L.altro_hip_set_model_source.argtypes = [vp, C.c_char_p, C.c_float]
+        L.altro_hip_set_time_steps.argtypes = [vp, vp]
+        L.altro_hip_get_time_steps.argtypes = [vp, vp]
         L.altro_hip_model_row_layout.argtypes = [vp]
         L.altro_hip_set_tracking_cost.argtypes = [vp, vp, vp, vp, vp, i, i]
         L.altro_hip_set_quadratic_cost.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, i]
@@ -424,6 +426,23 @@ class Batch:
     def set_model_source(self, source, timestep):
         """The caller's own continuous dynamics + Jacobian as HIP source (altro_hip_set_model_source), compiled at run time."""
         _check(self.L.altro_hip_set_model_source(self.h, source.encode(), float(timestep)))
+
+    def set_time_steps(self, dt):
+        """altro_hip_set_time_steps: dt[k] (N floats) = the step from knot point k to k + 1 of the handle's device model, shared by the
+        batch (ALTROSolver::SetTimeStep per range); None: the uniform step of set_model / set_model_source again."""
+        if dt is None:
+            _check(self.L.altro_hip_set_time_steps(self.h, None))
+            return
+        a = np.ascontiguousarray(dt, dtype=np.float32)
+        if a.shape != (self.N,):
+            raise ValueError("dt must hold N = %d time steps, got shape %s" % (self.N, a.shape))
+        _check(self.L.altro_hip_set_time_steps(self.h, a.ctypes.data_as(C.c_void_p)))
+
+    def get_time_steps(self):
+        """The N time steps in effect (float32; N copies of the uniform step without an array)."""
+        out = np.zeros(self.N, dtype=np.float32)
+        _check(self.L.altro_hip_get_time_steps(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def set_tracking_cost(self, Qd, Rd, xref, uref, k_stride_zero=False, batch_stride_zero=False):
         keep = [_in(v) for v in (Qd, Rd, xref, uref)]

@@ -3,6 +3,7 @@
 // every per-problem decision is taken on the device (kernels/ilqr_loop_kernels.hip).
 #include "capi_internal.h"
 
+#include <cmath>
 #include <cstring>
 
 using namespace altro_hip;
@@ -462,6 +463,41 @@ int altro_hip_set_model(altro_hip_batch* h, int model, float timestep, int bicyc
                          bicycle_lr > 0 ? bicycle_lr : 1.5};
   h->model_set = true;
   return tile ? model_takes_dynamics(h) : 0;
+}
+
+// ALTROSolver::SetTimeStep per knot-point range (altro_solver.hpp:55) for device models: one float[N] on the device, which every kernel
+// that steps the model at knot point k reads (models.h: ModelParams::hk, model_at)
+int altro_hip_set_time_steps(altro_hip_batch* h, const float* dt) {
+  int rc = loop_entry(h);   // (per-knot-point dimensions: ALTRO_HIP_ERR_UNSUPPORTED, as for altro_hip_set_model)
+  if (rc) return rc;
+  if (!h->model_set)
+    return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_set_time_steps needs a device model (altro_hip_set_model / altro_hip_set_model_source): dynamics "
+                                       "given as data carry their own discretisation");
+  if (!dt) {   // back to the uniform step
+    h->expansion_current = false;
+    h->model.hk = nullptr;
+    return 0;
+  }
+  for (int k = 0; k < h->N; ++k)
+    if (!(std::isfinite(dt[k]) && dt[k] > 0.0f))
+      return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "dt[%d] = %g: every time step must be finite and positive (ErrorCodes::TimestepNotPositive)", k, (double)dt[k]);
+  if (!h->d_hk && (rc = dmalloc(h, (void**)&h->d_hk, (size_t)h->N * sizeof(float)))) return rc;
+  std::vector<float> host(dt, dt + h->N);
+  // (on the handle's own stream: launches already enqueued read the old steps, later ones the new)
+  HIP_TRY(hipMemcpyAsync(h->d_hk, host.data(), (size_t)h->N * sizeof(float), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  h->hk_host.swap(host);
+  h->model.hk = h->d_hk;
+  h->expansion_current = false;
+  return 0;
+}
+int altro_hip_get_time_steps(altro_hip_batch* h, float* dt) {
+  int rc = loop_entry(h);
+  if (rc) return rc;
+  if (!dt) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "dt == NULL");
+  if (!h->model_set) return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_get_time_steps needs a device model (altro_hip_set_model / altro_hip_set_model_source)");
+  for (int k = 0; k < h->N; ++k) dt[k] = h->model.hk ? h->hk_host[k] : h->model.h;
+  return 0;
 }
 
 int altro_hip_set_tracking_cost(altro_hip_batch* h, const double* Qd, const double* Rd, const double* xref,

@@ -125,6 +125,10 @@ struct altro_hip_batch {
   int sweep_variant[2] = {0, 0};  // ALTRO_HIP_SWEEP_* bits of the last backward / forward launch (altro_hip_sweep_variant; sweep_route.h)
   bool spec_no_memory = false;    // the spare trajectories could not be allocated: no speculation on this handle
   ModelParams model{MODEL_LINEAR, 0.0f, 0, 2.7, 1.5};
+  // altro_hip_set_time_steps: the handle's float[N] on the device (allocated on first use) and its host copy; in effect while
+  // model.hk points at it -- altro_hip_set_model / _set_model_source assign a fresh ModelParams, whose hk is null
+  float* d_hk = nullptr;
+  std::vector<float> hk_host;
   bool model_set = false, lqr_cost_set = false, guess_set = false;
   std::vector<double> x0_host;    // the initial state as given, while the handle may still move to another plan (replan_empty_handle)
   int x0_host_bz = 0;

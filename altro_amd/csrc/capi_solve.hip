@@ -210,6 +210,7 @@ int SolveRun::choose_path() {
   if (lane_plan) merit_split_prepare(h);
   const bool fused_can = lane_plan && o.iterations_max > 0 && !h->spec_no_memory && h->merit_split == 1 &&
                          !(h->flags & ALTRO_HIP_LANE_FUSED) && h->model.kind != MODEL_USER &&   // (run-time models: sequenced loop)
+                         !h->model.hk &&   // (altro_hip_set_time_steps: the one-launch kernel steps by the uniform h only)
                          !h->cost_dense &&   // (the one-launch kernel is instantiated for the diagonal cost: a dense one runs sequenced)
                          o.stop_when_running_at_most <= 0;   // (the batch-level early return is the sequenced loop's)
   fused = fused_can && !form(h, ALTRO_HIP_FORM_SEQUENCED);
@@ -218,7 +219,7 @@ int SolveRun::choose_path() {
   if (async) {   // results while the solve runs: only the one-launch path can publish them
     if (!fused || o.fused_sweeps > 0)
       return fail(ALTRO_HIP_ERR_UNSUPPORTED, "altro_hip_ilqr_solve_async needs the one-launch solve kernel (plan LANE with a compiled-in "
-                                             "device model, default environment); use altro_hip_ilqr_solve");
+                                             "device model and a uniform time step, default environment); use altro_hip_ilqr_solve");
     const size_t bytes = (size_t)h->batch * sizeof(IlqrPollRec);
     if (!h->poll_host) {
       if (hipHostMalloc(&h->poll_host, bytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||

@@ -366,6 +366,8 @@ class SolverImpl {
   int device_model = -1, device_frame = 0;
   double device_length = 2.7, device_lr = 1.5;
   altro_hip_batch* dev = nullptr;
+  float dev_h = 0.0f;      // the uniform step the device model was set with
+  bool dev_grid = false;   // the device handle holds a time-step array (altro_hip_set_time_steps)
   ~SolverImpl() { if (dev) altro_hip_batch_destroy(dev); }
   ErrorCodes DeviceSolve();
   // pointer tables handed to the tvlqr_* kernel boundary (solver.cpp:63-106)
@@ -622,8 +624,8 @@ ErrorCodes SolverImpl::DeviceSolve() {
   const int n = data[0].n, m = data[0].m;
   for (int k = 0; k <= N; ++k) {
     const Knot& kp = data[k];
-    if (kp.n != n || (k < N && (kp.m != m || kp.h != data[0].h)))
-      return ALTRO_THROW("SetDeviceModel: the device loop takes one state / input dimension and one time step", ErrorCodes::DimensionMismatch);
+    if (kp.n != n || (k < N && kp.m != m))
+      return ALTRO_THROW("SetDeviceModel: the device loop takes one state / input dimension", ErrorCodes::DimensionMismatch);
     if (kp.cost_kind == CostKind::Generic)
       return ALTRO_THROW("SetDeviceModel: costs must be set as data (SetDiagonalCost / SetQuadraticCost / SetLQRCost)", ErrorCodes::CostNotQuadratic);
     for (const auto& cn : kp.cons)
@@ -638,6 +640,21 @@ ErrorCodes SolverImpl::DeviceSolve() {
   if (fresh) {
     if (altro_hip_batch_create(&dev, N, n, m, 1, ALTRO_HIP_F64, ALTRO_HIP_PLAN_AUTO, 0, 0, nullptr)) { dev = nullptr; return hip_fail("altro_hip_batch_create"); }
     if (altro_hip_set_model(dev, device_model, data[0].h, device_frame, device_length, device_lr)) return hip_fail("altro_hip_set_model");
+    dev_h = data[0].h; dev_grid = false;
+  }
+  {   // SetTimeStep per knot-point range (and between two Solves): the steps as they are NOW.  All equal to the model's own step: no array,
+      // and the handle solves as a uniform one does (plan LANE: in one launch); anything else goes over as the per-knot-point array.
+    bool as_model = true;
+    for (int k = 0; k < N; ++k) as_model = as_model && data[k].h == dev_h;
+    if (!as_model) {
+      std::vector<float> hk(N);
+      for (int k = 0; k < N; ++k) hk[k] = data[k].h;
+      if (altro_hip_set_time_steps(dev, hk.data())) return hip_fail("altro_hip_set_time_steps");
+      dev_grid = true;
+    } else if (dev_grid) {
+      if (altro_hip_set_time_steps(dev, nullptr)) return hip_fail("altro_hip_set_time_steps");
+      dev_grid = false;
+    }
   }
   // the cost, dense (a diagonal cost is its diagonal): [N+1][n*n], [N][m*m], [N][m*n], [N+1][n], [N][m], [N+1]
   std::vector<double> Q((size_t)(N + 1) * n * n, 0.0), R((size_t)N * m * m, 0.0), H((size_t)N * m * n, 0.0), q((size_t)(N + 1) * n, 0.0),

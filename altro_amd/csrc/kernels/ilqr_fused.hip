@@ -151,7 +151,7 @@ __global__ __launch_bounds__((64 * ilqr_fused_waves<n, T>())) void ilqr_fused_sw
     if (w < trials) {
       if (serial && la.active[bi]) {
         const MeritTrial<T> tr = ilqr_merit_trial<T>(am, b, w);
-        if (tr.run) ilqr_merit_roll_lane<KIND, n, m, T, Publish>(am, tr, b0, lane, rowB, Publish{&s_prog[w]});
+        if (tr.run) ilqr_merit_roll_lane<KIND, n, m, T, Publish, false>(am, tr, b0, lane, rowB, Publish{&s_prog[w]});
       }
       Publish{&s_prog[w]}(N + 1);               // (also when no problem of this workgroup takes this step)
     }
@@ -170,7 +170,7 @@ __global__ __launch_bounds__((64 * ilqr_fused_waves<n, T>())) void ilqr_fused_sw
       if (idx < total && validk && la.active[bik]) {
         const int k = idx / trials, trial = idx - k * trials;
         const MeritTrial<T> tr = ilqr_merit_trial<T>(am, bk, trial);
-        if (tr.run) ilqr_merit_point<KIND, n, m, T>(am, bk, k, trial, tr);
+        if (tr.run) ilqr_merit_point<KIND, n, m, T, 0, false>(am, bk, k, trial, tr);
       }
     }
     __syncthreads();
@@ -192,13 +192,13 @@ __global__ __launch_bounds__((64 * ilqr_fused_waves<n, T>())) void ilqr_fused_sw
       la.alpha[bi] = 0.0;
     }
     __syncthreads();
-    if (w == 0 && serial) ilqr_rollout_lane<KIND, n, m, T>(a, b);          // initial rollout on the candidate trajectory
+    if (w == 0 && serial) ilqr_rollout_lane<KIND, n, m, T, false>(a, b);          // initial rollout on the candidate trajectory
     __syncthreads();
     FUSED_FOR_K(true, (ilqr_accept_point<n, m, T>(a, bk, k)));             // ... which becomes the nominal one
     __syncthreads();
     // without constraints the cost Hessian is constant and is written once, here; with them the gradient is formed with
     // the penalty the constraints carry so far and SetPenalty comes after it (solver.cpp:424-430)
-    FUSED_FOR_K(true, (ilqr_expand_point<KIND, n, m, T>(a, bk, k, true, !al)));
+    FUSED_FOR_K(true, (ilqr_expand_point<KIND, n, m, T, 0, false>(a, bk, k, true, !al)));
     __syncthreads();
     if (al && lead) la.prob[bi].rho = la.penalty_initial;                   // ilqr_set_penalty_kernel
     __syncthreads();
@@ -227,7 +227,7 @@ __global__ __launch_bounds__((64 * ilqr_fused_waves<n, T>())) void ilqr_fused_sw
     }
     // CalcExpansions: the cost Hessians change only through the constraints' terms (solver.cpp:448)
     if (al) {
-      FUSED_FOR_K(la.active[bik], (ilqr_expand_point<KIND, n, m, T>(a, bk, k, false, true)));
+      FUSED_FOR_K(la.active[bik], (ilqr_expand_point<KIND, n, m, T, 0, false>(a, bk, k, false, true)));
       __syncthreads();
     }
     lap(0);
@@ -288,7 +288,7 @@ __global__ __launch_bounds__((64 * ilqr_fused_waves<n, T>())) void ilqr_fused_sw
     // steps accepted from a speculative trial carry no phi' pass: redo their expansion (what the derivative pass of a
     // sequential trial would have left behind)
     lap(5);
-    FUSED_FOR_K(la.spec_refresh[bik], (ilqr_expand_point<KIND, n, m, T>(a, bk, k, true, false)));
+    FUSED_FOR_K(la.spec_refresh[bik], (ilqr_expand_point<KIND, n, m, T, 0, false>(a, bk, k, true, false)));
     __syncthreads();
     lap(9);
     // convergence criteria on the accepted candidate, then make it the nominal (solver.cpp:459-469)
@@ -327,7 +327,7 @@ __global__ __launch_bounds__((64 * ilqr_fused_waves<n, T>())) void ilqr_fused_sw
       __syncthreads();
       if (lead) ilqr_penalty_update_body(la, bi);
       __syncthreads();
-      FUSED_FOR_K(la.active[bik], (ilqr_expand_point<KIND, n, m, T>(a, bk, k, true, false)));
+      FUSED_FOR_K(la.active[bik], (ilqr_expand_point<KIND, n, m, T, 0, false>(a, bk, k, true, false)));
       __syncthreads();
     }
     lap(11);

@@ -557,7 +557,7 @@ __global__ __launch_bounds__(64, 4) void generic_merit_kernel(IlqrGenArgs<T> a) 
     }
     } else {
       using M = DiscreteModel<MK, MN, MM, double>;
-      const float h = a.mp.h;
+      const float h = model_at(a.mp, k).h;   // the step of THIS knot point (models.h)
       if (deriv) {   // the two Jacobians zeroed by the whole wave (the evaluating lane then stores what its model knows to be nonzero)
         for (int e = lane; e < MN * (MN + MM); e += 64) { md_J0[e] = 0.0; md_Jm[e] = 0.0; }
         __syncthreads();
@@ -862,7 +862,7 @@ __global__ void generic_model_rollout_kernel(IlqrGenArgs<T> a) {
   for (int k = 0; k < a.N; ++k) {
     for (int e = 0; e < MN; ++e) xo[(int64_t)k * MN + e] = (T)x[e];
     for (int e = 0; e < MM; ++e) u[e] = (double)ui[(int64_t)k * MM + e];
-    M::dynamics(a.mp, x, u, xn);
+    M::dynamics(model_at(a.mp, k), x, u, xn);
     for (int e = 0; e < MN; ++e) x[e] = xn[e];
   }
   for (int e = 0; e < MN; ++e) xo[(int64_t)a.N * MN + e] = (T)x[e];
@@ -878,7 +878,7 @@ __global__ void generic_model_expand_dyn_kernel(IlqrGenArgs<T> a) {
   double x[MN], u[MM], A[MN * MN], B[MN * MM];
   for (int e = 0; e < MN; ++e) x[e] = (double)a.x[(int64_t)b * a.x_bs + (int64_t)k * MN + e];
   for (int e = 0; e < MM; ++e) u[e] = (double)a.u[(int64_t)b * a.u_bs + (int64_t)k * MM + e];
-  M::jacobian(a.mp, x, u, A, B);
+  M::jacobian(model_at(a.mp, k), x, u, A, B);
   T* Ao = const_cast<T*>(a.A) + (int64_t)b * a.A_bs + (int64_t)k * MN * MN;
   T* Bo = const_cast<T*>(a.B) + (int64_t)b * a.B_bs + (int64_t)k * MN * MM;
   for (int e = 0; e < MN * MN; ++e) Ao[e] = (T)A[e];

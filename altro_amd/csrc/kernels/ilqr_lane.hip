@@ -160,7 +160,9 @@ __device__ __forceinline__ void ilqr_cost_hessian(const T* cs, bool terminal, T*
   (void)N; (void)sizeof(D); (void)sizeof(I); (void)sizeof(Mdl)
 
 // x_0 = x0 ; x_{k+1} = f(x_k, u_k) on the candidate trajectory
-template <int KIND, int n, int m, typename T>
+// (GRID, here and below: the step of knot point k is the handle's time-step array's where it has one -- models.h, model_at; false:
+//  the uniform step, what the one-launch solve kernel of ilqr_fused.hip instantiates)
+template <int KIND, int n, int m, typename T, bool GRID = true>
 __device__ __forceinline__ void ilqr_rollout_lane(const IlqrArgs<T>& a, int64_t b) {
   using I = IlqrDims<n, m>;
   using Mdl = DiscreteModel<KIND, n, m, T>;
@@ -172,7 +174,7 @@ __device__ __forceinline__ void ilqr_rollout_lane(const IlqrArgs<T>& a, int64_t 
     T* c = a.cand + (int64_t)k * I::E_CAND * B + b;
     for (int e = 0; e < n; ++e) c[(int64_t)e * B] = x[e];
     for (int e = 0; e < m; ++e) u[e] = c[(int64_t)(2 * n + e) * B];
-    Mdl::dynamics(a.mp, x, u, xn);
+    Mdl::dynamics(model_at<GRID>(a.mp, k), x, u, xn);
     for (int e = 0; e < n; ++e) x[e] = xn[e];
   }
   T* c = a.cand + (int64_t)N * I::E_CAND * B + b;
@@ -220,7 +222,7 @@ __global__ void ilqr_accept_kernel(IlqrArgs<T> a) {
 
 // Expansion at the candidate point of ONE knot point: A, B (f = 0), lxx/luu/lux, lx, lu -> the backward pass's input
 // record.  Independent in k: the reference's own TODO ("do this in parallel", solver.cpp:190).
-template <int KIND, int n, int m, typename T, int CK = 0>
+template <int KIND, int n, int m, typename T, int CK = 0, bool GRID = true>
 __device__ __forceinline__ void ilqr_expand_point(const IlqrArgs<T>& a, int64_t b, int k, bool grad, bool hess) {
   using D = LaneDims<n, m>;
   using I = IlqrDims<n, m, CK>;
@@ -267,7 +269,7 @@ __device__ __forceinline__ void ilqr_expand_point(const IlqrArgs<T>& a, int64_t 
   T* in = a.in + (int64_t)k * D::E_IN * B + b;
   if (grad) {
     T Am[n * n], Bm[n * m];
-    Mdl::jacobian(a.mp, x, u, Am, Bm);
+    Mdl::jacobian(model_at<GRID>(a.mp, k), x, u, Am, Bm);
     for (int e = 0; e < n * n; ++e) in[(int64_t)(D::O_A + e) * B] = Am[e];
     for (int e = 0; e < n * m; ++e) in[(int64_t)(D::O_B + e) * B] = Bm[e];
     for (int e = 0; e < n; ++e) in[(int64_t)(D::O_f + e) * B] = T(0);
@@ -360,8 +362,9 @@ __device__ __forceinline__ void merit_step(const MeritRec<n, m, T, CK>& r, const
 #pragma unroll
   for (int e = 0; e < m; ++e) lane_st<T>(bc, lane, (uint32_t)(2 * n + e) * rowB, u[e]);
   T Am[n * n], Bm[n * m];
-  if (deriv) Mdl::step(a.mp, x, u, xn, Am, Bm);
-  else Mdl::dynamics(a.mp, x, u, xn);
+  const ModelParams mpk = model_at(a.mp, k);
+  if (deriv) Mdl::step(mpk, x, u, xn, Am, Bm);
+  else Mdl::dynamics(mpk, x, u, xn);
   T lx[n], lu[m];
   ilqr_cost_gradient<n, m, CK, T>(r.cs, x, u, false, lx, lu);
   T Jk = ilqr_cost_value<n, m, CK, T>(r.cs, x, u, false);
@@ -570,7 +573,7 @@ __device__ __forceinline__ void roll_load(RollRec<n, m, T>& r, const IlqrArgs<T>
 // other group of the loop and once at the end (c = N + 1), tells a consumer that knot points 0 .. c - 1 are stored (the
 // fused solve kernel evaluates their per-knot-point terms in other waves while the rollout goes on).
 struct RollNoPublish { __device__ __forceinline__ void operator()(int) const {} };
-template <int KIND, int n, int m, typename T, class Pub = RollNoPublish>
+template <int KIND, int n, int m, typename T, class Pub = RollNoPublish, bool GRID = true>
 __device__ __forceinline__ void ilqr_merit_roll_lane(const IlqrArgs<T>& a, const MeritTrial<T>& tr, int64_t b0, uint32_t lane,
                                                      uint32_t rowB, const Pub& pub = Pub()) {
   using I = IlqrDims<n, m>;
@@ -606,7 +609,7 @@ __device__ __forceinline__ void ilqr_merit_roll_lane(const IlqrArgs<T>& a, const
     for (int e = 0; e < n; ++e) lane_st<T>(bc, lane, (uint32_t)e * rowB, x[e]);
 #pragma unroll
     for (int e = 0; e < m; ++e) lane_st<T>(bc, lane, (uint32_t)(2 * n + e) * rowB, u[e]);
-    Mdl::dynamics(a.mp, x, u, xn);
+    Mdl::dynamics(model_at<GRID>(a.mp, k), x, u, xn);
     for (int e = 0; e < n; ++e) x[e] = xn[e];
   };
   int k = 0;
@@ -634,7 +637,7 @@ __global__ __launch_bounds__(64) void ilqr_merit_roll_kernel(IlqrArgs<T> a) {
 }
 
 // everything of MeritFunction at ONE knot point of a rolled-out trial (solver.cpp:286-332 without the two recursions)
-template <int KIND, int n, int m, typename T, int CK = 0>
+template <int KIND, int n, int m, typename T, int CK = 0, bool GRID = true>
 __device__ __forceinline__ void ilqr_merit_point(const IlqrArgs<T>& a, int64_t b, int k, int trial, const MeritTrial<T>& tr) {
   using D = LaneDims<n, m>;
   using I = IlqrDims<n, m, CK>;
@@ -670,7 +673,7 @@ __device__ __forceinline__ void ilqr_merit_point(const IlqrArgs<T>& a, int64_t b
     if (al) Jk += al_eval<n, m, T, true, false>(a.al, k, b, B, x, u, false, rho, rho, lx, lu, nullptr, nullptr, nullptr, nullptr, false);
     if (tr.deriv) {
       T Am[n * n], Bm[n * m];
-      Mdl::jacobian(a.mp, x, u, Am, Bm);
+      Mdl::jacobian(model_at<GRID>(a.mp, k), x, u, Am, Bm);
       T* j = jd.p + (int64_t)k * jd.E * B + b;
       for (int e = 0; e < n * n; ++e) j[(int64_t)(jd.oA + e) * B] = Am[e];
       for (int e = 0; e < n * m; ++e) j[(int64_t)(jd.oB + e) * B] = Bm[e];

@@ -669,10 +669,11 @@ __global__ __launch_bounds__(64, ((MK != 0 || (AL && DENSE && sizeof(S) == 8)) ?
 #pragma unroll
       for (int c = 0; c < 16; ++c) cR[c] = 0.0;
     } else if constexpr (MK != 0) {   // a device model: x+ = F(x, u), and row j of Z = [A B] at (x, u) where phi' is wanted
+      const ModelParams mpk = model_at(a.mp, kc);            // (kc: a padding pass of the ring stays inside the time-step array)
       if (DUAL || deriv) {
-        tile_model_step<MK, true>(a.mp, w, jr, xn, cR);
+        tile_model_step<MK, true>(mpk, w, jr, xn, cR);
       } else {
-        tile_model_step<MK, false>(a.mp, w, jr, xn, cR);
+        tile_model_step<MK, false>(mpk, w, jr, xn, cR);
 #pragma unroll
         for (int c = 0; c < 16; ++c) cR[c] = 0.0;
       }

@@ -378,7 +378,8 @@ __device__ __forceinline__ void r32_gather_inputs(const R32Vec& v, double* ul) {
   if constexpr (NU > 4) r32_gather4<11, -1, NU - 4>(v.hi, ul + 4);
 }
 // One explicit-midpoint step (test_utils.cpp:84-132) from the half's [x; u] (vw: states at positions 0.., input e at 31 - e): state
-// lane ix gets x+_ix and, with JAC, row ix of [A_k B_k] (lanes without a state compute row 0 along and must not use it).
+// lane ix gets x+_ix and, with JAC, row ix of [A_k B_k] (lanes without a state compute row 0 along and must not use it).  `mp`: the model's
+// parameters at the step's knot point (models.h, model_at).
 template <int MK, int NX, int NU, bool JAC>
 __device__ __forceinline__ void r32_model_step(const ModelParams& mp, const R32Vec& vw, double own, int ix, double& xnext, double (&zrow)[NX + NU]) {
   using M = DiscreteModel<MK, NX, NU, double>;
@@ -555,7 +556,7 @@ __global__ __launch_bounds__(64, WPS) void row32_merit_kernel(IlqrGenArgs<T> a) 
     if constexpr (MK != 0) {   // the model at this knot point's [x; u]; with the derivative the state lanes' rows of [A_k B_k] into the image
       if (deriv) {
         double zrow[NX + NU];
-        r32_model_step<MK, NX, NU, true>(a.mp, vw, x, ix, xmodel, zrow);
+        r32_model_step<MK, NX, NU, true>(model_at(a.mp, k), vw, x, ix, xmodel, zrow);
         if (isx) {
 #pragma unroll
           for (int c = 0; c < NX; ++c) Lw[oAm + ix + c * NX] = zrow[c];
@@ -573,7 +574,7 @@ __global__ __launch_bounds__(64, WPS) void row32_merit_kernel(IlqrGenArgs<T> a) 
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       } else {
         double unused[NX + NU];
-        r32_model_step<MK, NX, NU, false>(a.mp, vw, x, ix, xmodel, unused);
+        r32_model_step<MK, NX, NU, false>(model_at(a.mp, k), vw, x, ix, xmodel, unused);
       }
       gAw += sA; gBw += sB;
     }
@@ -693,7 +694,7 @@ __global__ __launch_bounds__(64, 1) void row32_expand_dyn_kernel(IlqrGenArgs<T> 
   const double w = isx ? (double)a.x[(int64_t)b * a.x_bs + (int64_t)k * NX + ix] : (isu ? (double)a.u[(int64_t)b * a.u_bs + (int64_t)k * NU + iu] : 0.0);
   const R32Vec vw = r32_spread(w, upper_row);
   double xn, zrow[NX + NU];
-  r32_model_step<MK, NX, NU, true>(a.mp, vw, w, ix, xn, zrow);
+  r32_model_step<MK, NX, NU, true>(model_at(a.mp, k), vw, w, ix, xn, zrow);   // (k: the half's own knot point)
   if (ok_own && isx) {
     T* Ao = const_cast<T*>(a.A) + (int64_t)b * a.A_bs + (int64_t)k * NX * NX + ix;
     T* Bo = const_cast<T*>(a.B) + (int64_t)b * a.B_bs + (int64_t)k * NX * NU + ix;

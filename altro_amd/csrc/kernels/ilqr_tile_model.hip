@@ -74,7 +74,8 @@ __device__ __forceinline__ void tile_cont(const ModelParams& mp, const double* x
 }
 
 // One explicit-midpoint step of model MK from the row's registers: lane j < 12 gets x+_j and, with JAC, row j of Z = [A B] of the
-// step (lanes 12..15 compute along as row 11 and must not use either).  Must be called by every lane of the row.
+// step (lanes 12..15 compute along as row 11 and must not use either).  Must be called by every lane of the row.  `mp`: the
+// model's parameters at the step's knot point (models.h, model_at).
 template <int MK, bool JAC>
 __device__ __forceinline__ void tile_model_step(const ModelParams& mp, double w, int jr, double& xnext, double (&zrow)[16]) {
   double z[16];
@@ -133,7 +134,7 @@ __global__ __launch_bounds__(64) void wave_rollout_model_kernel(IlqrWaveArgs<S> 
     unext = (double)candb[(size_t)(k + 1 < a.N ? k + 1 : k) * a.xuy_ks + 12 + j];
     if (on && isx) candb[(size_t)k * a.xuy_ks + j] = (S)x;
     double xn, unused[16];
-    tile_model_step<MK, false>(mp, w, jr, xn, unused);
+    tile_model_step<MK, false>(model_at(mp, k), w, jr, xn, unused);
     x = xn;
   }
   if (on && isx) candb[(size_t)a.N * a.xuy_ks + j] = (S)x;
@@ -159,7 +160,7 @@ __global__ __launch_bounds__(64) void wave_expand_dyn_kernel(IlqrWaveArgs<S> a) 
   const S* c = a.cand + (size_t)b * a.xuy_bs + (size_t)k * a.xuy_ks;
   const double w = isx ? (double)c[j] : (double)c[12 + j];
   double xn, zrow[16];
-  tile_model_step<MK, true>(mp, w, jr, xn, zrow);
+  tile_model_step<MK, true>(model_at(mp, k), w, jr, xn, zrow);
   if (on && isx) {
     S* z = const_cast<S*>(a.dyn) + (size_t)b * a.dyn_bs + (size_t)k * a.dyn_ks;
 #pragma unroll

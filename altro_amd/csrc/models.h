@@ -34,11 +34,32 @@ enum ModelKind { MODEL_LINEAR = 0, MODEL_DOUBLE_INTEGRATOR = 1, MODEL_PENDULUM =
 
 struct ModelParams {
   int kind;
-  float h;         // time step (uniform)
+  float h;         // time step (uniform; with `hk`: the step of the knot point the struct was taken at, see model_at)
   int frame;       // bicycle: 0 CoG, 1 rear, 2 front
   double length;   // bicycle wheel base (2.7)
   double lr;       // bicycle CoG -> rear axle (1.5)
+  // altro_hip_set_time_steps: hk[k] = the step from knot point k to k + 1, one float[N] on the device shared by the batch
+  // (ALTROSolver::SetTimeStep(h, k_start, k_stop), altro_solver.hpp:55; KnotPointData holds one h per knot point) -- or null: `h` everywhere
+  const float* hk = nullptr;
 };
+
+// The model's parameters AT knot point k: what every kernel that steps a model at k hands the functions below, which read `h`
+// and nothing else of the grid.  k is the same for a whole wave wherever a wave walks the horizon, so the read goes through the
+// constant address space like the constraint tables (kernels/al_types.h): one scalar load, and from there on the arithmetic is
+// that of a uniform handle -- a handle without the array and one whose array is constant run the same instructions on the same
+// values.  GRID = false (the one-launch solve kernel, kernels/ilqr_fused.hip, which serves uniform handles only): `mp` as it is.
+template <bool GRID = true>
+ALTRO_HD ModelParams model_at(const ModelParams& mp, int k) {
+  ModelParams q = mp;
+  if constexpr (GRID) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (mp.hk) q.h = ((const float __attribute__((address_space(4)))*)mp.hk)[k];
+#else
+    if (mp.hk) q.h = mp.hk[k];
+#endif
+  }
+  return q;
+}
 
 // sin and cos of one argument with a single range reduction on the device.  (A hand-written fp64 evaluation -- Cody-Waite
 // reduction as a double-double, fdlibm kernels, 0.78 ulp worst case over [-2^20, 2^20] -- was measured against the library

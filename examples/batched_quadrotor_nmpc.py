@@ -4,10 +4,16 @@ altro_amd/csrc/models.h; thrust and three body torques) fly a moving set-point u
 are a device model (altro_hip_set_model on plan MFMA16): every rollout, merit evaluation and expansion steps the model on the
 GPU in the tile plan's row layout, the backward sweeps are the benchmarked matrix-core kernel.
 
-    python examples/batched_quadrotor_nmpc.py [batch] [steps] [sweeps-per-step]
+    python examples/batched_quadrotor_nmpc.py [batch] [steps] [sweeps-per-step] [--source] [--time-grid FINE:COARSE]
 
 `sweeps-per-step` caps iLQR sweeps per MPC step (real-time iteration; default 3): a batch waits for its slowest problem, and a
 receding-horizon controller re-plans 50 times a second anyway.
+
+`--time-grid FINE:COARSE` (FINE + 4 COARSE = 40) runs the same 0.8 s look-ahead a second time on FINE steps of h followed by COARSE
+steps of 4 h (altro_hip_set_time_steps; ALTROSolver::SetTimeStep per knot-point range) -- FINE + COARSE knot points instead of 40 --
+and prints its time per NMPC step and closed-loop tracking error next to the uniform run's.  The grid is relative to "now": it does
+not move with the horizon, and such a run warm-starts from the previous plan as it is (one knot point of the coarse tail is four
+plant steps: there is no whole-knot shift).
 """
 import os
 import sys
@@ -37,13 +43,12 @@ def plant(x, u, h):   # explicit midpoint, like the solver's discretisation (tes
     return x + h * f_cont(x + 0.5 * h * f_cont(x, u), u)
 
 
-def main():
-    argv = [a for a in sys.argv if not a.startswith("--")]
-    batch = int(argv[1]) if len(argv) > 1 else 4096
-    steps = int(argv[2]) if len(argv) > 2 else 50
-    sweeps = int(argv[3]) if len(argv) > 3 else 3
-    from_source = "--source" in sys.argv          # the same model handed over as HIP source (altro_hip_set_model_source: hiprtc)
-    N, n, m, h = 40, 12, 4, 0.02
+def run(batch, steps, sweeps, from_source, grid=None):
+    """One closed-loop run; grid = (fine, coarse) knot points of h and 4 h, or None: 40 of h.  -> (ms per step, mean position error)"""
+    n, m, h = 12, 4, 0.02
+    N = 40 if grid is None else grid[0] + grid[1]
+    hk = np.full(N, h) if grid is None else np.concatenate([np.full(grid[0], h), np.full(grid[1], 4 * h)])
+    tk = np.concatenate([[0.0], np.cumsum(hk)])   # knot point k lies tk[k] ahead of "now"
     hover = np.array([MASS * GRAV, 0.0, 0.0, 0.0])
     Qd = np.concatenate([np.full(3, 4.0), np.full(3, 1.0), np.full(3, 0.5), np.full(3, 0.1)])
     Rd = np.array([0.05, 20.0, 20.0, 20.0])
@@ -61,7 +66,9 @@ def main():
         bt.set_model_source(QUADROTOR_SRC, np.float32(h))
     else:
         bt.set_model(altro_amd.MODEL_QUADROTOR, np.float32(h))
-    xref = np.stack([goal(k * h) for k in range(N + 1)])
+    if grid is not None:
+        bt.set_time_steps(hk.astype(np.float32))
+    xref = np.stack([goal(tk[k]) for k in range(N + 1)])
     Q = np.tile(Qd, (1, N + 1, 1)); Q[0, N] *= 10.0
     bt.set_tracking_cost(Q, np.tile(Rd, (1, N, 1)), xref[None], np.tile(hover, (1, N, 1)), batch_stride_zero=True)
     G = np.zeros((2 * m, n + m)); G[:m, n:] = np.eye(m); G[m:, n:] = -np.eye(m)
@@ -71,7 +78,7 @@ def main():
     bt.set_initial_state(x)
     bt.set_input_guess(hover[None, None], k_stride_zero=True, batch_stride_zero=True)
 
-    t_solve = 0.0
+    t_solve, err_sum = 0.0, 0.0
     for t in range(steps):
         t0 = time.perf_counter()
         res = bt.ilqr_solve(iterations_max=(20 if t == 0 else sweeps), tol_stationarity=1e-3, use_backtracking=True)
@@ -80,18 +87,42 @@ def main():
             t_solve += dt
         _, u = bt.get_knot(0)
         x = plant(x, u, h)
+        err = np.linalg.norm(x[:, :3] - goal((t + 1) * h)[:3], axis=1)
+        err_sum += err.mean()
         if t % 10 == 0 or t == steps - 1:
-            err = np.linalg.norm(x[:, :3] - goal((t + 1) * h)[:3], axis=1)
             print("step %3d: %.2f ms, %5d/%d converged, sweeps %d, thrust in [%.2f, %.2f], max |tau| %.3f, position error mean %.3f max %.3f"
                   % (t, dt * 1e3, int((res["status"] == 0).sum()), batch, res["sweeps"], u[:, 0].min(), u[:, 0].max(), np.abs(u[:, 1:]).max(),
                      err.mean(), err.max()))
-        xr = np.stack([goal((t + 1 + k) * h) for k in range(N + 1)])
+        xr = np.stack([goal((t + 1) * h + tk[k]) for k in range(N + 1)])
         Qk = np.tile(Qd, (N + 1, 1)); Qk[N] *= 10.0
         bt.update_linear_costs(-(Qk * xr)[None], None, (0.5 * (Qk * xr * xr).sum(1))[None], 0, N, batch_stride_zero=True)
         bt.set_initial_state(x)
-        bt.shift_trajectory()
-    print("%d NMPC steps x %d quadrotors (n=12, m=4, N=%d, h=%.2f, <= %d sweeps per step): %.2f ms per step in the solver (%.0f solves/s)"
-          % (steps - 1, batch, N, h, sweeps, t_solve / (steps - 1) * 1e3, (steps - 1) * batch / t_solve))
+        if grid is None:
+            bt.shift_trajectory()
+    print("%d NMPC steps x %d quadrotors (n=12, m=4, N=%d, %s, <= %d sweeps per step): %.2f ms per step in the solver (%.0f solves/s)"
+          % (steps - 1, batch, N, "h=%.2f" % h if grid is None else "%d steps of %.2f + %d of %.2f" % (grid[0], h, grid[1], 4 * h), sweeps,
+             t_solve / (steps - 1) * 1e3, (steps - 1) * batch / t_solve))
+    bt.close()
+    return t_solve / (steps - 1) * 1e3, err_sum / steps
+
+
+def main():
+    argv = [a for i, a in enumerate(sys.argv) if not a.startswith("--") and (i == 0 or sys.argv[i - 1] != "--time-grid")]
+    batch = int(argv[1]) if len(argv) > 1 else 4096
+    steps = int(argv[2]) if len(argv) > 2 else 50
+    sweeps = int(argv[3]) if len(argv) > 3 else 3
+    from_source = "--source" in sys.argv          # the same model handed over as HIP source (altro_hip_set_model_source: hiprtc)
+    grid = None
+    if "--time-grid" in sys.argv:
+        fine, coarse = (int(v) for v in sys.argv[sys.argv.index("--time-grid") + 1].split(":"))
+        if fine < 1 or coarse < 0 or fine + 4 * coarse != 40:
+            sys.exit("--time-grid FINE:COARSE needs FINE + 4 COARSE = 40 (the uniform run's look-ahead), e.g. 8:8 or 12:7")
+        grid = (fine, coarse)
+    ms_u, err_u = run(batch, steps, sweeps, from_source)
+    if grid is not None:
+        ms_g, err_g = run(batch, steps, sweeps, from_source, grid)
+        print("uniform 40 x h: %.2f ms per NMPC step, mean position error %.4f | grid %d x h + %d x 4h (%d knot points): %.2f ms per NMPC step, "
+              "mean position error %.4f" % (ms_u, err_u, grid[0], grid[1], grid[0] + grid[1], ms_g, err_g))
 
 
 if __name__ == "__main__":

@@ -259,6 +259,25 @@ int altro_hip_set_model(altro_hip_batch* h, int model, float timestep, int bicyc
  * (ALTRO_HIP_ERR_UNSUPPORTED) unless the handle was created with ALTRO_HIP_TILE_USER_BLOCKS (fp64 records): then it takes the
  * source and an AUTO handle stays on the tile.  A source that defines only one of the pair is ALTRO_HIP_ERR_BAD_ARGUMENT.   */
 int altro_hip_set_model_source(altro_hip_batch* h, const char* source, float timestep);
+/* ALTROSolver::SetTimeStep(h, k_start, k_stop) (altro_solver.hpp:55) for the batched path: one time step PER KNOT POINT.  dt is a
+ * host array of N floats, dt[k] = the step from knot point k to k + 1 -- the `float h` the reference hands its dynamics callbacks
+ * (typedefs.hpp:31-35) -- shared by the batch and kept as one float[N] on the handle's device.  Every kernel that steps the model at
+ * knot point k (rollout, expansion, merit evaluation) reads dt[k] in the place of the uniform `timestep`; a constant array gives the
+ * bits of the uniform handle.  Valid after altro_hip_set_model / altro_hip_set_model_source on every plan that takes a device model
+ * (LANE, MFMA16 with fp64 records, GENERIC / MFMA32 in the row layout and the wave-per-problem kernels).
+ *   dt == NULL                         back to the uniform step of altro_hip_set_model; a later altro_hip_set_model / _set_model_source
+ *                                      clears the array too
+ *   an entry not finite or not > 0     ALTRO_HIP_ERR_BAD_ARGUMENT, nothing is written
+ *   no device model                    ALTRO_HIP_ERR_NOT_SET: dynamics given as data (altro_hip_set_dynamics) carry their own
+ *                                      discretisation, there is no step to set for them
+ *   per-knot-point dimensions          ALTRO_HIP_ERR_UNSUPPORTED, like altro_hip_set_model
+ * One grid per handle: there are no per-problem time steps.  altro_hip_shift_trajectory and altro_hip_shift_duals do NOT move the
+ * array: the grid is relative to "now", like the cost's knot points (after a shift, knot point k still steps by dt[k]).
+ * Plan LANE's one-launch solve kernel does not read the array: altro_hip_ilqr_solve of a handle with one runs the launch-sequenced
+ * loop (as a model from source does), and altro_hip_ilqr_solve_async / _poll answer ALTRO_HIP_ERR_UNSUPPORTED for it.
+ * altro_hip_get_time_steps returns the N steps in effect (N copies of the uniform step on a handle without an array).             */
+int altro_hip_set_time_steps(altro_hip_batch* h, const float* dt);
+int altro_hip_get_time_steps(altro_hip_batch* h, float* dt);
 /* Plans GENERIC / MFMA32: 1 when the handle's device model (compiled in, or the caller's source) runs the loop's ROW-LAYOUT model kernels
  * (kernels/ilqr_row32.hip: two problems per wave, every lane evaluates the model -- plan MFMA32's shapes), 0 when it runs the
  * wave-per-problem ones.  A model from source gets the row layout when hiprtc compiled those kernels without scratch memory (a sparse

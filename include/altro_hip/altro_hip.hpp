@@ -80,6 +80,10 @@ class BatchSolver {
   }
   // SetExplicitDynamics with the caller's own continuous model as HIP source, compiled at run time (altro_hip_set_model_source)
   void SetModelSource(const char* source, float timestep) { Check(altro_hip_set_model_source(h_, source, timestep)); }
+  // ALTROSolver::SetTimeStep per knot-point range for the device model: dt[k] (N floats) = the step from knot point k to k + 1, shared by
+  // the batch; nullptr: the uniform step of SetModel / SetModelSource again (altro_hip_set_time_steps)
+  void SetTimeSteps(const float* dt) { Check(altro_hip_set_time_steps(h_, dt)); }
+  void GetTimeSteps(float* dt) { Check(altro_hip_get_time_steps(h_, dt)); }
   // whether the device model runs the loop's row-layout model kernels (plans GENERIC / MFMA32; altro_hip_model_row_layout)
   bool ModelRowLayout() const { return altro_hip_model_row_layout(h_) != 0; }
   void SetInitialState(const double* x0, bool shared_over_batch = false) {
