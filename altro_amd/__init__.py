@@ -34,7 +34,8 @@ C_ABI_SYMBOLS = [
     "altro_hip_comm_destroy", "altro_hip_comm_rank", "altro_hip_comm_world", "altro_hip_comm_device", "altro_hip_stats_allreduce", "altro_hip_stats_allreduce_multi",
     "altro_hip_profile_enable", "altro_hip_profile_reset",
     "altro_hip_profile_get", "altro_hip_profile_get_range", "altro_hip_profile_dropped", "altro_hip_sweep_variant", "altro_hip_algorithmic_bytes",
-    "altro_hip_set_model", "altro_hip_set_model_source", "altro_hip_set_time_steps", "altro_hip_get_time_steps", "altro_hip_model_row_layout", "altro_hip_set_tracking_cost", "altro_hip_set_quadratic_cost",
+    "altro_hip_set_model", "altro_hip_set_model_source", "altro_hip_set_model_source_params", "altro_hip_set_model_params", "altro_hip_get_model_params",
+    "altro_hip_model_num_params", "altro_hip_set_time_steps", "altro_hip_get_time_steps", "altro_hip_model_row_layout", "altro_hip_set_tracking_cost", "altro_hip_set_quadratic_cost",
     "altro_hip_set_input_guess", "altro_hip_set_state_guess",
     "altro_hip_open_loop_rollout", "altro_hip_accept", "altro_hip_expand", "altro_hip_merit", "altro_hip_merit_affine",
     "altro_hip_stationarity", "altro_hip_get_nominal", "altro_hip_get_expansion",
@@ -213,6 +214,10 @@ def lib():
         L.altro_hip_algorithmic_bytes.restype = d
         L.altro_hip_set_model.argtypes = [vp, i, C.c_float, i, d, d]
         L.altro_hip_set_model_source.argtypes = [vp, C.c_char_p, C.c_float]
+        L.altro_hip_set_model_source_params.argtypes = [vp, C.c_char_p, C.c_float, i]
+        L.altro_hip_set_model_params.argtypes = [vp, vp, i]
+        L.altro_hip_get_model_params.argtypes = [vp, vp]
+        L.altro_hip_model_num_params.argtypes = [vp]
         L.altro_hip_set_time_steps.argtypes = [vp, vp]
         L.altro_hip_get_time_steps.argtypes = [vp, vp]
         L.altro_hip_model_row_layout.argtypes = [vp]
@@ -423,9 +428,33 @@ class Batch:
     def set_model(self, model, timestep, frame=0, length=2.7, lr=1.5):
         _check(self.L.altro_hip_set_model(self.h, model, float(timestep), frame, length, lr))
 
-    def set_model_source(self, source, timestep):
-        """The caller's own continuous dynamics + Jacobian as HIP source (altro_hip_set_model_source), compiled at run time."""
-        _check(self.L.altro_hip_set_model_source(self.h, source.encode(), float(timestep)))
+    def set_model_source(self, source, timestep, num_params=0):
+        """The caller's own continuous dynamics + Jacobian as HIP source (altro_hip_set_model_source), compiled at run time.
+        num_params > 0 (altro_hip_set_model_source_params): the source's functions take `const T* p`, that many per-problem
+        parameters, which set_model_params must supply before anything steps the model."""
+        if num_params == 0:
+            _check(self.L.altro_hip_set_model_source(self.h, source.encode(), float(timestep)))
+        else:
+            _check(self.L.altro_hip_set_model_source_params(self.h, source.encode(), float(timestep), int(num_params)))
+
+    def set_model_params(self, theta):
+        """altro_hip_set_model_params: theta [batch, P] -- or [P], one set for every problem."""
+        a = np.ascontiguousarray(theta, dtype=np.float64)
+        P = self.model_num_params
+        if P and a.shape not in ((self.batch, P), (P,)):   # (P = 0: the library says what is missing)
+            raise ValueError("theta must have shape (%d, %d) or (%d,), got %s" % (self.batch, P, P, a.shape))
+        _check(self.L.altro_hip_set_model_params(self.h, a.ctypes.data_as(C.c_void_p), int(a.ndim == 1)))
+
+    def get_model_params(self):
+        """The stored parameters, widened to float64: [batch, P]."""
+        out = np.zeros((self.batch, self.model_num_params), dtype=np.float64)
+        _check(self.L.altro_hip_get_model_params(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    @property
+    def model_num_params(self):
+        """Per-problem parameters the handle's model from source takes (0: none)."""
+        return int(self.L.altro_hip_model_num_params(self.h))
 
     def set_time_steps(self, dt):
         """altro_hip_set_time_steps: dt[k] (N floats) = the step from knot point k to k + 1 of the handle's device model, shared by the

@@ -78,6 +78,7 @@ AlTable<T> al_table(const altro_hip_batch* h) {
   t.knots = h->al_d_knots; t.big = h->al_d_big; t.G = (const T*)h->al_d_G; t.g = (const T*)h->al_d_g; t.z = (T*)h->al_d_z; t.enabled = h->al_defs.empty() ? 0 : 1;
   t.uniform = h->al_sum.uniform; t.rows_per_knot = h->al_sum.rows_per_knot; t.N = h->N; t.G_count = h->al_sum.G_count; t.Gpad = (const T*)h->al_d_Gpad; t.Gpad_count = h->al_sum.Gpad_count;
   t.all_sel = h->al_sum.all_sel; t.has_soc = h->al_sum.has_soc; t.gsel = h->al_d_gsel; t.max_ncon = h->al_sum.max_ncon; t.guser = h->al_d_guser;
+  t.theta = (const T*)h->model.theta; t.theta_bs = h->batch;   // (altro_hip_set_model_params; null without)
   return t;
 }
 
@@ -412,6 +413,9 @@ int ilqr_check(altro_hip_batch* h, bool need_guess) {
   if (!h->lqr_cost_set) return fail(ALTRO_HIP_ERR_NOT_SET, "neither altro_hip_set_tracking_cost nor altro_hip_set_quadratic_cost has been called");
   if (!h->x0_set) return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_set_initial_state has not been called");
   if (need_guess && !h->guess_set) return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_set_input_guess has not been called");
+  // a source with per-problem parameters has no default for them (a mass of 0 divides): nothing steps the model before the setter
+  if (h->model_set && h->model.kind == MODEL_USER && h->model_np > 0 && !h->model.theta)
+    return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_set_model_params has not been called: the handle's source takes %d per-problem parameters", h->model_np);
   return 0;
 }
 
@@ -451,6 +455,7 @@ int altro_hip_set_model(altro_hip_batch* h, int model, float timestep, int bicyc
                                              "ALTRO_HIP_MODEL_QUADROTOR13 at (13, 4)", model, altro_hip_batch_plan(h), h->n, h->m);
     if (h->dtype != ALTRO_HIP_F64) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "device models on plans GENERIC / MFMA32 run on fp64 handles");
     h->model = ModelParams{model, timestep, 0, 2.7, 1.5};
+    model_params_drop(h);
     h->model_set = true;
     return model_takes_dynamics(h);
   }
@@ -461,6 +466,7 @@ int altro_hip_set_model(altro_hip_batch* h, int model, float timestep, int bicyc
     return fail(ALTRO_HIP_ERR_UNSUPPORTED, "no device model %d for plan %d with (n, m) = (%d, %d)", model, h->plan, h->n, h->m);
   h->model = ModelParams{model, timestep, bicycle_frame, bicycle_length > 0 ? bicycle_length : 2.7,
                          bicycle_lr > 0 ? bicycle_lr : 1.5};
+  model_params_drop(h);
   h->model_set = true;
   return tile ? model_takes_dynamics(h) : 0;
 }

@@ -129,6 +129,13 @@ struct altro_hip_batch {
   // model.hk points at it -- altro_hip_set_model / _set_model_source assign a fresh ModelParams, whose hk is null
   float* d_hk = nullptr;
   std::vector<float> hk_host;
+  // altro_hip_set_model_source_params / _set_model_params: the source's parameter count (0: none), the handle's [P][batch] array on the
+  // device in its element type (allocated by the first setter) and what it holds, widened, [batch][P]; in effect while model.theta points
+  // at it.  altro_hip_set_model / _set_model_source / _set_model_source_params drop all three (model_params_drop).
+  int model_np = 0;
+  void* d_theta = nullptr;
+  size_t d_theta_bytes = 0;
+  std::vector<double> theta_host;
   bool model_set = false, lqr_cost_set = false, guess_set = false;
   std::vector<double> x0_host;    // the initial state as given, while the handle may still move to another plan (replan_empty_handle)
   int x0_host_bz = 0;
@@ -204,6 +211,18 @@ inline int dmalloc(altro_hip_batch* h, void** p, size_t bytes) {
   }
   h->device_bytes += bytes;
   return 0;
+}
+
+// a new model: the parameters of the last one go (the array is sized by ITS count); launches in flight may still read them
+inline void model_params_drop(altro_hip_batch* h) {
+  if (h->d_theta) {
+    (void)hipStreamSynchronize(h->stream);
+    (void)hipFree(h->d_theta);
+    h->device_bytes -= h->d_theta_bytes;
+  }
+  h->d_theta = nullptr; h->d_theta_bytes = 0; h->model_np = 0;
+  h->model.theta = nullptr; h->model.theta_bs = 0;
+  h->theta_host.clear();
 }
 
 inline int check(altro_hip_batch* h) {

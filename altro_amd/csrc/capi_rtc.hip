@@ -11,6 +11,8 @@
 // fused kernel is not compiled at run time: it is the library's longest compile).
 #include "capi_internal.h"
 
+#include <cmath>
+#include <cstring>
 #include <dlfcn.h>
 #include <hip/hiprtc.h>
 
@@ -185,12 +187,13 @@ static int rtc_build(altro_hip_batch* h, const RtcUnit& unit, const std::string&
   return 0;
 }
 // the lane and tile kinds' units from a handle
-static int rtc_lane_module(altro_hip_batch* h, const std::string& source, int ck, RtcModule** out) {
-  return rtc_build(h, rtc_unit_lane(h->n, h->m, h->dtype == ALTRO_HIP_F64 ? "double" : "float", ck, source), source, out);
+// (np: the source's per-problem parameters, altro_hip_batch::model_np once the source is the handle's)
+static int rtc_lane_module(altro_hip_batch* h, const std::string& source, int ck, int np, RtcModule** out) {
+  return rtc_build(h, rtc_unit_lane(h->n, h->m, h->dtype == ALTRO_HIP_F64 ? "double" : "float", ck, source, np), source, out);
 }
 // (ck: altro_hip_batch::rtc_ck, the bits of loop_route.h: route_tile_module_key)
 static int rtc_tile_module(altro_hip_batch* h, int ck, RtcModule** out) {
-  return rtc_build(h, rtc_unit_tile(h->n, h->m, ck & 1, (ck >> 1) & 1, h->rtc_source, (ck >> 2) & 1, (ck >> 3) & 1), h->rtc_source, out);
+  return rtc_build(h, rtc_unit_tile(h->n, h->m, ck & 1, (ck >> 1) & 1, h->rtc_source, (ck >> 2) & 1, (ck >> 3) & 1, h->model_np), h->rtc_source, out);
 }
 // The handle's module for the shape's route (once per operation, before its first step from the module).  Plan MFMA16: blocks, a dense cost, a
 // third slot or a slot from the source came or went since the module was built; plan LANE: the handle's cost changed kind -- the
@@ -201,7 +204,7 @@ int rtc_current(altro_hip_batch* h, const RouteShape& s) {
   const int ck = s.plan == ALTRO_HIP_PLAN_LANE ? (s.cost_dense ? 1 : 0) : route_tile_module_key(s);
   if (h->rtc && h->rtc_ck == ck) return 0;
   RtcModule* m2 = nullptr;
-  if (const int rc = s.plan == ALTRO_HIP_PLAN_LANE ? rtc_lane_module(h, h->rtc_source, ck, &m2) : rtc_tile_module(h, ck, &m2)) return rc;
+  if (const int rc = s.plan == ALTRO_HIP_PLAN_LANE ? rtc_lane_module(h, h->rtc_source, ck, h->model_np, &m2) : rtc_tile_module(h, ck, &m2)) return rc;
   h->rtc = m2; h->rtc_ck = ck;
   return 0;
 }
@@ -219,9 +222,8 @@ int rtc_step(altro_hip_batch* h, const RouteStep& st, const void* args) {
 }  // namespace capi
 }  // namespace altro_hip
 
-extern "C" {
-
-int altro_hip_set_model_source(altro_hip_batch* h, const char* source, float timestep) {
+// altro_hip_set_model_source (num_params = 0) and altro_hip_set_model_source_params: the same path, the unit's makers take the count
+static int set_model_source(altro_hip_batch* h, const char* source, float timestep, int num_params) {
   int rc = loop_entry(h);
   if (rc) return rc;
   h->expansion_current = false;
@@ -246,8 +248,9 @@ int altro_hip_set_model_source(altro_hip_batch* h, const char* source, float tim
       return fail(ALTRO_HIP_ERR_UNSUPPORTED, "run-time compiled models on plan GENERIC take n, m <= 32 (got %d, %d)", h->n, h->m);
     h->rtc_source = src;
     h->model = ModelParams{MODEL_USER, timestep, 0, 2.7, 1.5};
+    model_params_drop(h); h->model_np = num_params;
     RtcModule* gm = nullptr;   // compile now: a source that does not build must fail HERE, with the compiler's log
-    if ((rc = rtc_build(h, rtc_unit_generic(h->n, h->m, tile32_shape_ok(h->n, h->m), src), src, &gm))) { h->rtc_source.clear(); h->model = ModelParams{MODEL_LINEAR, 0.0f, 0, 2.7, 1.5}; return rc; }
+    if ((rc = rtc_build(h, rtc_unit_generic(h->n, h->m, tile32_shape_ok(h->n, h->m), src, num_params), src, &gm))) { h->rtc_source.clear(); h->model = ModelParams{MODEL_LINEAR, 0.0f, 0, 2.7, 1.5}; h->model_np = 0; return rc; }
     h->model_set = true; h->rtc_has_constraints = c_val && c_jac;
     h->rtc = gm; h->rtc_row32_ok = gm->row_ok;
     return model_takes_dynamics(h);
@@ -262,11 +265,12 @@ int altro_hip_set_model_source(altro_hip_batch* h, const char* source, float tim
                                              "and plan LANE; plan MFMA16 takes the model's two functions and linear blocks (altro_hip_add_linear_constraint)");
     h->rtc_source = src;
     h->model = ModelParams{MODEL_USER, timestep, 0, 2.7, 1.5};
+    model_params_drop(h); h->model_np = num_params;
     RtcModule* tm = nullptr;   // compile now: a source that does not build must fail HERE, with the compiler's log
-    if (!h->al_defs.empty() && (rc = al_upload(h))) { h->rtc_source.clear(); h->model = ModelParams{MODEL_LINEAR, 0.0f, 0, 2.7, 1.5}; return rc; }   // (al_sum.max_ncon: the slots of the blocks so far)
+    if (!h->al_defs.empty() && (rc = al_upload(h))) { h->rtc_source.clear(); h->model = ModelParams{MODEL_LINEAR, 0.0f, 0, 2.7, 1.5}; h->model_np = 0; return rc; }   // (al_sum.max_ncon: the slots of the blocks so far)
     const bool user = !h->al_defs.empty() && h->al_sum.has_user;   // (a source that replaces one whose blocks the handle still has)
     if (user && !c_val) {
-      h->rtc_source.clear(); h->model = ModelParams{MODEL_LINEAR, 0.0f, 0, 2.7, 1.5};
+      h->rtc_source.clear(); h->model = ModelParams{MODEL_LINEAR, 0.0f, 0, 2.7, 1.5}; h->model_np = 0;
       return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "the handle has constraint blocks from source (altro_hip_add_user_constraint): the new source must define "
                                               "altro_user_constraint and altro_user_constraint_jacobian, or altro_hip_clear_constraints must come first");
     }
@@ -274,20 +278,78 @@ int altro_hip_set_model_source(altro_hip_batch* h, const char* source, float tim
     //  handle with such a block launches, at the width of the blocks registered so far; rtc_tile_current builds another if it turns out otherwise)
     const bool expect_user = user || (tile_user && c_val);
     const int ck = ((h->al_defs.empty() && !expect_user) ? 0 : 1) | (h->cost_dense ? 2 : 0) | ((!h->al_defs.empty() && h->al_sum.max_ncon > AL_MAXC) ? 4 : 0) | (expect_user ? 8 : 0);
-    if ((rc = rtc_tile_module(h, ck, &tm))) { h->rtc_source.clear(); return rc; }
+    if ((rc = rtc_tile_module(h, ck, &tm))) { h->rtc_source.clear(); h->model_np = 0; return rc; }
     h->rtc = tm; h->rtc_ck = ck; h->model_set = true; h->rtc_has_constraints = tile_user && c_val && c_jac;
     return model_takes_dynamics(h);
   }
   RtcModule* m = nullptr;
   const int ck = h->cost_dense ? 1 : 0;
-  if ((rc = rtc_lane_module(h, src, ck, &m))) return rc;   // (altro_hip_last_error has the compiler's log)
+  if ((rc = rtc_lane_module(h, src, ck, num_params, &m))) return rc;   // (altro_hip_last_error has the compiler's log)
   h->rtc = m; h->rtc_ck = ck; h->rtc_source = src;
   h->rtc_has_constraints = c_val && c_jac;
   h->model = ModelParams{MODEL_USER, timestep, 0, 2.7, 1.5};
+  model_params_drop(h); h->model_np = num_params;
   h->model_set = true;
   return 0;
 }
 
+extern "C" {
+
+int altro_hip_set_model_source(altro_hip_batch* h, const char* source, float timestep) { return set_model_source(h, source, timestep, 0); }
+
+int altro_hip_set_model_source_params(altro_hip_batch* h, const char* source, float timestep, int num_params) {
+  if (num_params < 0 || num_params > ALTRO_HIP_MODEL_MAX_PARAMS)
+    return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "num_params = %d: a model from source takes 0 .. ALTRO_HIP_MODEL_MAX_PARAMS = %d per-problem parameters",
+                num_params, ALTRO_HIP_MODEL_MAX_PARAMS);
+  return set_model_source(h, source, timestep, num_params);
+}
+
+// The per-problem parameters of the handle's source (ModelParams::theta, AlTable::theta): host [batch][P] in, [P][batch] in the handle's
+// element type on the device -- what std::function callbacks closing over each solver's own constants are in the reference (typedefs.hpp:31-53)
+int altro_hip_set_model_params(altro_hip_batch* h, const double* theta, int batch_stride_zero) {
+  int rc = loop_entry(h);
+  if (rc) return rc;
+  const int P = h->model_np;
+  if (!h->model_set || h->model.kind != MODEL_USER || P == 0)
+    return fail(ALTRO_HIP_ERR_NOT_SET, "altro_hip_set_model_params needs a model from source with parameters (altro_hip_set_model_source_params, num_params > 0)");
+  if (!theta) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "theta == NULL");
+  const size_t B = (size_t)h->batch;
+  const bool f64 = h->dtype == ALTRO_HIP_F64;
+  for (size_t e = 0; e < (batch_stride_zero ? 1 : B) * P; ++e)
+    if (!std::isfinite(theta[e]) || (!f64 && !std::isfinite((float)theta[e])))   // (fp32 handles: finite in the element type)
+      return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "theta[%zu][%zu] = %g: every model parameter must be finite", e / P, e % P, theta[e]);
+  const size_t esz = f64 ? sizeof(double) : sizeof(float), bytes = (size_t)P * B * esz;
+  std::vector<double> kept(B * P);          // [batch][P], as stored: converted once to the element type, widened
+  std::vector<char> dev(bytes);             // [P][batch] in the element type
+  for (size_t b = 0; b < B; ++b)
+    for (int i = 0; i < P; ++i) {
+      const double v = theta[(batch_stride_zero ? 0 : b * P) + i];
+      if (f64) { ((double*)dev.data())[(size_t)i * B + b] = v; kept[b * P + i] = v; }
+      else { const float f = (float)v; ((float*)dev.data())[(size_t)i * B + b] = f; kept[b * P + i] = (double)f; }
+    }
+  if (!h->d_theta) {
+    if ((rc = dmalloc(h, &h->d_theta, bytes))) return rc;
+    h->d_theta_bytes = bytes;
+  }
+  // (on the handle's own stream: launches already enqueued read the old values, later ones the new)
+  HIP_TRY(hipMemcpyAsync(h->d_theta, dev.data(), bytes, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  h->theta_host.swap(kept);
+  h->model.theta = h->d_theta; h->model.theta_bs = h->batch;
+  h->expansion_current = false;
+  return 0;
+}
+int altro_hip_get_model_params(altro_hip_batch* h, double* theta) {
+  int rc = loop_entry(h);
+  if (rc) return rc;
+  if (!h->model_set || h->model.kind != MODEL_USER || h->model_np == 0 || !h->model.theta)
+    return fail(ALTRO_HIP_ERR_NOT_SET, h->model_np ? "altro_hip_set_model_params has not been called"
+                                                   : "the handle's model takes no parameters (altro_hip_set_model_source_params, num_params > 0)");
+  if (!theta) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "theta == NULL");
+  std::memcpy(theta, h->theta_host.data(), h->theta_host.size() * sizeof(double));
+  return 0;
+}
+int altro_hip_model_num_params(const altro_hip_batch* h) { return (h && h->model_set && h->model.kind == MODEL_USER) ? h->model_np : 0; }
 int altro_hip_model_row_layout(const altro_hip_batch* h) { return (h && row32_model_eligible(route_shape(h))) ? 1 : 0; }
 
 }  // extern "C"

@@ -166,8 +166,9 @@ __device__ __forceinline__ T al_eval(const AlTable<T>& t, int k, int64_t b, int6
       T uu[m];
 #pragma unroll
       for (int e = 0; e < m; ++e) uu[e] = terminal ? T(0) : u[e];
-      altro_user_constraint<T>(uid - 1, x, uu, cuser);
-      altro_user_constraint_jacobian<T>(uid - 1, x, uu, Guser);
+      AL_USER_P_DECL(T, t, b);
+      altro_user_constraint<T>(uid - 1, x, uu, AL_USER_P cuser);
+      altro_user_constraint_jacobian<T>(uid - 1, x, uu, AL_USER_P Guser);
     }
 #endif
     if (cone != CONE_SOC && kn.sel[j]) {

@@ -93,7 +93,24 @@ struct AlTable {
   // plan GENERIC: per block definition the caller's constraint id + 1 (AlDef::user), 0 for c = G [x;u] - g -- or null when the handle
   // has no such block.  Read only by the kernels compiled around a source that defines them (kernels/ilqr_generic.hip: GEN_USER_BLOCKS).
   const int* guser = nullptr;
+  // altro_hip_set_model_params: the handle's per-problem parameters (ModelParams::theta, models.h), [P][theta_bs = batch] -- what the
+  // caller's constraint pair gets as `p`.  Read only under ALTRO_HIP_USER_NP, i.e. in units compiled at run time; else null and dead.
+  const T* theta = nullptr;
+  int theta_bs = 0;
 };
+#if defined(ALTRO_HIP_USER_NP)
+// problem b's parameters into registers, and the caller's constraint pair with or without them: one spelling at the three call sites
+template <typename T>
+__device__ __forceinline__ void al_theta(const AlTable<T>& t, int64_t b, T (&p)[ALTRO_HIP_USER_NP]) {
+#pragma unroll
+  for (int i = 0; i < ALTRO_HIP_USER_NP; ++i) p[i] = t.theta[(int64_t)i * t.theta_bs + b];
+}
+#define AL_USER_P_DECL(T, t, b) T al_p_[ALTRO_HIP_USER_NP]; al_theta<T>(t, b, al_p_)
+#define AL_USER_P al_p_,
+#else
+#define AL_USER_P_DECL(T, t, b) (void)0
+#define AL_USER_P
+#endif
 #define ALTRO_CONST_AS __attribute__((address_space(4)))
 // table entry and dual-row shift for knot point k
 template <typename T>

@@ -169,8 +169,8 @@ __device__ __forceinline__ int gen_uid(const AlTable<T>& t, int def) {   // the 
 }
 // the knot point's image (all lanes; barriers inside when the knot point has a user block -- the table says so, wave-uniformly)
 template <typename T>
-__device__ __forceinline__ void gen_user_stage(const AlTable<T>& t, const AlKnotBig ALTRO_CONST_AS& kn, int n, int m, const double* xs,
-                                               const double* us, bool terminal, int lane) {
+__device__ __forceinline__ void gen_user_stage(const AlTable<T>& t, const AlKnotBig ALTRO_CONST_AS& kn, int b, int n, int m,
+                                               const double* xs, const double* us, bool terminal, int lane) {
   bool any = false;
   for (int c = 0; c < kn.ncon; ++c) any = any || gen_uid<T>(t, kn.def[c]) != 0;
   if (!any) return;
@@ -180,11 +180,13 @@ __device__ __forceinline__ void gen_user_stage(const AlTable<T>& t, const AlKnot
   __syncthreads();
   if (lane == 0) {
     int ro = 0;
+    AL_USER_P_DECL(T, t, b);
+    (void)b;
     for (int c = 0; c < kn.ncon; ++c) {
       const int uid = gen_uid<T>(t, kn.def[c]);
       if (!uid) continue;
-      altro_user_constraint<T>(uid - 1, img, img + ALTRO_HIP_GEN_UN, img + GEN_UIMG_C + ro);
-      altro_user_constraint_jacobian<T>(uid - 1, img, img + ALTRO_HIP_GEN_UN, img + GEN_UIMG_J + ro * GEN_UW);
+      altro_user_constraint<T>(uid - 1, img, img + ALTRO_HIP_GEN_UN, AL_USER_P img + GEN_UIMG_C + ro);
+      altro_user_constraint_jacobian<T>(uid - 1, img, img + ALTRO_HIP_GEN_UN, AL_USER_P img + GEN_UIMG_J + ro * GEN_UW);
       ro += kn.p[c];
     }
   }
@@ -209,7 +211,7 @@ __device__ __forceinline__ void gen_al_rows(const AlTable<T>& t, int k, int b, i
   const int i = lane;
   const int ncon = kn.ncon;
 #ifdef GEN_USER_BLOCKS
-  gen_user_stage<T>(t, kn, n, m, xs, us, terminal, lane);
+  gen_user_stage<T>(t, kn, b, n, m, xs, us, terminal, lane);
   int ro = 0;
 #endif
   for (int c = 0; c < ncon; ++c) {
@@ -557,7 +559,8 @@ __global__ __launch_bounds__(64, 4) void generic_merit_kernel(IlqrGenArgs<T> a) 
     }
     } else {
       using M = DiscreteModel<MK, MN, MM, double>;
-      const float h = model_at(a.mp, k).h;   // the step of THIS knot point (models.h)
+      const ModelParams mpk = model_at(a.mp, k, b);   // the step of THIS knot point, the parameters of THIS problem (models.h)
+      const float h = mpk.h;
       if (deriv) {   // the two Jacobians zeroed by the whole wave (the evaluating lane then stores what its model knows to be nonzero)
         for (int e = lane; e < MN * (MN + MM); e += 64) { md_J0[e] = 0.0; md_Jm[e] = 0.0; }
         __syncthreads();
@@ -567,13 +570,13 @@ __global__ __launch_bounds__(64, 4) void generic_merit_kernel(IlqrGenArgs<T> a) 
         for (int e = 0; e < MN; ++e) xl[e] = xs[e];
         for (int e = 0; e < MM; ++e) ul[e] = us[e];
         if (deriv) {   // (the Jacobians are written where the rows are formed from -- two local arrays of n (n + m) doubles lived in scratch memory)
-          M::cont_fJ_zeroed(a.mp, xl, ul, k1, md_J0);
+          M::cont_fJ_zeroed(mpk, xl, ul, k1, md_J0);
           for (int e = 0; e < MN; ++e) xm[e] = xl[e] + (double)(h / 2) * k1[e];
-          M::cont_fJ_zeroed(a.mp, xm, ul, k2, md_Jm);
+          M::cont_fJ_zeroed(mpk, xm, ul, k2, md_Jm);
         } else {
-          M::cont_f(a.mp, xl, ul, k1);
+          M::cont_f(mpk, xl, ul, k1);
           for (int e = 0; e < MN; ++e) xm[e] = xl[e] + (double)(h / 2) * k1[e];
-          M::cont_f(a.mp, xm, ul, k2);
+          M::cont_f(mpk, xm, ul, k2);
         }
         for (int e = 0; e < MN; ++e) md_xn[e] = xl[e] + (double)h * k2[e];
       }
@@ -862,7 +865,7 @@ __global__ void generic_model_rollout_kernel(IlqrGenArgs<T> a) {
   for (int k = 0; k < a.N; ++k) {
     for (int e = 0; e < MN; ++e) xo[(int64_t)k * MN + e] = (T)x[e];
     for (int e = 0; e < MM; ++e) u[e] = (double)ui[(int64_t)k * MM + e];
-    M::dynamics(model_at(a.mp, k), x, u, xn);
+    M::dynamics(model_at(a.mp, k, b), x, u, xn);
     for (int e = 0; e < MN; ++e) x[e] = xn[e];
   }
   for (int e = 0; e < MN; ++e) xo[(int64_t)a.N * MN + e] = (T)x[e];
@@ -878,7 +881,7 @@ __global__ void generic_model_expand_dyn_kernel(IlqrGenArgs<T> a) {
   double x[MN], u[MM], A[MN * MN], B[MN * MM];
   for (int e = 0; e < MN; ++e) x[e] = (double)a.x[(int64_t)b * a.x_bs + (int64_t)k * MN + e];
   for (int e = 0; e < MM; ++e) u[e] = (double)a.u[(int64_t)b * a.u_bs + (int64_t)k * MM + e];
-  M::jacobian(model_at(a.mp, k), x, u, A, B);
+  M::jacobian(model_at(a.mp, k, b), x, u, A, B);
   T* Ao = const_cast<T*>(a.A) + (int64_t)b * a.A_bs + (int64_t)k * MN * MN;
   T* Bo = const_cast<T*>(a.B) + (int64_t)b * a.B_bs + (int64_t)k * MN * MM;
   for (int e = 0; e < MN * MN; ++e) Ao[e] = (T)A[e];

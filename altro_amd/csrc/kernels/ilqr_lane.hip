@@ -174,7 +174,7 @@ __device__ __forceinline__ void ilqr_rollout_lane(const IlqrArgs<T>& a, int64_t 
     T* c = a.cand + (int64_t)k * I::E_CAND * B + b;
     for (int e = 0; e < n; ++e) c[(int64_t)e * B] = x[e];
     for (int e = 0; e < m; ++e) u[e] = c[(int64_t)(2 * n + e) * B];
-    Mdl::dynamics(model_at<GRID>(a.mp, k), x, u, xn);
+    Mdl::dynamics(model_at<GRID>(a.mp, k, (int)b), x, u, xn);
     for (int e = 0; e < n; ++e) x[e] = xn[e];
   }
   T* c = a.cand + (int64_t)N * I::E_CAND * B + b;
@@ -269,7 +269,7 @@ __device__ __forceinline__ void ilqr_expand_point(const IlqrArgs<T>& a, int64_t 
   T* in = a.in + (int64_t)k * D::E_IN * B + b;
   if (grad) {
     T Am[n * n], Bm[n * m];
-    Mdl::jacobian(model_at<GRID>(a.mp, k), x, u, Am, Bm);
+    Mdl::jacobian(model_at<GRID>(a.mp, k, (int)b), x, u, Am, Bm);
     for (int e = 0; e < n * n; ++e) in[(int64_t)(D::O_A + e) * B] = Am[e];
     for (int e = 0; e < n * m; ++e) in[(int64_t)(D::O_B + e) * B] = Bm[e];
     for (int e = 0; e < n; ++e) in[(int64_t)(D::O_f + e) * B] = T(0);
@@ -362,7 +362,7 @@ __device__ __forceinline__ void merit_step(const MeritRec<n, m, T, CK>& r, const
 #pragma unroll
   for (int e = 0; e < m; ++e) lane_st<T>(bc, lane, (uint32_t)(2 * n + e) * rowB, u[e]);
   T Am[n * n], Bm[n * m];
-  const ModelParams mpk = model_at(a.mp, k);
+  const ModelParams mpk = model_at(a.mp, k, (int)b);
   if (deriv) Mdl::step(mpk, x, u, xn, Am, Bm);
   else Mdl::dynamics(mpk, x, u, xn);
   T lx[n], lu[m];
@@ -609,7 +609,7 @@ __device__ __forceinline__ void ilqr_merit_roll_lane(const IlqrArgs<T>& a, const
     for (int e = 0; e < n; ++e) lane_st<T>(bc, lane, (uint32_t)e * rowB, x[e]);
 #pragma unroll
     for (int e = 0; e < m; ++e) lane_st<T>(bc, lane, (uint32_t)(2 * n + e) * rowB, u[e]);
-    Mdl::dynamics(model_at<GRID>(a.mp, k), x, u, xn);
+    Mdl::dynamics(model_at<GRID>(a.mp, k, (int)b0 + (int)(lane / (uint32_t)sizeof(T))), x, u, xn);   // (lane: this problem's byte offset in a row)
     for (int e = 0; e < n; ++e) x[e] = xn[e];
   };
   int k = 0;
@@ -673,7 +673,7 @@ __device__ __forceinline__ void ilqr_merit_point(const IlqrArgs<T>& a, int64_t b
     if (al) Jk += al_eval<n, m, T, true, false>(a.al, k, b, B, x, u, false, rho, rho, lx, lu, nullptr, nullptr, nullptr, nullptr, false);
     if (tr.deriv) {
       T Am[n * n], Bm[n * m];
-      Mdl::jacobian(model_at<GRID>(a.mp, k), x, u, Am, Bm);
+      Mdl::jacobian(model_at<GRID>(a.mp, k, (int)b), x, u, Am, Bm);
       T* j = jd.p + (int64_t)k * jd.E * B + b;
       for (int e = 0; e < n * n; ++e) j[(int64_t)(jd.oA + e) * B] = Am[e];
       for (int e = 0; e < n * m; ++e) j[(int64_t)(jd.oB + e) * B] = Bm[e];

@@ -178,7 +178,10 @@ __device__ __forceinline__ void md_gather16(double v, double (&o)[16]);   // (il
 // pair per call site -- a loop over the table entry in constant memory, not unrolled: inlined per slot of the unrolled slot loops it
 // would be there NC times, and the merit kernel's knot-point loop would then no longer unroll (its record ring would go to scratch).
 // Must be called by every lane of the wave; w: the row's [x; u], zero in the input lanes at the terminal knot point.
-__device__ __forceinline__ void tile_user_eval_knot(const AlKnot ALTRO_CONST_AS& kn, double w, int j, double* uimg) {
+// (t, b: the table and the row's problem -- whose parameters the caller's pair gets under ALTRO_HIP_USER_NP, al_types.h)
+template <typename S>
+__device__ __forceinline__ void tile_user_eval_knot(const AlTable<S>& t, int b, const AlKnot ALTRO_CONST_AS& kn, double w, int j, double* uimg) {
+  (void)t; (void)b;
   double z[16];
   md_gather16(w, z);
   __syncthreads();                                  // the images' last readers are done
@@ -188,8 +191,9 @@ __device__ __forceinline__ void tile_user_eval_knot(const AlKnot ALTRO_CONST_AS&
     const int uid = kn.user[c];
     if (uid == 0) continue;                         // (wave-uniform: the table is the handle's)
     if (j == 0 && nu < AL_TILE_USER_MAXC) {
-      altro_user_constraint<double>(uid - 1, z, z + 12, uimg + nu * MD_UIMG);
-      altro_user_constraint_jacobian<double>(uid - 1, z, z + 12, uimg + nu * MD_UIMG + AL_MAXP);
+      AL_USER_P_DECL(S, t, b);
+      altro_user_constraint<double>(uid - 1, z, z + 12, AL_USER_P uimg + nu * MD_UIMG);
+      altro_user_constraint_jacobian<double>(uid - 1, z, z + 12, AL_USER_P uimg + nu * MD_UIMG + AL_MAXP);
     }
     ++nu;
   }
@@ -224,7 +228,7 @@ __device__ __forceinline__ void dpp_al_rows(const AlTable<S>& t, int k, int b, i
   int zshift;
   const AlKnot ALTRO_CONST_AS& kn = al_knot<S>(t, k, zshift);
 #ifdef MD_USER_BLOCKS
-  tile_user_eval_knot(kn, w, j, uimg);
+  tile_user_eval_knot(t, b, kn, w, j, uimg);
   int nu = 0;                                       // user slots so far: the next one's image
 #endif
 #pragma unroll
@@ -625,7 +629,7 @@ __global__ __launch_bounds__(64, ((MK != 0 || (AL && DENSE && sizeof(S) == 8)) ?
     if (al) {   // both trials' constraint rows at the candidate point [x; u]; the feasibility that counts is trial 1's
       double Ja = 0.0, vv = 0.0;
 #ifdef MD_USER_BLOCKS
-      if (live) tile_user_eval_knot(*(const AlKnot ALTRO_CONST_AS*)(a.al.knots + (al_uni ? 0 : k)), w, j, uimg_row);   // (a padding step's rows are discarded)
+      if (live) tile_user_eval_knot(a.al, b, *(const AlKnot ALTRO_CONST_AS*)(a.al.knots + (al_uni ? 0 : k)), w, j, uimg_row);   // (a padding step's rows are discarded)
 #endif
       if (live) {
         if (k + 1 >= N) alp_knot<S, NC>(a.al, N, kn_s);           // (k + 1 <= N: the terminal knot point's too)
@@ -669,7 +673,7 @@ __global__ __launch_bounds__(64, ((MK != 0 || (AL && DENSE && sizeof(S) == 8)) ?
 #pragma unroll
       for (int c = 0; c < 16; ++c) cR[c] = 0.0;
     } else if constexpr (MK != 0) {   // a device model: x+ = F(x, u), and row j of Z = [A B] at (x, u) where phi' is wanted
-      const ModelParams mpk = model_at(a.mp, kc);            // (kc: a padding pass of the ring stays inside the time-step array)
+      const ModelParams mpk = model_at(a.mp, kc, b);            // (kc: a padding pass of the ring stays inside the time-step array)
       if (DUAL || deriv) {
         tile_model_step<MK, true>(mpk, w, jr, xn, cR);
       } else {
@@ -767,7 +771,7 @@ __global__ __launch_bounds__(64, ((MK != 0 || (AL && DENSE && sizeof(S) == 8)) ?
     if (al) {
       double Ja = 0.0, vv = 0.0;
 #ifdef MD_USER_BLOCKS
-      tile_user_eval_knot(*(const AlKnot ALTRO_CONST_AS*)(a.al.knots + N), isx ? x : 0.0, j, uimg_row);
+      tile_user_eval_knot(a.al, b, *(const AlKnot ALTRO_CONST_AS*)(a.al.knots + N), isx ? x : 0.0, j, uimg_row);
 #endif
       if constexpr (DUAL) {
         alp_rows<SOC, NC, FUSE>(kc_s, isx ? x : 0.0, rho, j, rowb, jvr, Ja, vv, Gdyn, zg, jr, &colsum MD_UARGS(true));
@@ -1006,7 +1010,7 @@ __global__ __launch_bounds__(64) void wave_expand_dpp_kernel(IlqrWaveArgs<S> a) 
   double scol = 0.0;
   bool tile_counts = true;
 #ifdef MD_USER_BLOCKS
-  tile_user_eval_knot(kn, w, j, uimg_row);
+  tile_user_eval_knot(a.al, b, kn, w, j, uimg_row);
   int nu = 0;                                       // user slots so far: the next one's image
 #endif
 #pragma unroll

@@ -556,7 +556,7 @@ __global__ __launch_bounds__(64, WPS) void row32_merit_kernel(IlqrGenArgs<T> a) 
     if constexpr (MK != 0) {   // the model at this knot point's [x; u]; with the derivative the state lanes' rows of [A_k B_k] into the image
       if (deriv) {
         double zrow[NX + NU];
-        r32_model_step<MK, NX, NU, true>(model_at(a.mp, k), vw, x, ix, xmodel, zrow);
+        r32_model_step<MK, NX, NU, true>(model_at(a.mp, k, b), vw, x, ix, xmodel, zrow);
         if (isx) {
 #pragma unroll
           for (int c = 0; c < NX; ++c) Lw[oAm + ix + c * NX] = zrow[c];
@@ -574,7 +574,7 @@ __global__ __launch_bounds__(64, WPS) void row32_merit_kernel(IlqrGenArgs<T> a) 
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       } else {
         double unused[NX + NU];
-        r32_model_step<MK, NX, NU, false>(model_at(a.mp, k), vw, x, ix, xmodel, unused);
+        r32_model_step<MK, NX, NU, false>(model_at(a.mp, k, b), vw, x, ix, xmodel, unused);
       }
       gAw += sA; gBw += sB;
     }
@@ -694,7 +694,7 @@ __global__ __launch_bounds__(64, 1) void row32_expand_dyn_kernel(IlqrGenArgs<T> 
   const double w = isx ? (double)a.x[(int64_t)b * a.x_bs + (int64_t)k * NX + ix] : (isu ? (double)a.u[(int64_t)b * a.u_bs + (int64_t)k * NU + iu] : 0.0);
   const R32Vec vw = r32_spread(w, upper_row);
   double xn, zrow[NX + NU];
-  r32_model_step<MK, NX, NU, true>(model_at(a.mp, k), vw, w, ix, xn, zrow);   // (k: the half's own knot point)
+  r32_model_step<MK, NX, NU, true>(model_at(a.mp, k, b), vw, w, ix, xn, zrow);   // (k: the half's own knot point)
   if (ok_own && isx) {
     T* Ao = const_cast<T*>(a.A) + (int64_t)b * a.A_bs + (int64_t)k * NX * NX + ix;
     T* Bo = const_cast<T*>(a.B) + (int64_t)b * a.B_bs + (int64_t)k * NX * NU + ix;

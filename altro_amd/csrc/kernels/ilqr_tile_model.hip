@@ -134,7 +134,7 @@ __global__ __launch_bounds__(64) void wave_rollout_model_kernel(IlqrWaveArgs<S> 
     unext = (double)candb[(size_t)(k + 1 < a.N ? k + 1 : k) * a.xuy_ks + 12 + j];
     if (on && isx) candb[(size_t)k * a.xuy_ks + j] = (S)x;
     double xn, unused[16];
-    tile_model_step<MK, false>(model_at(mp, k), w, jr, xn, unused);
+    tile_model_step<MK, false>(model_at(mp, k, b), w, jr, xn, unused);
     x = xn;
   }
   if (on && isx) candb[(size_t)a.N * a.xuy_ks + j] = (S)x;
@@ -160,7 +160,7 @@ __global__ __launch_bounds__(64) void wave_expand_dyn_kernel(IlqrWaveArgs<S> a) 
   const S* c = a.cand + (size_t)b * a.xuy_bs + (size_t)k * a.xuy_ks;
   const double w = isx ? (double)c[j] : (double)c[12 + j];
   double xn, zrow[16];
-  tile_model_step<MK, true>(model_at(mp, k), w, jr, xn, zrow);
+  tile_model_step<MK, true>(model_at(mp, k, b), w, jr, xn, zrow);
   if (on && isx) {
     S* z = const_cast<S*>(a.dyn) + (size_t)b * a.dyn_bs + (size_t)k * a.dyn_ks;
 #pragma unroll

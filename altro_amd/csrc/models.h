@@ -41,6 +41,12 @@ struct ModelParams {
   // altro_hip_set_time_steps: hk[k] = the step from knot point k to k + 1, one float[N] on the device shared by the batch
   // (ALTROSolver::SetTimeStep(h, k_start, k_stop), altro_solver.hpp:55; KnotPointData holds one h per knot point) -- or null: `h` everywhere
   const float* hk = nullptr;
+  // altro_hip_set_model_params: the per-problem parameters of a model from source, [P][theta_bs] in the handle's element type on the
+  // device (parameter i of problem b at theta[i * theta_bs + b]: plan LANE's lane-per-problem reads are coalesced, a row of the row
+  // layouts reads one address) -- or null.  theta_b: the problem the struct was taken for (model_at).  Read only under
+  // ALTRO_HIP_USER_NP, which exists only in the units compiled at run time (rtc_unit.h): dead code in every kernel of the library.
+  const void* theta = nullptr;
+  int theta_bs = 0, theta_b = 0;
 };
 
 // The model's parameters AT knot point k: what every kernel that steps a model at k hands the functions below, which read `h`
@@ -48,9 +54,11 @@ struct ModelParams {
 // constant address space like the constraint tables (kernels/al_types.h): one scalar load, and from there on the arithmetic is
 // that of a uniform handle -- a handle without the array and one whose array is constant run the same instructions on the same
 // values.  GRID = false (the one-launch solve kernel, kernels/ilqr_fused.hip, which serves uniform handles only): `mp` as it is.
+// b: the problem, whose view of the parameter array the struct carries from here on (theta_b; model_theta below reads through it).
 template <bool GRID = true>
-ALTRO_HD ModelParams model_at(const ModelParams& mp, int k) {
+ALTRO_HD ModelParams model_at(const ModelParams& mp, int k, int b) {
   ModelParams q = mp;
+  q.theta_b = b;
   if constexpr (GRID) {
 #if defined(__HIP_DEVICE_COMPILE__)
     if (mp.hk) q.h = ((const float __attribute__((address_space(4)))*)mp.hk)[k];
@@ -60,6 +68,23 @@ ALTRO_HD ModelParams model_at(const ModelParams& mp, int k) {
   }
   return q;
 }
+
+#if defined(ALTRO_HIP_USER_NP)
+// The ALTRO_HIP_USER_NP parameters of the problem `mp` was taken for (model_at), into registers: what the caller's functions get as `p`.
+// (Called where the caller's functions are; between the two evaluations of one midpoint step nothing is stored, so the loads are shared.)
+template <typename T>
+ALTRO_HD void model_theta(const ModelParams& mp, T (&p)[ALTRO_HIP_USER_NP]) {
+  const T* t = (const T*)mp.theta + mp.theta_b;
+#pragma unroll
+  for (int i = 0; i < ALTRO_HIP_USER_NP; ++i) p[i] = t[(size_t)i * (size_t)mp.theta_bs];
+}
+// the caller's dynamics pair with or without the parameters: one spelling at every call site
+#define ALTRO_USER_P_DECL(T, mp) T altro_p_[ALTRO_HIP_USER_NP]; model_theta<T>(mp, altro_p_)
+#define ALTRO_USER_P altro_p_,
+#else
+#define ALTRO_USER_P_DECL(T, mp) (void)0
+#define ALTRO_USER_P
+#endif
 
 // sin and cos of one argument with a single range reduction on the device.  (A hand-written fp64 evaluation -- Cody-Waite
 // reduction as a double-double, fdlibm kernels, 0.78 ulp worst case over [-2^20, 2^20] -- was measured against the library
@@ -289,20 +314,22 @@ ALTRO_HD void quadrotor_J_from(const QuadTrig<T>& t, const T* x, const T* u, T* 
 // inputs in columns 12..15.  Padding states have xdot = 0 (they stay at 0; their rows of A are the identity's), padding inputs
 // no effect.
 template <typename T>
-ALTRO_HD void altro_tile_user_f(const T* x, const T* u, T* xdot) {
+ALTRO_HD void altro_tile_user_f(const ModelParams& mp, const T* x, const T* u, T* xdot) {
   T xd[ALTRO_HIP_TILE_N];
-  altro_user_dynamics<T>(x, u, xd);
+  ALTRO_USER_P_DECL(T, mp);
+  altro_user_dynamics<T>(x, u, ALTRO_USER_P xd);
 #pragma unroll
   for (int i = 0; i < 12; ++i) xdot[i] = T(0);
 #pragma unroll
   for (int i = 0; i < ALTRO_HIP_TILE_N; ++i) xdot[i] = xd[i];
 }
 template <typename T>
-ALTRO_HD void altro_tile_user_J(const T* x, const T* u, T* J) {
+ALTRO_HD void altro_tile_user_J(const ModelParams& mp, const T* x, const T* u, T* J) {
   T Ju[ALTRO_HIP_TILE_N * (ALTRO_HIP_TILE_N + ALTRO_HIP_TILE_M)];
 #pragma unroll
   for (int e = 0; e < ALTRO_HIP_TILE_N * (ALTRO_HIP_TILE_N + ALTRO_HIP_TILE_M); ++e) Ju[e] = T(0);
-  altro_user_jacobian<T>(x, u, Ju);
+  ALTRO_USER_P_DECL(T, mp);
+  altro_user_jacobian<T>(x, u, ALTRO_USER_P Ju);
 #pragma unroll
   for (int e = 0; e < 192; ++e) J[e] = T(0);
 #pragma unroll
@@ -381,9 +408,9 @@ struct DiscreteModel {
   static ALTRO_HD void cont_f(const ModelParams& mp, const T* x, const T* u, T* xdot) {
     if (KIND == MODEL_PENDULUM) pendulum_f<T>(x, u, xdot);
 #if defined(ALTRO_HIP_USER_MODEL) && defined(ALTRO_HIP_TILE_N)
-    else if (KIND == MODEL_USER) altro_tile_user_f<T>(x, u, xdot);
+    else if (KIND == MODEL_USER) altro_tile_user_f<T>(mp, x, u, xdot);
 #elif defined(ALTRO_HIP_USER_MODEL)
-    else if (KIND == MODEL_USER) altro_user_dynamics<T>(x, u, xdot);
+    else if (KIND == MODEL_USER) { ALTRO_USER_P_DECL(T, mp); altro_user_dynamics<T>(x, u, ALTRO_USER_P xdot); }
 #endif
     else if (KIND == MODEL_QUADROTOR) quadrotor_f_from<T>(quadrotor_trig<T>(x), x, u, xdot);
     else if (KIND == MODEL_QUADROTOR13) quadrotor13_f<T>(x, u, xdot);
@@ -392,9 +419,9 @@ struct DiscreteModel {
   static ALTRO_HD void cont_J(const ModelParams& mp, const T* x, const T* u, T* J) {
     if (KIND == MODEL_PENDULUM) pendulum_J<T>(x, u, J);
 #if defined(ALTRO_HIP_USER_MODEL) && defined(ALTRO_HIP_TILE_N)
-    else if (KIND == MODEL_USER) altro_tile_user_J<T>(x, u, J);
+    else if (KIND == MODEL_USER) altro_tile_user_J<T>(mp, x, u, J);
 #elif defined(ALTRO_HIP_USER_MODEL)
-    else if (KIND == MODEL_USER) altro_user_jacobian<T>(x, u, J);
+    else if (KIND == MODEL_USER) { ALTRO_USER_P_DECL(T, mp); altro_user_jacobian<T>(x, u, ALTRO_USER_P J); }
 #endif
     else if (KIND == MODEL_QUADROTOR) quadrotor_J_from<T>(quadrotor_trig<T>(x), x, u, J);
     else if (KIND == MODEL_QUADROTOR13) quadrotor13_J<T>(x, u, J);
@@ -408,9 +435,9 @@ struct DiscreteModel {
   }
   static ALTRO_HD void cont_fJ(const ModelParams& mp, const T* x, const T* u, T* xdot, T* J) {
 #if defined(ALTRO_HIP_USER_MODEL) && defined(ALTRO_HIP_TILE_N)
-    if (KIND == MODEL_USER) { altro_tile_user_f<T>(x, u, xdot); altro_tile_user_J<T>(x, u, J); return; }
+    if (KIND == MODEL_USER) { altro_tile_user_f<T>(mp, x, u, xdot); altro_tile_user_J<T>(mp, x, u, J); return; }
 #elif defined(ALTRO_HIP_USER_MODEL)
-    if (KIND == MODEL_USER) { altro_user_dynamics<T>(x, u, xdot); altro_user_jacobian<T>(x, u, J); return; }
+    if (KIND == MODEL_USER) { ALTRO_USER_P_DECL(T, mp); altro_user_dynamics<T>(x, u, ALTRO_USER_P xdot); altro_user_jacobian<T>(x, u, ALTRO_USER_P J); return; }
 #endif
     if (KIND == MODEL_QUADROTOR) {   // one set of sincos for f and J
       const QuadTrig<T> t = quadrotor_trig<T>(x);

@@ -98,12 +98,19 @@ inline bool source_has_constraints(const std::string& src) {
 // every entry then counts as a nonzero, and the kernel spills 585 registers, the tile plan's merit kernels 240-330.)
 inline const std::vector<const char*> kRtcOptions = {"-O3", "-std=c++17"}, kRtcRowOptions = {"-O3", "-std=c++17", "-mllvm", "-unroll-threshold=5000"};
 
+// num_params (every maker's last argument): altro_hip_set_model_source_params' P.  P > 0: the caller's functions take `const T* p`, the
+// P per-problem parameters -- ALTRO_HIP_USER_NP in the unit's defines (models.h, kernels/al_types.h gather them) and a piece of its key,
+// so that one source text with and without parameters are two modules.  P = 0 adds nothing to either: the unit of altro_hip_set_model_source.
+inline std::string rtc_np_key(int num_params) { return num_params > 0 ? "P" + std::to_string(num_params) + "|" : std::string(); }
+inline std::string rtc_np_define(int num_params) { return num_params > 0 ? "#define ALTRO_HIP_USER_NP " + std::to_string(num_params) + "\n" : std::string(); }
+
 // plan LANE: the launch-sequenced loop's kernels (kernels/ilqr_lane.hip) for one (source, n, m, element type, cost kind)
-inline RtcUnit rtc_unit_lane(int n, int m, const char* T, int ck, const std::string& source) {
+inline RtcUnit rtc_unit_lane(int n, int m, const char* T, int ck, const std::string& source, int num_params = 0) {
   RtcUnit u;
   u.kind = RtcKind::lane; u.program = "altro_user_model.hip";
-  u.key = std::string(1, (char)u.kind) + "|" + std::to_string(n) + "|" + std::to_string(m) + "|" + T + "|" + std::to_string(ck) + "|" + source;
+  u.key = std::string(1, (char)u.kind) + "|" + std::to_string(n) + "|" + std::to_string(m) + "|" + T + "|" + std::to_string(ck) + "|" + rtc_np_key(num_params) + source;
   if (source_has_constraints(source)) u.defines = "#define ALTRO_HIP_USER_CONSTRAINTS 1\n";
+  u.defines += rtc_np_define(num_params);
   u.includes = "#include \"kernels/ilqr_lane.hip\"\n";
   for (int w = 0; w < RTC_NUM; ++w) u.exprs.push_back(kernel_expr(w, n, m, T, ck));
   u.args = std::string("IlqrArgs<") + T + ">"; u.options = kRtcOptions;
@@ -116,13 +123,14 @@ inline RtcUnit rtc_unit_lane(int n, int m, const char* T, int ck, const std::str
 // user: some slot of the handle comes from the source's altro_user_constraint / _jacobian (al != 0, and the source defines the pair):
 // the unit is compiled with ALTRO_HIP_USER_CONSTRAINTS and also instantiates the three row-layout kernels that evaluate constraint
 // rows outside the merit pass -- the library's own instantiations of them know nothing of such a slot.
-inline RtcUnit rtc_unit_tile(int n, int m, int al, int dense, const std::string& source, int wide = 0, int user = 0) {
+inline RtcUnit rtc_unit_tile(int n, int m, int al, int dense, const std::string& source, int wide = 0, int user = 0, int num_params = 0) {
   RtcUnit u;
   u.kind = RtcKind::tile; u.program = "altro_user_tile_model.hip"; u.where = " for the tile plan"; u.noun = "tile model";
   u.key = std::string(1, (char)u.kind) + "|" + std::to_string(n) + "|" + std::to_string(m) + "|" + std::to_string(al) + "|" + std::to_string(dense) + "|" +
-          std::to_string(wide) + (user ? "u" : "") + "|" + source;
+          std::to_string(wide) + (user ? "u" : "") + "|" + rtc_np_key(num_params) + source;
   u.defines = "#define ALTRO_HIP_TILE_N " + std::to_string(n) + "\n#define ALTRO_HIP_TILE_M " + std::to_string(m) + "\n";
   if (user) u.defines += "#define ALTRO_HIP_USER_CONSTRAINTS 1\n";
+  u.defines += rtc_np_define(num_params);
   u.includes = "#include \"kernels/ilqr_mfma16.hip\"\n#include \"kernels/ilqr_merit2_dpp.hip\"\n";
   const char* B_[2] = {"false", "true"};
   u.exprs.resize(RTT_NUM);
@@ -142,12 +150,13 @@ inline RtcUnit rtc_unit_tile(int n, int m, int al, int dense, const std::string&
 }
 // plans GENERIC / MFMA32: the caller's model inside that plan's loop kernels (kernels/ilqr_generic.hip); row_shape: the shape is one of
 // plan MFMA32's (tile32_supported), so the row-layout kernels are instantiated too
-inline RtcUnit rtc_unit_generic(int n, int m, bool row_shape, const std::string& source) {
+inline RtcUnit rtc_unit_generic(int n, int m, bool row_shape, const std::string& source, int num_params = 0) {
   RtcUnit u;
   u.kind = RtcKind::generic; u.program = "altro_user_generic_model.hip"; u.where = " for plan GENERIC's loop";
-  u.key = std::string(1, (char)u.kind) + "|" + std::to_string(n) + "|" + std::to_string(m) + "|" + source;
+  u.key = std::string(1, (char)u.kind) + "|" + std::to_string(n) + "|" + std::to_string(m) + "|" + rtc_np_key(num_params) + source;
   const bool al = source_has_constraints(source);
   if (al) u.defines = "#define ALTRO_HIP_USER_CONSTRAINTS 1\n#define ALTRO_HIP_GEN_UN " + std::to_string(n) + "\n#define ALTRO_HIP_GEN_UM " + std::to_string(m) + "\n";
+  u.defines += rtc_np_define(num_params);
   u.includes = std::string("#include \"kernels/ilqr_generic.hip\"\n") + (row_shape ? "#include \"kernels/ilqr_row32.hip\"\n" : "");
   const std::string nm = std::to_string(n) + ", " + std::to_string(m);
   u.exprs.resize(RTG_NUM_ALL);

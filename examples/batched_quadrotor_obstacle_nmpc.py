@@ -6,10 +6,14 @@ the same source (altro_hip_add_user_constraint).  The handle is created with ALT
 the sphere takes one of the knot points' six slots and is evaluated inside the row-layout kernels.  Every MPC step applies
 u_0, shifts the horizon and re-solves warm-started.
 
-    python examples/batched_quadrotor_obstacle_nmpc.py [batch] [steps] [--plan generic] [--no-obstacle] [--warm-duals]
+    python examples/batched_quadrotor_obstacle_nmpc.py [batch] [steps] [--plan generic] [--no-obstacle] [--warm-duals] [--own-spheres]
 
 --warm-duals carries the multipliers from one step to the next: instead of zeroing them after the shift (reset_duals), the duals move one
 knot point forward with the trajectory (shift_duals) and the penalty goes back to the solve's penalty_initial (set_penalty).
+
+--own-spheres gives every vehicle a sphere of its own: the centre moves sideways by up to +-0.15 over the batch and the radius runs from
+0.25 to 0.35.  The source then reads (centre, radius) from four per-problem parameters (altro_hip_set_model_source_params /
+altro_hip_set_model_params) -- one handle and one compile for 1024 different keep-out regions.
 
 --plan generic runs the same problem on plan GENERIC's wave-per-problem kernels (where such a source went before the flag), so that the
 two timings can be put side by side.  Prints the ms per NMPC step (median over the warm steps) with the mean iteration counts, and the
@@ -84,9 +88,26 @@ template <typename T> __device__ void altro_user_constraint_jacobian(int id, con
 """
 
 
-def clearance(p):
-    """distance to the sphere's surface of positions p[..., 3]"""
-    return np.linalg.norm(p - CENTER, axis=-1) - RADIUS
+def own_sphere_source(src):
+    """SOURCE with the sphere read from the problem's parameters p = (centre x, y, z, radius): the four functions take `const T* p`."""
+    out = src.replace("const T* x, const T* u, T* xd)", "const T* x, const T* u, const T* p, T* xd)")
+    out = out.replace("const T* x, const T* u, T* J)", "const T* x, const T* u, const T* p, T* J)")
+    out = out.replace("const T* x, const T* u, T* c)", "const T* x, const T* u, const T* p, T* c)")
+    out = out.replace("const T dx = x[0] - T(-0.75), dy = x[1], dz = x[2];", "const T dx = x[0] - p[0], dy = x[1] - p[1], dz = x[2] - p[2];")
+    out = out.replace("c[0] = T(0.09) - dx * dx", "c[0] = p[3] * p[3] - dx * dx")
+    out = out.replace("J[0] = -T(2) * (x[0] - T(-0.75)); J[1] = -T(2) * x[1]; J[2] = -T(2) * x[2];",
+                      "J[0] = -T(2) * (x[0] - p[0]); J[1] = -T(2) * (x[1] - p[1]); J[2] = -T(2) * (x[2] - p[2]);")
+    assert out.count("const T* p") == 4 and "T(-0.75)" not in out and "T(0.09)" not in out
+    return out
+
+
+def clearance(p, center=CENTER, radius=RADIUS):
+    """distance to the sphere's surface of positions p[batch, ..., 3]; center [3] / radius, or one per vehicle ([batch, 3] / [batch])"""
+    c = np.asarray(center)
+    if c.ndim == 2:
+        c = c.reshape((c.shape[0],) + (1,) * (p.ndim - 2) + (3,))
+        radius = np.asarray(radius).reshape((c.shape[0],) + (1,) * (p.ndim - 2))
+    return np.linalg.norm(p - c, axis=-1) - radius
 
 
 def main():
@@ -99,6 +120,7 @@ def main():
     steps = int(argv[1]) if len(argv) > 1 else 8
     obstacle = "--no-obstacle" not in args
     warm_duals = "--warm-duals" in args
+    own = "--own-spheres" in args and obstacle
     rng = np.random.default_rng(5)
     x0 = np.zeros((batch, n))
     x0[:, :3] = np.array([-1.5, 0.0, 0.0]) + 0.05 * rng.standard_normal((batch, 3))
@@ -114,14 +136,21 @@ def main():
     gb = np.concatenate([[1.25 * HOVER[0], 0.05, 0.05, 0.05], [-0.6 * HOVER[0], 0.05, 0.05, 0.05]])
     bt.add_linear_constraint(0, N - 1, altro_amd.CONE_INEQUALITY, Gb, gb)
     bt.set_tracking_cost(np.stack([Qd, 20.0 * Qd]), Rd[None], np.zeros((2, n)), HOVER[None], k_stride_zero=True, batch_stride_zero=True)
-    bt.set_model_source(SOURCE, H)
+    center, radius = CENTER, RADIUS
+    if own:
+        center = np.tile(CENTER, (batch, 1)); center[:, 1] += 0.15 * np.linspace(-1.0, 1.0, batch)
+        radius = np.linspace(0.25, 0.35, batch)
+        bt.set_model_source(own_sphere_source(SOURCE), H, num_params=4)
+        bt.set_model_params(np.concatenate([center, radius[:, None]], axis=1))
+    else:
+        bt.set_model_source(SOURCE, H)
     if obstacle:
         bt.add_user_constraint(1, N, altro_amd.CONE_INEQUALITY, 1, 0)
     bt.set_initial_state(x0)
     bt.set_input_guess(HOVER[None, None], k_stride_zero=True, batch_stride_zero=True)
     opts = dict(iterations_max=60, tol_stationarity=1e-3, penalty_initial=10.0)
     plan = {altro_amd.PLAN_MFMA16: "MFMA16", altro_amd.PLAN_GENERIC: "GENERIC"}.get(bt.plan, str(bt.plan))
-    print("%d vehicles, (n, m) = (%d, %d), N = %d, plan %s, keep-out sphere %s" % (batch, n, m, N, plan, "on" if obstacle else "off"))
+    print("%d vehicles, (n, m) = (%d, %d), N = %d, plan %s, keep-out sphere %s" % (batch, n, m, N, plan, ("one per vehicle" if own else "on") if obstacle else "off"))
 
     t0 = time.perf_counter(); res = bt.ilqr_solve(**opts); bt.synchronize()
     print("first solve: %.2f ms, %d of %d converged" % ((time.perf_counter() - t0) * 1e3, int((res["status"] == 0).sum()), batch))
@@ -144,12 +173,14 @@ def main():
         print("step %d: %.2f ms, mean iterations %.2f, %d converged; %d sweeps, mean dual updates %.2f, worst feasibility %.2e"
               % (step, ts[-1], its[-1], int((res["status"] == 0).sum()), res["sweeps"], float(res["dual_updates"].mean()), float(res["feasibility"].max())))
     x, _ = bt.get_nominal()
-    cl = min(clearance(np.stack(flown, axis=1)).min(), clearance(x[:, :, :3]).min())
+    cl = min(clearance(np.stack(flown, axis=1), center, radius).min(), clearance(x[:, :, :3], center, radius).min())
     ok = res["status"] == 0
-    cl_ok = clearance(x[ok][:, :, :3]).min() if ok.any() else float("nan")
+    cl_ok = float("nan")
+    if ok.any():
+        cl_ok = clearance(x[ok][:, :, :3], center[ok] if own else center, radius[ok] if own else radius).min()
     print("duals after the shift: %s" % ("shifted with the trajectory (--warm-duals)" if warm_duals else "reset to zero"))
     print("plan %s, %d vehicles: median NMPC step %.2f ms (mean iterations over the warm steps %.2f); minimum clearance over the batch %+.4f, "
-          "over the last solve's converged plans %+.4f (sphere radius %.2f)" % (plan, batch, sorted(ts)[len(ts) // 2], float(np.mean(its)), cl, cl_ok, RADIUS))
+          "over the last solve's converged plans %+.4f (sphere radius %s)" % (plan, batch, sorted(ts)[len(ts) // 2], float(np.mean(its)), cl, cl_ok, "0.25 .. 0.35, one per vehicle" if own else "%.2f" % RADIUS))
     bt.close()
 
 

@@ -191,7 +191,7 @@ int altro_hip_set_initial_state(altro_hip_batch* h, const double* x0, int batch_
  * altro_hip_get_K .. get_y / get_nominal / get_knot are DEVICE pointers (fp64, the same reference layout) on the
  * handle's device: kernels on the handle's stream read / write them in place, no staging copy -- for callers whose
  * linearisation already lives in HBM.  Everything else (status, delta_V, alpha / phi, results, duals, tracking-cost
- * arguments) stays in host memory.  Default 0.  Stream ordering is the caller's: the handle works on its own
+ * arguments, the model parameters of altro_hip_set_model_params) stays in host memory.  Default 0.  Stream ordering is the caller's: the handle works on its own
  * stream, so work other streams still have pending on those arrays must be complete before the call; on return
  * the call's own reads / writes are complete (it synchronises its stream).                                */
 int altro_hip_set_pointer_mode(altro_hip_batch* h, int device_pointers);
@@ -259,6 +259,34 @@ int altro_hip_set_model(altro_hip_batch* h, int model, float timestep, int bicyc
  * (ALTRO_HIP_ERR_UNSUPPORTED) unless the handle was created with ALTRO_HIP_TILE_USER_BLOCKS (fp64 records): then it takes the
  * source and an AUTO handle stays on the tile.  A source that defines only one of the pair is ALTRO_HIP_ERR_BAD_ARGUMENT.   */
 int altro_hip_set_model_source(altro_hip_batch* h, const char* source, float timestep);
+/* PER-PROBLEM PARAMETERS for a model from source.  The reference's dynamics and constraints are std::function callbacks that close over
+ * whatever the caller likes (typedefs.hpp:31-53), one solver per problem: every problem has its own constants for free.  Here a batch
+ * shares one source text, so its constants -- a mass, a wheel base, an obstacle's centre -- come as `num_params` = P numbers per problem.
+ * altro_hip_set_model_source_params is altro_hip_set_model_source for a source whose functions take one more argument, `p`: the P
+ * parameters of THIS problem, in the element type of the handle,
+ *     template <typename T> __device__ void altro_user_dynamics(const T* x, const T* u, const T* p, T* xdot);
+ *     template <typename T> __device__ void altro_user_jacobian(const T* x, const T* u, const T* p, T* J);
+ *     template <typename T> __device__ void altro_user_constraint(int id, const T* x, const T* u, const T* p, T* c);            // optional pair,
+ *     template <typename T> __device__ void altro_user_constraint_jacobian(int id, const T* x, const T* u, const T* p, T* J);   // both or neither
+ * on every plan and element type that takes a source (LANE fp64 / fp32, MFMA16 fp64 records, GENERIC / MFMA32).  num_params = 0 is
+ * altro_hip_set_model_source exactly (the three-argument forms, the same compiled module); num_params < 0 or > ALTRO_HIP_MODEL_MAX_PARAMS
+ * is ALTRO_HIP_ERR_BAD_ARGUMENT.  An old-style source compiled with P > 0 fails to compile, with the compiler's log.
+ * altro_hip_set_model_params: theta is a HOST array [batch][P] (or [P] with batch_stride_zero != 0: one set for every problem) -- always
+ * a host pointer, whatever altro_hip_set_pointer_mode says -- converted once to the handle's element type and kept on the device as
+ * [P][batch].  A non-finite entry (on an fp32 handle: one that is not finite as a float) is
+ * ALTRO_HIP_ERR_BAD_ARGUMENT and nothing is written.  The call invalidates the current expansion,
+ * like altro_hip_set_model_source.  There is NO default: until it has been called, every call that steps the model or evaluates a block
+ * from the source (rollout, expand, merit, stationarity, feasibility, solve) answers ALTRO_HIP_ERR_NOT_SET and the handle stays usable.
+ * altro_hip_get_model_params returns what is stored, widened ([batch][P]).  On a handle whose model takes no parameters both answer
+ * ALTRO_HIP_ERR_NOT_SET and altro_hip_model_num_params returns 0.  A later altro_hip_set_model / _set_model_source /
+ * _set_model_source_params drops the array; altro_hip_shift_trajectory and altro_hip_shift_duals do not touch it (a parameter belongs to
+ * the problem, not to a knot point: the grid along the horizon is altro_hip_set_time_steps'); altro_hip_batch_device_bytes counts it.
+ * Handles with per-knot-point dimensions: ALTRO_HIP_ERR_UNSUPPORTED, like altro_hip_set_model_source.                                  */
+#define ALTRO_HIP_MODEL_MAX_PARAMS 16
+int altro_hip_set_model_source_params(altro_hip_batch* h, const char* source, float timestep, int num_params);
+int altro_hip_set_model_params(altro_hip_batch* h, const double* theta, int batch_stride_zero);
+int altro_hip_get_model_params(altro_hip_batch* h, double* theta);
+int altro_hip_model_num_params(const altro_hip_batch* h);
 /* ALTROSolver::SetTimeStep(h, k_start, k_stop) (altro_solver.hpp:55) for the batched path: one time step PER KNOT POINT.  dt is a
  * host array of N floats, dt[k] = the step from knot point k to k + 1 -- the `float h` the reference hands its dynamics callbacks
  * (typedefs.hpp:31-35) -- shared by the batch and kept as one float[N] on the handle's device.  Every kernel that steps the model at

@@ -80,6 +80,12 @@ class BatchSolver {
   }
   // SetExplicitDynamics with the caller's own continuous model as HIP source, compiled at run time (altro_hip_set_model_source)
   void SetModelSource(const char* source, float timestep) { Check(altro_hip_set_model_source(h_, source, timestep)); }
+  // ... whose functions take num_params per-problem parameters `p` (altro_hip_set_model_source_params); theta: host [batch][num_params],
+  // or one set for every problem; nothing steps the model before SetModelParams
+  void SetModelSource(const char* source, float timestep, int num_params) { Check(altro_hip_set_model_source_params(h_, source, timestep, num_params)); }
+  void SetModelParams(const double* theta, bool shared_over_batch = false) { Check(altro_hip_set_model_params(h_, theta, shared_over_batch ? 1 : 0)); }
+  void GetModelParams(double* theta) { Check(altro_hip_get_model_params(h_, theta)); }
+  int ModelNumParams() const { return altro_hip_model_num_params(h_); }
   // ALTROSolver::SetTimeStep per knot-point range for the device model: dt[k] (N floats) = the step from knot point k to k + 1, shared by
   // the batch; nullptr: the uniform step of SetModel / SetModelSource again (altro_hip_set_time_steps)
   void SetTimeSteps(const float* dt) { Check(altro_hip_set_time_steps(h_, dt)); }
