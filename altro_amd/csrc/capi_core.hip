@@ -144,6 +144,7 @@ static int batch_create_impl(altro_hip_batch** out, int N, int n, int m, int bat
   int rc = 0;
   const size_t B = (size_t)batch, E = h->esz;
 #define ALLOC(ptr, bytes) if (!rc) rc = dmalloc(h, (void**)&(ptr), (bytes))
+#define ALLOC_ZERO(ptr, bytes) if (!rc) rc = dmalloc_zero(h, (void**)&(ptr), (bytes))
   h->x0_stride = plan == ALTRO_HIP_PLAN_MFMA16 ? MF_N : n;      // plan MFMA16 keeps x0 in tile rows of 12
   ALLOC(h->x0, B * h->x0_stride * E);
   ALLOC(h->delta_V, B * 2 * E);
@@ -181,13 +182,10 @@ static int batch_create_impl(altro_hip_batch** out, int N, int n, int m, int bat
     ALLOC(h->l_term, B * z.e_term * E);
     ALLOC(h->l_out, B * N * z.e_out * E);
     ALLOC(h->l_outn, B * z.e_term * E);
-    ALLOC(h->l_xuy, B * (N + 1) * z.e_xuy * E);
+    ALLOC_ZERO(h->l_xuy, B * (N + 1) * z.e_xuy * E);
     ALLOC(h->l_x0, B * n * E);
     ALLOC(h->l_nom, B * (N + 1) * (n + m) * E);
-    ALLOC(h->l_cost, B * (N + 1) * (2 * n + 2 * m + 1) * E);
-    // on the handle's own (non-blocking) stream: a null-stream memset would race the first kernels launched on it
-    if (!rc && hipMemsetAsync(h->l_xuy, 0, B * (N + 1) * z.e_xuy * E, h->stream) != hipSuccess) rc = fail(ALTRO_HIP_ERR_HIP, "memset failed");
-    if (!rc && hipMemsetAsync(h->l_cost, 0, B * (N + 1) * (2 * n + 2 * m + 1) * E, h->stream) != hipSuccess) rc = fail(ALTRO_HIP_ERR_HIP, "memset failed");
+    ALLOC_ZERO(h->l_cost, B * (N + 1) * (2 * n + 2 * m + 1) * E);
   } else {
     // block sizes of knot point k (tvlqr.cpp:92-121: A_k is nx[k+1] x nx[k], B_k nx[k+1] x nu[k], K_k nu[k] x nx[k], ...)
     std::vector<int> nx(N + 1, n), nu(N + 1, m);
@@ -208,12 +206,10 @@ static int batch_create_impl(altro_hip_batch** out, int N, int n, int m, int bat
       for (int k = 0; k <= N; ++k) { off[(size_t)k * G_NUM + a] = at; if (k < nks[a]) at += blk_at(a, k); }
       h->g_bstride[a] = at;
       if (qb && !(flags & ALTRO_HIP_STORE_QBLOCKS)) continue;
-      ALLOC(h->g_arr[a], B * (size_t)at * E);
+      ALLOC_ZERO(h->g_arr[a], B * (size_t)at * E);
       // everything defined (zero) from the start: the candidate trajectory, so that altro_hip_set_input_guess / _set_state_guess may come
       // in any order with the cost; the gains, so that the forward sweep of a problem whose backward sweep stopped at a failed
       // factorisation (its K, d below the failing knot point are never written) rolls out finite numbers
-      if (!rc && hipMemsetAsync(h->g_arr[a], 0, B * (size_t)at * E, h->stream) != hipSuccess)
-        rc = fail(ALTRO_HIP_ERR_HIP, "memset failed");
     }
     ALLOC(h->g_off, off.size() * sizeof(int64_t));
     ALLOC(h->g_nx, (size_t)(N + 1) * sizeof(int));
@@ -232,14 +228,12 @@ static int batch_create_impl(altro_hip_batch** out, int N, int n, int m, int bat
     ALLOC(h->i_phi, B * 8 * ILQR_SPEC_TRIALS);
     ALLOC(h->i_spec_sel, B * sizeof(int));
     ALLOC(h->i_spec_refresh, B * sizeof(int));
-    ALLOC(h->i_guard, B * sizeof(int));
-    ALLOC(h->i_active_exact, B * sizeof(int));
-    if (!rc && (hipMemsetAsync(h->i_guard, 0, B * sizeof(int), h->stream) != hipSuccess || hipMemsetAsync(h->i_active_exact, 0, B * sizeof(int), h->stream) != hipSuccess)) rc = fail(ALTRO_HIP_ERR_HIP, "memset failed");
+    ALLOC_ZERO(h->i_guard, B * sizeof(int));
+    ALLOC_ZERO(h->i_active_exact, B * sizeof(int));
     ALLOC(h->i_stat_done, B * sizeof(int));
     ALLOC(h->i_dphi, B * 8 * 2);
     ALLOC(h->i_active, B * sizeof(int));
-    ALLOC(h->i_counters, (size_t)kCounterSlots * 8 * sizeof(int));
-    if (!rc && hipMemsetAsync(h->i_counters, 0, (size_t)kCounterSlots * 8 * sizeof(int), h->stream) != hipSuccess) rc = fail(ALTRO_HIP_ERR_HIP, "memset failed");
+    ALLOC_ZERO(h->i_counters, (size_t)kCounterSlots * 8 * sizeof(int));
     ALLOC(h->i_reg, B * 8);
     if (!rc) {   // every constraint starts with penalty 1 (knotpoint_data.cpp:343)
       std::vector<IlqrProb> pr((size_t)B);
@@ -250,6 +244,7 @@ static int batch_create_impl(altro_hip_batch** out, int N, int n, int m, int bat
     }
   }
 #undef ALLOC
+#undef ALLOC_ZERO
   if (!rc && (hipEventCreate(&h->ev0) != hipSuccess || hipEventCreate(&h->ev1) != hipSuccess))
     rc = fail(ALTRO_HIP_ERR_HIP, "hipEventCreate failed");
   if (rc) {
@@ -320,20 +315,8 @@ void altro_hip_batch_destroy(altro_hip_batch* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  void* ptrs[] = {h->x0, h->delta_V, h->status, h->m_in, h->m_cin, h->m_term, h->m_out, h->m_outn, h->m_xuy,
-                  h->m_qblk, h->m_trash, h->g_off, h->g_nx, h->g_nu, h->stage,
-                  h->l_in, h->l_term, h->l_out, h->l_outn, h->l_xuy, h->l_x0,
-                  h->l_nom, h->l_cost, h->g_ws, h->i_prob, h->i_alpha, h->i_phi, h->i_dphi, h->i_active, h->i_counters,
-                  h->al_d_knots, h->al_d_big, h->al_d_gsel, h->al_d_guser, h->al_d_order, h->al_d_start, h->g_stat_part, h->al_d_G, h->al_d_Gpad, h->al_d_g, h->al_d_z, h->i_reg, h->m_nom, h->m_costp,
-                  h->i_cand_spec, h->i_spec_sel, h->i_spec_refresh, h->i_fused_list, h->i_guard, h->i_active_exact, h->i_stat_done, h->st_partial, h->st_red, h->i_merit_jk, h->i_spec_jac, h->i_results,
-                  h->m_costd, h->m_costd_term, h->l_costq, h->i_sens, h->i_sens_alpha, h->i_aff_part, h->i_aff_on, h->g_xn, h->g_un, h->g_cQ, h->g_cR, h->g_cH, h->g_cq, h->g_cr, h->g_cc, h->d_hk, h->d_theta};
-  for (void* p : ptrs) if (p) (void)hipFree(p);
-  if (h->i_results_host) (void)hipHostFree(h->i_results_host);
-  if (h->poll_host) (void)hipHostFree(h->poll_host);
-  if (h->poll_count_host) (void)hipHostFree(h->poll_count_host);
-  if (h->cnt_host) (void)hipHostFree(h->cnt_host);
+  h->ledger.drain(hipFree, hipHostFree);   // every buffer the handle allocated, device and pinned (capi_internal.h: dmalloc, hmalloc_quiet)
   for (hipEvent_t e : h->cnt_ev) if (e) (void)hipEventDestroy(e);
-  for (int a = 0; a < G_NUM; ++a) if (h->g_arr[a]) (void)hipFree(h->g_arr[a]);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   for (hipEvent_t e : h->prof_ev) if (e) (void)hipEventDestroy(e);
@@ -342,7 +325,7 @@ void altro_hip_batch_destroy(altro_hip_batch* h) {
 }
 
 int altro_hip_batch_plan(const altro_hip_batch* h) { return h ? (h->g_tile ? (int)ALTRO_HIP_PLAN_MFMA32 : h->plan) : ALTRO_HIP_ERR_BAD_ARGUMENT; }
-size_t altro_hip_batch_device_bytes(const altro_hip_batch* h) { return h ? h->device_bytes : 0; }
+size_t altro_hip_batch_device_bytes(const altro_hip_batch* h) { return h ? h->ledger.counted_bytes() : 0; }
 
 int altro_hip_set_dynamics(altro_hip_batch* h, const double* A, const double* B, const double* f,
                            int kz, int bz) {

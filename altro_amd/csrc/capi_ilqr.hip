@@ -33,7 +33,7 @@ static int al_copy_pool(altro_hip_batch* h, void** dst, const std::vector<double
 static int al_upload_tables(altro_hip_batch* h) {
   for (void** p : {(void**)&h->al_d_knots, (void**)&h->al_d_big, (void**)&h->al_d_gsel, (void**)&h->al_d_guser, &h->al_d_G, &h->al_d_Gpad, &h->al_d_g, &h->al_d_z,
                    (void**)&h->al_d_order, (void**)&h->al_d_start})
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
+    dfree(h, p);
   h->al_sum = AlSummary{}; h->al_rows = 0; h->al_nchains = 0;   // (nothing on the device: what a handle without blocks has)
   const AlTables t = al_build(al_input(h));
   if (t.error == AL_BUILD_SLOTS)
@@ -51,9 +51,7 @@ static int al_upload_tables(altro_hip_batch* h) {
   if ((rc = al_copy_pool(h, &h->al_d_g, t.g))) return rc;
   if (!t.Gpad.empty() && (rc = al_copy_pool(h, &h->al_d_Gpad, t.Gpad))) return rc;
   const size_t zbytes = (size_t)t.rows * h->batch * (h->dtype == ALTRO_HIP_F64 ? sizeof(double) : sizeof(float));
-  if ((rc = dmalloc(h, &h->al_d_z, zbytes))) return rc;
-  // (memsets go on the handle's own stream: it is non-blocking, so a null-stream memset would race the kernels)
-  HIP_TRY(hipMemsetAsync(h->al_d_z, 0, zbytes, h->stream));
+  if ((rc = dmalloc_zero(h, &h->al_d_z, zbytes))) return rc;
   // altro_hip_shift_duals' chains: the rows of one block definition at consecutive knot points, in walking order (al_shift.h)
   const AlShift sh = al_shift_build(t.big, h->al_defs, t.rows);
   if ((rc = al_copy(h, (void**)&h->al_d_order, sh.order.data(), sh.order.size() * sizeof(int)))) return rc;
@@ -119,11 +117,11 @@ bool ensure_spares(altro_hip_batch* h, int count, size_t bytes_each) {
   if (h->spare_count >= count) return true;
   if (h->spare_failed > 0 && count >= h->spare_failed) return false;   // this size did not fit before: do not ask again
   void* fresh = nullptr;
-  if (hipMalloc(&fresh, (size_t)count * bytes_each) != hipSuccess) { (void)hipGetLastError(); h->spare_failed = count; return false; }
-  if (h->i_cand_spec) { (void)hipStreamSynchronize(h->stream); (void)hipFree(h->i_cand_spec); h->device_bytes -= (size_t)h->spare_count * bytes_each; }
+  if (dmalloc_quiet(h, &fresh, (size_t)count * bytes_each, true) != hipSuccess) { (void)hipGetLastError(); h->spare_failed = count; return false; }
+  if (h->i_cand_spec) (void)hipStreamSynchronize(h->stream);
+  dfree(h, &h->i_cand_spec);
   h->i_cand_spec = fresh;
   h->spare_count = count;
-  h->device_bytes += (size_t)count * bytes_each;
   return true;
 }
 // The buffers of the three-launch merit evaluation (first use).  No memory for them: the one-launch kernel, for good.
@@ -135,7 +133,7 @@ void merit_split_prepare(altro_hip_batch* h) {
   const size_t jac = ((size_t)h->N * (h->n * h->n + h->n * h->m + h->n + h->m) + h->n) * h->batch * h->esz;
   if (dmalloc(h, &h->i_merit_jk, jk) || dmalloc(h, &h->i_spec_jac, jac)) {
     (void)hipGetLastError();
-    if (h->i_merit_jk) { (void)hipFree(h->i_merit_jk); h->i_merit_jk = nullptr; }
+    dfree(h, &h->i_merit_jk);
     h->merit_split = 0;
   }
 }
@@ -158,14 +156,13 @@ bool affine_buffers(altro_hip_batch* h) {
   // runs a large batch out of memory
   const size_t B = h->batch, chunks = (h->N + 15) / 16;
   const size_t sens_bytes = B * (h->N + 1) * 24 * sizeof(double);
-  int rc = sens_bytes > h->device_bytes / 4 + (size_t(64) << 20) ? 1 : 0;
+  int rc = sens_bytes > h->ledger.counted_bytes() / 4 + (size_t(64) << 20) ? 1 : 0;
   if (!rc) rc = dmalloc(h, &h->i_sens, sens_bytes);
   if (!rc) rc = dmalloc(h, &h->i_sens_alpha, B * sizeof(double));
   if (!rc) rc = dmalloc(h, &h->i_aff_part, chunks * ILQR_SPEC_TRIALS * B * 2 * sizeof(double));
-  if (!rc) rc = dmalloc(h, &h->i_aff_on, (size_t)ILQR_SPEC_TRIALS * B * sizeof(int));
-  if (!rc && hipMemsetAsync(h->i_aff_on, 0, (size_t)ILQR_SPEC_TRIALS * B * sizeof(int), h->stream) != hipSuccess) rc = 1;
+  if (!rc) rc = dmalloc_zero(h, &h->i_aff_on, (size_t)ILQR_SPEC_TRIALS * B * sizeof(int));
   if (rc) {   // an optimisation only: this handle's rounds stay rollouts
-    for (void** q : {&h->i_sens, &h->i_sens_alpha, &h->i_aff_part, &h->i_aff_on}) { if (*q) (void)hipFree(*q); *q = nullptr; }
+    for (void** q : {&h->i_sens, &h->i_sens_alpha, &h->i_aff_part, &h->i_aff_on}) dfree(h, q);
     h->aff_failed = true;
     (void)hipGetLastError();
   }
@@ -308,10 +305,9 @@ int gen_run(altro_hip_batch* h, const LoopCall& c) {
   a.row32m = row32_model_eligible(shape) ? 1 : 0;
   if ((a.row32 || a.row32m) && which == IK_STATIONARITY && N > R32_STAT_CHUNK) {   // the stationarity walk in chunks of knot points: their maxima meet here
     const size_t need = (size_t)((N + R32_STAT_CHUNK - 1) / R32_STAT_CHUNK) * h->batch * 2 * sizeof(double);
-    if (h->g_stat_part_bytes < need) {
-      if (h->g_stat_part) { (void)hipFree(h->g_stat_part); h->g_stat_part = nullptr; h->g_stat_part_bytes = 0; }
-      if (hipMalloc((void**)&h->g_stat_part, need) == hipSuccess) h->g_stat_part_bytes = need;
-      else { (void)hipGetLastError(); h->g_stat_part = nullptr; }   // (an optimisation only: one chunk then)
+    if (h->ledger.bytes_of(h->g_stat_part) < need) {   // (not counted: the handle's, but not part of altro_hip_batch_device_bytes)
+      dfree(h, &h->g_stat_part);
+      if (dmalloc_quiet(h, (void**)&h->g_stat_part, need, false) != hipSuccess) (void)hipGetLastError();   // (an optimisation only: one chunk then)
     }
     a.stat_part = h->g_stat_part;
   }
@@ -373,8 +369,7 @@ int generic_cost_def(altro_hip_batch* h, const double* Q, const double* R, const
         {&h->g_xn, B * gs.sx * E, true},  {&h->g_un, B * gs.su * E, true}};
     for (auto& w : want) {
       if (*w.p) continue;
-      if ((rc = dmalloc(h, w.p, w.bytes))) return rc;
-      if (w.zero) HIP_TRY(hipMemsetAsync(*w.p, 0, w.bytes, h->stream));
+      if ((rc = w.zero ? dmalloc_zero(h, w.p, w.bytes) : dmalloc(h, w.p, w.bytes))) return rc;
     }
     // the candidate inputs (g_arr[G_u]) are NOT touched here: altro_hip_set_input_guess may come before the cost, like the reference's
     // SetInput may; they are zeroed once, when the handle is created
@@ -420,7 +415,7 @@ int ilqr_check(altro_hip_batch* h, bool need_guess) {
 }
 
 // A device model on plan GENERIC or MFMA16: A_k, B_k (plan MFMA16: the DYN records, Z = [A B]) are the EXPANSION's from now on, written
-// by the expansion / merit kernels, and f = 0.  (memsets on the handle's own stream: see al_upload_tables)
+// by the expansion / merit kernels, and f = 0.  (memsets on the handle's own stream: see dmalloc_zero)
 int model_takes_dynamics(altro_hip_batch* h) {
   if (h->plan == ALTRO_HIP_PLAN_GENERIC) for (int a : {G_f, G_A, G_B}) HIP_TRY(hipMemsetAsync(h->g_arr[a], 0, (size_t)h->batch * h->g_bstride[a] * h->esz, h->stream));
   if (h->plan == ALTRO_HIP_PLAN_MFMA16) HIP_TRY(hipMemsetAsync(h->m_in, 0, (size_t)h->batch * h->N * MF_DYN * h->esz, h->stream));
@@ -594,10 +589,8 @@ int altro_hip_set_tracking_cost(altro_hip_batch* h, const double* Qd, const doub
     // (b) the cost parameters the merit function needs: COSTP records [k][b][36] = Qd | Rd | q | r | c
     const int64_t B = h->batch;
     if (!h->m_costp) {
-      if ((rc = dmalloc(h, &h->m_costp, (size_t)B * (N + 1) * MF_COSTP * h->esz))) return rc;
-      if ((rc = dmalloc(h, &h->m_nom, (size_t)B * (N + 1) * MF_NOM * h->esz))) return rc;
-      HIP_TRY(hipMemsetAsync(h->m_costp, 0, (size_t)B * (N + 1) * MF_COSTP * h->esz, h->stream));
-      HIP_TRY(hipMemsetAsync(h->m_nom, 0, (size_t)B * (N + 1) * MF_NOM * h->esz, h->stream));
+      if ((rc = dmalloc_zero(h, &h->m_costp, (size_t)B * (N + 1) * MF_COSTP * h->esz))) return rc;
+      if ((rc = dmalloc_zero(h, &h->m_nom, (size_t)B * (N + 1) * MF_NOM * h->esz))) return rc;
     }
   }
   // plans MFMA16 and LANE: the diagonal cost's record Qd | Rd | q | r | c of every knot point (record N: Qd, q, c)
@@ -638,15 +631,10 @@ int altro_hip_set_quadratic_cost(altro_hip_batch* h, const double* Q, const doub
     if (rc) return rc;
     // (b) the cost's own record, in the COST / TERM layout, for the merit function and the expansion
     if (!h->m_costd) {
-      if ((rc = dmalloc(h, &h->m_costd, (size_t)B * (N + 1) * MF_COST * Ez))) return rc;
-      if ((rc = dmalloc(h, &h->m_costd_term, (size_t)B * MF_TERM * Ez))) return rc;
-      HIP_TRY(hipMemsetAsync(h->m_costd, 0, (size_t)B * (N + 1) * MF_COST * Ez, h->stream));
-      HIP_TRY(hipMemsetAsync(h->m_costd_term, 0, (size_t)B * MF_TERM * Ez, h->stream));
+      if ((rc = dmalloc_zero(h, &h->m_costd, (size_t)B * (N + 1) * MF_COST * Ez))) return rc;
+      if ((rc = dmalloc_zero(h, &h->m_costd_term, (size_t)B * MF_TERM * Ez))) return rc;
     }
-    if (!h->m_nom) {
-      if ((rc = dmalloc(h, &h->m_nom, (size_t)B * (N + 1) * MF_NOM * Ez))) return rc;
-      HIP_TRY(hipMemsetAsync(h->m_nom, 0, (size_t)B * (N + 1) * MF_NOM * Ez, h->stream));
-    }
+    if (!h->m_nom && (rc = dmalloc_zero(h, &h->m_nom, (size_t)B * (N + 1) * MF_NOM * Ez))) return rc;
     {
       Dims d{n, m};
       DevSrc dQ, dR, dH, dq, dr;
@@ -685,10 +673,7 @@ int altro_hip_set_quadratic_cost(altro_hip_batch* h, const double* Q, const doub
   const int E = loop_field(s, LF_COST_c, 0).E;
   if ((uint64_t)B * (uint64_t)E * Ez >= (1ull << 31))
     return fail(ALTRO_HIP_ERR_UNSUPPORTED, "plan LANE: batch %d too large for one handle (dense cost rows exceed 2 GiB)", h->batch);
-  if (!h->l_costq) {
-    if ((rc = dmalloc(h, &h->l_costq, (size_t)B * (N + 1) * E * Ez))) return rc;
-    HIP_TRY(hipMemsetAsync(h->l_costq, 0, (size_t)B * (N + 1) * E * Ez, h->stream));
-  }
+  if (!h->l_costq && (rc = dmalloc_zero(h, &h->l_costq, (size_t)B * (N + 1) * E * Ez))) return rc;
   const CostUpload up[] = {{LF_COST_Q, Q, nkx}, {LF_COST_R, R, nku}, {LF_COST_H, H, nku}, {LF_COST_q, q, nkx}, {LF_COST_r, r, nku}, {LF_COST_c, c, nkx}};   // (c == NULL: zeros)
   rc = cost_fields_set(h, true, up, 6, kz, bz);
   if (!rc) { h->lqr_cost_set = true; h->cost_set = true; h->dyn_set = true; h->is_diag = 0; h->has_f = 0; h->cost_dense = true; }
@@ -1097,7 +1082,7 @@ int altro_hip::capi::ilqr_gather_results(altro_hip_batch* h, altro_hip_solve_res
   const size_t bytes = (size_t)h->batch * sizeof(IlqrResult);
   if (!h->i_results) {
     if ((rc = dmalloc(h, &h->i_results, bytes))) return rc;
-    if (hipHostMalloc(&h->i_results_host, bytes, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h->i_results_host = nullptr; }
+    if (hmalloc_quiet(h, &h->i_results_host, bytes, false) != hipSuccess) (void)hipGetLastError();
   }
   if (ilqr_launch_results(h->stream, h->i_prob, (IlqrResult*)h->i_results, h->batch)) return fail(ALTRO_HIP_ERR_HIP, "results kernel launch failed");
   void* stage = h->i_results_host ? h->i_results_host : (void*)results;
@@ -1169,8 +1154,8 @@ int altro_hip_set_forms(altro_hip_batch* h, unsigned forms) {
     return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "ALTRO_HIP_FORM_GENERIC_LATE_Q_OFF and _ON exclude each other");
   if (((h->forms ^ forms) & ALTRO_HIP_FORM_MERIT_ONE_LAUNCH) && h->merit_split >= 0) {   // decided at the first evaluation: decide again
     HIP_TRY(hipStreamSynchronize(h->stream));
-    if (h->i_merit_jk) { (void)hipFree(h->i_merit_jk); h->i_merit_jk = nullptr; }
-    if (h->i_spec_jac) { (void)hipFree(h->i_spec_jac); h->i_spec_jac = nullptr; }
+    dfree(h, &h->i_merit_jk);
+    dfree(h, &h->i_spec_jac);
     h->merit_split = -1;
   }
   h->forms = forms;

@@ -25,6 +25,7 @@
 #include "linesearch_sm.h"
 #include "al_tables.h"
 #include "al_shift.h"
+#include "device_ledger.h"
 #include "loop_fields.h"
 #include "loop_route.h"
 #include "rtc_unit.h"
@@ -134,7 +135,6 @@ struct altro_hip_batch {
   // at it.  altro_hip_set_model / _set_model_source / _set_model_source_params drop all three (model_params_drop).
   int model_np = 0;
   void* d_theta = nullptr;
-  size_t d_theta_bytes = 0;
   std::vector<double> theta_host;
   bool model_set = false, lqr_cost_set = false, guess_set = false;
   std::vector<double> x0_host;    // the initial state as given, while the handle may still move to another plan (replan_empty_handle)
@@ -153,7 +153,7 @@ struct altro_hip_batch {
   AlKnotBig* al_d_big = nullptr;
   void *al_d_G = nullptr, *al_d_g = nullptr, *al_d_z = nullptr;
   void* al_d_Gpad = nullptr;                 // AlTable::Gpad (plan MFMA16)
-  double* g_stat_part = nullptr; size_t g_stat_part_bytes = 0;   // row32_stationarity_kernel's per-chunk maxima (capi_ilqr.hip: gen_run)
+  double* g_stat_part = nullptr;   // row32_stationarity_kernel's per-chunk maxima (capi_ilqr.hip: gen_run)
   int* al_d_gsel = nullptr;              // plan GENERIC: AlTable::gsel (bound-type blocks)
   int* al_d_guser = nullptr;             // plan GENERIC: AlTable::guser (blocks from the caller's source), null without such a block
   int *al_d_order = nullptr, *al_d_start = nullptr;   // altro_hip_shift_duals' chains of dual rows (al_shift.h: AlShift::order, ::start), every plan
@@ -178,7 +178,9 @@ struct altro_hip_batch {
   // staging for host <-> device conversion (grown lazily, never inside the hot path)
   void* stage = nullptr;
   size_t stage_bytes = 0;
-  size_t device_bytes = 0;
+  // every buffer above that the handle allocated, device or pinned, with its size (device_ledger.h): dmalloc / dfree below keep it,
+  // altro_hip_batch_destroy drains it, altro_hip_batch_device_bytes is its counted sum
+  capi::DeviceLedger ledger;
   // statistics reduction (capi_stats.hip): per-block partials and the reduced vector, on the device
   double *st_partial = nullptr, *st_red = nullptr;
   bool solve_done = false;   // altro_hip_ilqr_solve has run: the per-problem control blocks hold AltroStats
@@ -202,25 +204,53 @@ namespace capi {
 
 inline bool form(const altro_hip_batch* h, unsigned bit) { return (h->forms & bit) != 0; }
 
+// ---- the handle's buffers: every one is allocated and freed here, and listed in altro_hip_batch::ledger in between ----------------
+// A device buffer of the handle's, with no message on failure (*p is null then).  `counted`: part of altro_hip_batch_device_bytes --
+// everything but the staging buffer and the stationarity partials.
+inline hipError_t dmalloc_quiet(altro_hip_batch* h, void** p, size_t bytes, bool counted) {
+  const hipError_t e = hipMalloc(p, bytes ? bytes : 16);
+  if (e != hipSuccess) *p = nullptr;
+  else h->ledger.add(*p, bytes, MEM_DEVICE, counted);
+  return e;
+}
 inline int dmalloc(altro_hip_batch* h, void** p, size_t bytes) {
-  hipError_t e = hipMalloc(p, bytes ? bytes : 16);
-  if (e != hipSuccess) {
-    *p = nullptr;
-    return fail(ALTRO_HIP_ERR_OUT_OF_MEMORY, "hipMalloc(%zu bytes) failed: %s", bytes,
-                hipGetErrorString(e));
-  }
-  h->device_bytes += bytes;
+  const hipError_t e = dmalloc_quiet(h, p, bytes, true);
+  if (e != hipSuccess)
+    return fail(ALTRO_HIP_ERR_OUT_OF_MEMORY, "hipMalloc(%zu bytes) failed: %s", bytes, hipGetErrorString(e));
   return 0;
+}
+// ... that reads as zero to everything enqueued after it (the memset goes on the handle's own stream: that stream is non-blocking, so a
+// null-stream memset would race the first kernels launched on it)
+inline int dmalloc_zero(altro_hip_batch* h, void** p, size_t bytes) {
+  if (const int rc = dmalloc(h, p, bytes)) return rc;
+  HIP_TRY(hipMemsetAsync(*p, 0, bytes, h->stream));
+  return 0;
+}
+// pinned host memory of the handle's (never counted: altro_hip_batch_device_bytes is device memory); `mapped`: the device reads and
+// writes it in place, coherently
+inline hipError_t hmalloc_quiet(altro_hip_batch* h, void** p, size_t bytes, bool mapped) {
+  const hipError_t e = hipHostMalloc(p, bytes, mapped ? hipHostMallocMapped | hipHostMallocCoherent : hipHostMallocDefault);
+  if (e != hipSuccess) *p = nullptr;
+  else h->ledger.add(*p, bytes, MEM_PINNED, false);
+  return e;
+}
+// Frees a buffer of either kind and nulls the field; nothing on null.  There is NO synchronisation in here: where launches in flight may
+// still read the buffer, the caller waits for the stream first.
+template <typename T>
+inline void dfree(altro_hip_batch* h, T** p) {
+  LedgerEntry e;
+  if (*p && h->ledger.remove(*p, &e)) {
+    if (e.kind == MEM_PINNED) (void)hipHostFree(e.p);
+    else (void)hipFree(e.p);
+  }
+  *p = nullptr;
 }
 
 // a new model: the parameters of the last one go (the array is sized by ITS count); launches in flight may still read them
 inline void model_params_drop(altro_hip_batch* h) {
-  if (h->d_theta) {
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(h->d_theta);
-    h->device_bytes -= h->d_theta_bytes;
-  }
-  h->d_theta = nullptr; h->d_theta_bytes = 0; h->model_np = 0;
+  if (h->d_theta) (void)hipStreamSynchronize(h->stream);
+  dfree(h, &h->d_theta);
+  h->model_np = 0;
   h->model.theta = nullptr; h->model.theta_bs = 0;
   h->theta_host.clear();
 }
@@ -248,10 +278,9 @@ inline int loop_entry(altro_hip_batch* h, bool takes_varying_dims = false) {
 
 inline int ensure_stage(altro_hip_batch* h, size_t bytes) {
   if (h->stage_bytes >= bytes) return 0;
-  if (h->stage) (void)hipFree(h->stage);
-  h->stage = nullptr;
+  dfree(h, &h->stage);
   h->stage_bytes = 0;
-  hipError_t e = hipMalloc(&h->stage, bytes);
+  const hipError_t e = dmalloc_quiet(h, &h->stage, bytes, false);
   if (e != hipSuccess)
     return fail(ALTRO_HIP_ERR_OUT_OF_MEMORY, "staging hipMalloc(%zu) failed: %s", bytes,
                 hipGetErrorString(e));
@@ -435,10 +464,19 @@ inline int mfma16_get(altro_hip_batch* h, int what, double* host, int block, int
 
 // Whole-array upload of one reference-layout source for the MFMA16 pack kernels (setup path).
 // `nk_host` = knot points per problem actually present in the host array.
+// (a device buffer that lives for one call: the call's, not the handle's -- not in the ledger, not in altro_hip_batch_device_bytes)
+struct DevTemp {
+  void* p = nullptr;
+  DevTemp() = default;
+  DevTemp(const DevTemp&) = delete;
+  DevTemp& operator=(const DevTemp&) = delete;
+  ~DevTemp() { if (p) (void)hipFree(p); }
+  bool alloc(size_t bytes) { return hipMalloc(&p, bytes) == hipSuccess; }
+  template <typename T> T* as() const { return (T*)p; }
+};
 struct DevSrc {
-  void* dev = nullptr;
+  DevTemp dev;
   SrcArr s{nullptr, 0, 0, 0};
-  ~DevSrc() { if (dev) (void)hipFree(dev); }
 };
 inline int put_src(altro_hip_batch* h, const double* src, int blk, int nk_host, int k_zero, int b_zero,
             DevSrc* out) {
@@ -450,11 +488,11 @@ inline int put_src(altro_hip_batch* h, const double* src, int blk, int nk_host, 
     out->s = SrcArr{src, b_zero ? 0 : (int64_t)per_b, k_zero ? 0 : (int64_t)blk, tiled};
     return 0;
   }
-  if (hipMalloc(&out->dev, bytes) != hipSuccess)
+  if (!out->dev.alloc(bytes))
     return fail(ALTRO_HIP_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) failed", bytes);
-  if (hipMemcpyAsync(out->dev, src, bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess)
+  if (hipMemcpyAsync(out->dev.p, src, bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess)
     return fail(ALTRO_HIP_ERR_HIP, "H2D copy failed");
-  out->s = SrcArr{(const double*)out->dev, b_zero ? 0 : (int64_t)per_b, k_zero ? 0 : (int64_t)blk, tiled};
+  out->s = SrcArr{out->dev.as<const double>(), b_zero ? 0 : (int64_t)per_b, k_zero ? 0 : (int64_t)blk, tiled};
   return 0;
 }
 // (cin / term: the COST and TERM records to fill -- the handle's own, or the dense cost's copies m_costd / m_costd_term, which

@@ -327,10 +327,7 @@ int altro_hip_set_model_params(altro_hip_batch* h, const double* theta, int batc
       if (f64) { ((double*)dev.data())[(size_t)i * B + b] = v; kept[b * P + i] = v; }
       else { const float f = (float)v; ((float*)dev.data())[(size_t)i * B + b] = f; kept[b * P + i] = (double)f; }
     }
-  if (!h->d_theta) {
-    if ((rc = dmalloc(h, &h->d_theta, bytes))) return rc;
-    h->d_theta_bytes = bytes;
-  }
+  if (!h->d_theta && (rc = dmalloc(h, &h->d_theta, bytes))) return rc;
   // (on the handle's own stream: launches already enqueued read the old values, later ones the new)
   HIP_TRY(hipMemcpyAsync(h->d_theta, dev.data(), bytes, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));

@@ -186,7 +186,7 @@ int SolveRun::configure(const altro_hip_solve_options* opts) {
 // AHEAD of a verdict it has not read yet.
 int SolveRun::ensure_counters() {
   if (h->cnt_host) return 0;
-  if (hipHostMalloc((void**)&h->cnt_host, (size_t)kCounterSlots * 8 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
+  if (hmalloc_quiet(h, (void**)&h->cnt_host, (size_t)kCounterSlots * 8 * sizeof(int), true) != hipSuccess) {
     (void)hipGetLastError();
     return fail(ALTRO_HIP_ERR_OUT_OF_MEMORY, "pinned host memory for the solve loop's counters");
   }
@@ -222,9 +222,10 @@ int SolveRun::choose_path() {
                                              "device model and a uniform time step, default environment); use altro_hip_ilqr_solve");
     const size_t bytes = (size_t)h->batch * sizeof(IlqrPollRec);
     if (!h->poll_host) {
-      if (hipHostMalloc(&h->poll_host, bytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-          hipHostMalloc((void**)&h->poll_count_host, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
+      if (hmalloc_quiet(h, &h->poll_host, bytes, true) != hipSuccess ||
+          hmalloc_quiet(h, (void**)&h->poll_count_host, 64, true) != hipSuccess) {
         (void)hipGetLastError();
+        dfree(h, &h->poll_host);   // both or neither: the next call asks again
         return fail(ALTRO_HIP_ERR_OUT_OF_MEMORY, "pinned host memory for %d poll records", h->batch);
       }
     }
@@ -318,10 +319,10 @@ int SolveRun::run_fused() {
   }
   const int clk_G = ilqr_fused_group(h->batch);
   const int clk_groups = (h->batch + clk_G - 1) / clk_G;
-  unsigned long long* clk = nullptr;     // ALTRO_HIP_FORM_FUSED_CLOCK: per-phase time of the kernel, printed to stderr (a tuning aid)
+  DevTemp clk;     // ALTRO_HIP_FORM_FUSED_CLOCK: per-phase time of the kernel, printed to stderr (a tuning aid); freed on every way out
   if (clock_on) {
     const size_t bytes = (size_t)clk_groups * ILQR_FUSED_PHASES * sizeof(unsigned long long);
-    if (hipMalloc((void**)&clk, bytes) == hipSuccess) { (void)hipMemsetAsync(clk, 0, bytes, h->stream); fa.clk = clk; }
+    if (clk.alloc(bytes)) { (void)hipMemsetAsync(clk.p, 0, bytes, h->stream); fa.clk = clk.as<unsigned long long>(); }
   }
   LoopCall mc = call(IK_MERIT);   // (the kernel's own merit evaluations: one trial, the solve's search options)
   mc.want_deriv = 1;
@@ -350,7 +351,7 @@ int SolveRun::run_fused() {
                          nullptr, nullptr};
       frc = ilqr_launch_fused<float>(h->stream, h->model.kind, h->n, h->m, ilqr_args<float>(h, mc), la, ba, fa);
     }
-    if (frc) { if (clk) (void)hipFree(clk); return fail(ALTRO_HIP_ERR_HIP, "fused iLQR kernel launch failed"); }
+    if (frc) return fail(ALTRO_HIP_ERR_HIP, "fused iLQR kernel launch failed");
     h->backward_done = true;
     if (async) {   // the caller polls; altro_hip_ilqr_wait finishes the bookkeeping
       h->async_pending = true;
@@ -358,10 +359,8 @@ int SolveRun::run_fused() {
       h->solve_done = true;
       return 0;
     }
-    if (fa.run_flags && ilqr_launch_list_running(h->stream, flags, fa.list, slots, lists[pp], h->fused_resident)) {
-      if (clk) (void)hipFree(clk);
+    if (fa.run_flags && ilqr_launch_list_running(h->stream, flags, fa.list, slots, lists[pp], h->fused_resident))
       return fail(ALTRO_HIP_ERR_HIP, "list kernel launch failed");
-    }
     int c4[4];
     HIP_TRY(hipMemcpyAsync(c4, h->i_counters, sizeof(c4), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -373,10 +372,9 @@ int SolveRun::run_fused() {
     fa.list = lists[pp]; fa.list_count = slots = fa.group * groups;
     pp ^= 1;
   }
-  if (clk) {
+  if (clk.p) {
     std::vector<unsigned long long> hc((size_t)clk_groups * ILQR_FUSED_PHASES);
-    (void)hipMemcpy(hc.data(), clk, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    (void)hipFree(clk);
+    (void)hipMemcpy(hc.data(), clk.p, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost);
     print_fused_clock(hc, clk_groups, sweeps);
   }
   iter0 = running > 0 ? budget : o.iterations_max;

@@ -353,21 +353,14 @@ __global__ void sincos_selftest_kernel(const double* x, int n, double* s, double
 int altro_hip_selftest_sincos(int device, const double* x, int n, double* s, double* c) {
   if (!x || !s || !c || n <= 0) return ALTRO_HIP_ERR_BAD_ARGUMENT;
   if (hipSetDevice(device) != hipSuccess) return ALTRO_HIP_ERR_NO_DEVICE;
-  double *dx = nullptr, *ds = nullptr, *dc = nullptr;
+  DevTemp dx, ds, dc;
   const size_t bytes = (size_t)n * sizeof(double);
-  int rc = 0;
-  if (hipMalloc((void**)&dx, bytes) != hipSuccess || hipMalloc((void**)&ds, bytes) != hipSuccess ||
-      hipMalloc((void**)&dc, bytes) != hipSuccess) rc = ALTRO_HIP_ERR_OUT_OF_MEMORY;
-  if (!rc && hipMemcpy(dx, x, bytes, hipMemcpyHostToDevice) != hipSuccess) rc = ALTRO_HIP_ERR_HIP;
-  if (!rc) {
-    hipLaunchKernelGGL(sincos_selftest_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, dx, n, ds, dc);
-    if (hipMemcpy(s, ds, bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(c, dc, bytes, hipMemcpyDeviceToHost) != hipSuccess)
-      rc = ALTRO_HIP_ERR_HIP;
-  }
-  if (dx) (void)hipFree(dx);
-  if (ds) (void)hipFree(ds);
-  if (dc) (void)hipFree(dc);
-  return rc;
+  if (!dx.alloc(bytes) || !ds.alloc(bytes) || !dc.alloc(bytes)) return ALTRO_HIP_ERR_OUT_OF_MEMORY;
+  if (hipMemcpy(dx.p, x, bytes, hipMemcpyHostToDevice) != hipSuccess) return ALTRO_HIP_ERR_HIP;
+  hipLaunchKernelGGL(sincos_selftest_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, dx.as<const double>(), n, ds.as<double>(), dc.as<double>());
+  if (hipMemcpy(s, ds.p, bytes, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(c, dc.p, bytes, hipMemcpyDeviceToHost) != hipSuccess)
+    return ALTRO_HIP_ERR_HIP;
+  return 0;
 }
 double altro_hip_selftest_mfma_f64(int device) {
   if (hipSetDevice(device) != hipSuccess) return -1.0;
@@ -377,16 +370,13 @@ double altro_hip_selftest_mfma_f64(int device) {
   for (double& v : hA) v = rnd();
   for (double& v : hB) v = rnd();
   for (double& v : hC) v = rnd();
-  double *dA, *dB, *dC, *dD;
-  if (hipMalloc(&dA, sizeof(hA)) != hipSuccess || hipMalloc(&dB, sizeof(hB)) != hipSuccess ||
-      hipMalloc(&dC, sizeof(hC)) != hipSuccess || hipMalloc(&dD, sizeof(hD)) != hipSuccess)
-    return -1.0;
-  (void)hipMemcpy(dA, hA, sizeof(hA), hipMemcpyHostToDevice);
-  (void)hipMemcpy(dB, hB, sizeof(hB), hipMemcpyHostToDevice);
-  (void)hipMemcpy(dC, hC, sizeof(hC), hipMemcpyHostToDevice);
-  hipLaunchKernelGGL(mfma16_selftest_kernel, dim3(1), dim3(64), 0, 0, dA, dB, dC, dD);
-  if (hipMemcpy(hD, dD, sizeof(hD), hipMemcpyDeviceToHost) != hipSuccess) return -1.0;
-  (void)hipFree(dA); (void)hipFree(dB); (void)hipFree(dC); (void)hipFree(dD);
+  DevTemp dA, dB, dC, dD;
+  if (!dA.alloc(sizeof(hA)) || !dB.alloc(sizeof(hB)) || !dC.alloc(sizeof(hC)) || !dD.alloc(sizeof(hD))) return -1.0;
+  (void)hipMemcpy(dA.p, hA, sizeof(hA), hipMemcpyHostToDevice);
+  (void)hipMemcpy(dB.p, hB, sizeof(hB), hipMemcpyHostToDevice);
+  (void)hipMemcpy(dC.p, hC, sizeof(hC), hipMemcpyHostToDevice);
+  hipLaunchKernelGGL(mfma16_selftest_kernel, dim3(1), dim3(64), 0, 0, dA.as<double>(), dB.as<double>(), dC.as<double>(), dD.as<double>());
+  if (hipMemcpy(hD, dD.p, sizeof(hD), hipMemcpyDeviceToHost) != hipSuccess) return -1.0;
   double worst = 0.0;
   for (int i = 0; i < 16; ++i)
     for (int j = 0; j < 16; ++j) {
@@ -407,16 +397,13 @@ double altro_hip_selftest_mfma_f32_4b(int device) {
   for (float& v : hA) v = rnd();
   for (float& v : hB) v = rnd();
   for (float& v : hC) v = rnd();
-  float *dA, *dB, *dC, *dD;
-  if (hipMalloc(&dA, sizeof(hA)) != hipSuccess || hipMalloc(&dB, sizeof(hB)) != hipSuccess ||
-      hipMalloc(&dC, sizeof(hC)) != hipSuccess || hipMalloc(&dD, sizeof(hD)) != hipSuccess)
-    return -1.0;
-  (void)hipMemcpy(dA, hA, sizeof(hA), hipMemcpyHostToDevice);
-  (void)hipMemcpy(dB, hB, sizeof(hB), hipMemcpyHostToDevice);
-  (void)hipMemcpy(dC, hC, sizeof(hC), hipMemcpyHostToDevice);
-  hipLaunchKernelGGL(mfma16_selftest_4b_kernel, dim3(1), dim3(64), 0, 0, dA, dB, dC, dD);
-  if (hipMemcpy(hD, dD, sizeof(hD), hipMemcpyDeviceToHost) != hipSuccess) return -1.0;
-  (void)hipFree(dA); (void)hipFree(dB); (void)hipFree(dC); (void)hipFree(dD);
+  DevTemp dA, dB, dC, dD;
+  if (!dA.alloc(sizeof(hA)) || !dB.alloc(sizeof(hB)) || !dC.alloc(sizeof(hC)) || !dD.alloc(sizeof(hD))) return -1.0;
+  (void)hipMemcpy(dA.p, hA, sizeof(hA), hipMemcpyHostToDevice);
+  (void)hipMemcpy(dB.p, hB, sizeof(hB), hipMemcpyHostToDevice);
+  (void)hipMemcpy(dC.p, hC, sizeof(hC), hipMemcpyHostToDevice);
+  hipLaunchKernelGGL(mfma16_selftest_4b_kernel, dim3(1), dim3(64), 0, 0, dA.as<float>(), dB.as<float>(), dC.as<float>(), dD.as<float>());
+  if (hipMemcpy(hD, dD.p, sizeof(hD), hipMemcpyDeviceToHost) != hipSuccess) return -1.0;
   double worst = 0.0;
   for (int b = 0; b < 4; ++b)
     for (int i = 0; i < 16; ++i)
