@@ -26,7 +26,7 @@ C_ABI_SYMBOLS = [
     "altro_hip_version", "altro_hip_last_error", "altro_hip_device_count", "altro_hip_device_info", "altro_hip_device_pci_bus_id",
     "altro_hip_batch_create", "altro_hip_batch_create_dims", "altro_hip_batch_destroy", "altro_hip_batch_plan",
     "altro_hip_batch_device_bytes", "altro_hip_set_dynamics", "altro_hip_set_cost",
-    "altro_hip_set_initial_state", "altro_hip_set_host_batch", "altro_hip_backward", "altro_hip_forward_ltv", "altro_hip_sweep",
+    "altro_hip_set_initial_state", "altro_hip_set_host_batch", "altro_hip_backward", "altro_hip_backward_per_problem", "altro_hip_forward_ltv", "altro_hip_sweep",
     "altro_hip_synchronize", "altro_hip_get_K", "altro_hip_get_d", "altro_hip_get_P",
     "altro_hip_get_p", "altro_hip_get_x", "altro_hip_get_u", "altro_hip_get_y",
     "altro_hip_get_delta_V", "altro_hip_get_status", "altro_hip_get_qblocks",
@@ -60,8 +60,10 @@ FORM_AFFINE_EXACT = 0x8000
 FORM_NO_COMPACTION = 0x10000
 FORM_GENERIC_MERIT_LDS = 0x20000
 FORM_FORWARD_WAVE = 0x40000
+FORM_BACKWARD_WAVE = 0x80000
 # altro_hip_sweep_variant (ALTRO_HIP_SWEEP_*): which instantiation of plan GENERIC's sweep kernels the last launch was
 SWEEP_LATE_Q, SWEEP_GLOBAL_WORKSPACE, SWEEP_MATRIX_CORES, SWEEP_FORWARD_STAGED = 0x1, 0x2, 0x4, 0x8
+SWEEP_GROUP = 0x10   # plan MFMA16, slot 0: the backward sweep ran one workgroup per 16 problems
 
 
 def forms_from_env():
@@ -189,6 +191,7 @@ def lib():
         L.altro_hip_set_initial_state.argtypes = [vp, vp, i]
         L.altro_hip_set_host_batch.argtypes = [vp, i]
         L.altro_hip_backward.argtypes = [vp, d]
+        L.altro_hip_backward_per_problem.argtypes = [vp, vp]
         L.altro_hip_forward_ltv.argtypes = [vp]
         L.altro_hip_sweep.argtypes = [vp, d]
         L.altro_hip_synchronize.argtypes = [vp]
@@ -362,6 +365,13 @@ class Batch:
     def backward(self, reg=0.0):
         self._sync_forms()
         _check(self.L.altro_hip_backward(self.h, float(reg)))
+
+    def backward_per_problem(self, reg):
+        """altro_hip_backward_per_problem: the backward sweep with reg[b] added to problem b's Quu."""
+        self._sync_forms()
+        reg = np.ascontiguousarray(reg, dtype=np.float64)
+        assert reg.shape == (self.batch,)
+        _check(self.L.altro_hip_backward_per_problem(self.h, reg.ctypes.data))
 
     def forward_ltv(self):
         self._sync_forms()

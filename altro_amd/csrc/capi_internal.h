@@ -86,6 +86,8 @@ struct altro_hip_batch {
        *m_qblk = nullptr, *m_trash = nullptr;   // element type = handle dtype (fp32 storage allowed)
   Mfma16Strides m_st{};
   bool fwd_group_ready = false;   // mfma16_forward_group_kernel may use its dynamic LDS on this handle's device
+  bool bwd_group_ready = false;   // ... and mfma16_backward_group_kernel
+  bool bwd_group = false;         // the last MFMA16 backward sweep ran one workgroup per 16 problems (kernels/tvlqr_mfma16_bwd_group.hip)
   // plan LANE: batch structure-of-arrays ([k][element][batch])
   void *l_in = nullptr, *l_term = nullptr, *l_out = nullptr, *l_outn = nullptr, *l_xuy = nullptr,
        *l_x0 = nullptr;

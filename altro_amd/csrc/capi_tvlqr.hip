@@ -8,6 +8,7 @@
 #include "kernels/tvlqr_mfma16_f32x4.hip"
 #include "kernels/tvlqr_mfma16_fwd_f32x4.hip"
 #include "kernels/tvlqr_mfma16_fwd_group.hip"
+#include "kernels/tvlqr_mfma16_bwd_group.hip"
 
 using namespace altro_hip;
 using namespace altro_hip::capi;
@@ -182,6 +183,34 @@ int mfma16_launch_forward_group(altro_hip_batch* h, const Mfma16Args<double>& a)
   return 0;
 }
 
+
+// fp64, whole groups of 16 problems, no mask: one workgroup of 16 waves per group fetches the group's DYN and COST records as
+// contiguous runs (kernels/tvlqr_mfma16_bwd_group.hip).  127 KB of dynamic LDS: one workgroup per CU, sixteen waves, the occupancy of
+// the wave-per-problem kernel.  A launch with an `active` mask keeps that kernel: a masked wave must not leave a workgroup that has
+// barriers, and a launch with few active problems is better served by waves that return at once.
+constexpr int kBwdGroup = 16;
+bool mfma16_backward_is_group(const altro_hip_batch* h, const BackwardMask& pp) {
+  const int64_t B = h->batch;
+  return h->plan == ALTRO_HIP_PLAN_MFMA16 && h->dtype == ALTRO_HIP_F64 && !form(h, ALTRO_HIP_FORM_BACKWARD_WAVE) &&
+         !(h->flags & ALTRO_HIP_STORE_QBLOCKS) && !pp.active && h->batch % kBwdGroup == 0 && h->m_st.in_bs == MF_DYN &&
+         h->m_st.in_ks == B * MF_DYN && h->m_st.cin_bs == MF_COST && h->m_st.cin_ks == B * MF_COST && h->m_st.out_bs == MF_OUT &&
+         h->m_st.out_ks == B * MF_OUT;
+}
+int mfma16_launch_backward_group(altro_hip_batch* h, const Mfma16Args<double>& a) {
+  const size_t lds = Mfma16BwdGroup<kBwdGroup>::lds_bytes();
+  if (!h->bwd_group_ready) {   // more than 64 KB of dynamic LDS has to be asked for, once per device: a handle stays on its own
+    for (const void* kernel : {(const void*)mfma16_backward_group_kernel<true, kBwdGroup>, (const void*)mfma16_backward_group_kernel<false, kBwdGroup>}) {
+      hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return fail(ALTRO_HIP_ERR_HIP, "backward group kernel: %s", hipGetErrorString(e));
+    }
+    h->bwd_group_ready = true;
+  }
+  const dim3 grid(mf_grid(h->batch / kBwdGroup)), block(64 * kBwdGroup);
+  if (a.has_f) PROF_LAUNCH((mfma16_backward_group_kernel<true, kBwdGroup>), grid, block, lds, h->stream, a);
+  else PROF_LAUNCH((mfma16_backward_group_kernel<false, kBwdGroup>), grid, block, lds, h->stream, a);
+  return 0;
+}
+
 }  // namespace
 
 namespace altro_hip {
@@ -193,7 +222,12 @@ int launch_backward(altro_hip_batch* h, double reg, const BackwardMask& pp) {
   h->aff_base = false;   // (new gains: altro_hip_merit_affine's stored base is the last sweep's)
   if (h->plan == ALTRO_HIP_PLAN_MFMA16) {
     const bool sq = (h->flags & ALTRO_HIP_STORE_QBLOCKS) != 0;
-    if (h->dtype == ALTRO_HIP_F64) mfma16_launch_backward<double>(h, reg, pp, sq);
+    h->bwd_group = mfma16_backward_is_group(h, pp);
+    if (h->bwd_group) {
+      h->sweep_variant[0] = ALTRO_HIP_SWEEP_GROUP;
+      int rc = mfma16_launch_backward_group(h, mfma16_args<double>(h, reg, pp));
+      if (rc) return rc;
+    } else if (h->dtype == ALTRO_HIP_F64) mfma16_launch_backward<double>(h, reg, pp, sq);
     else if (sq || !(h->flags & ALTRO_HIP_F32_PURE)) mfma16_launch_backward<float>(h, reg, pp, sq);   // fp32 storage, fp64 tiles
     else {   // opt-in: pure fp32 on v_mfma_f32_16x16x4_f32
       auto a = mfma16_args<float>(h, reg, pp);
@@ -322,6 +356,19 @@ int altro_hip_backward(altro_hip_batch* h, double reg) {
   if (rc) return rc;
   if (!h->dyn_set || !h->cost_set) return fail(ALTRO_HIP_ERR_NOT_SET, "set_dynamics and set_cost must precede backward");
   rc = launch_backward(h, reg, {});
+  if (!rc) h->backward_done = true;
+  return rc;
+}
+
+int altro_hip_backward_per_problem(altro_hip_batch* h, const double* reg) {
+  int rc = check(h);
+  if (rc) return rc;
+  if (!reg) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "reg is null");
+  if (!h->dyn_set || !h->cost_set) return fail(ALTRO_HIP_ERR_NOT_SET, "set_dynamics and set_cost must precede backward");
+  // (the solve loop's own per-problem vector: every solve initialises it before it reads it)
+  HIP_TRY(hipMemcpyAsync(h->i_reg, reg, (size_t)h->batch * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));   // the caller's array is free on return
+  rc = launch_backward(h, 0.0, BackwardMask{nullptr, h->i_reg});
   if (!rc) h->backward_done = true;
   return rc;
 }

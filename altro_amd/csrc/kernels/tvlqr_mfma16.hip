@@ -177,73 +177,232 @@ __device__ __forceinline__ double rsqrt_nr(double x) {
   return __builtin_fma(y * e, t, y);
 }
 
+// The two LDS scratch areas of one wave's backward sweep, in doubles.  The exchange area: [0..63] = [Qux | Quu] (row g, col j),
+// [64..79] = [Qx | Qu], [80] = 0.0 (the "zero slot" padding lanes read instead of selecting: their loop-invariant LDS
+// addresses point here).  The tile area: the new [P | p] tile, written row-major and read back mirrored (see the symmetry note).
+constexpr int MF_BWD_XCH = 64 + 16 + 2, MF_BWD_PTILE = 12 * MF_PT_LD;
+
+// What a lane does in every step of the backward sweep (the same for every kernel that runs it): its loop-invariant LDS
+// addresses (element indices) and where its results go inside an OUT record.
+struct Mfma16BwdLane {
+  int j, g, jc;
+  int rhs_idx[4];   // column j of Qt = [Qux | Qu]; zero for the padding columns 13..15
+  int qmine_idx;    // Qt[g][j]
+  int qx_idx[3];    // column 12 of [Qxx | Qx]: Qx[g + 4r]; zero for columns 13..15 (unused for j < 12)
+  // where this lane's three [P | p] registers (rows g + 4r, column j) go inside an OUT record: the packed upper
+  // triangle, the p block, or -- for the entries below the diagonal and the padding columns -- the record's two
+  // spare slots (garbage nobody reads; same cache lines, so no extra traffic and no exec-masked store)
+  int p_off[3];
+  // the tile exchange that keeps the carried P symmetric: every lane writes its three entries (row g + 4r, column j) and reads
+  // them back -- the entries BELOW the diagonal from the mirrored position above it, every other one from its own slot (no
+  // selects, no masked accesses)
+  int pt_wr[3], pt_rd[3];
+};
+__device__ __forceinline__ Mfma16BwdLane mfma16_bwd_lane(int lane) {
+  Mfma16BwdLane ln;
+  const int j = lane & 15, g = lane >> 4;
+  ln.j = j; ln.g = g;
+  ln.jc = (j <= 12) ? j : 12;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) ln.rhs_idx[r] = (j < 12) ? (r * 16 + j) : ((j == 12) ? (64 + 12 + r) : 80);
+  ln.qmine_idx = (j < 12) ? lane : ((j == 12) ? (64 + 12 + g) : 80);
+#pragma unroll
+  for (int r = 0; r < 3; ++r) ln.qx_idx[r] = (j == 12) ? (64 + g + 4 * r) : 80;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const int row = g + 4 * r;
+    ln.p_off[r] = (j == 12) ? MF_OFF_p + row : ((j < 12 && j >= row) ? MF_OFF_P + mf_sym(row, j) : MF_OFF_PAD + (j > 12 ? 1 : 0));
+    ln.pt_wr[r] = row * MF_PT_LD + j;
+    ln.pt_rd[r] = (j < 12 && j < row) ? j * MF_PT_LD + row : ln.pt_wr[r];
+  }
+  return ln;
+}
+// what the recursion carries from knot point to knot point
+struct Mfma16BwdState {
+  double Pt[3];      // the tile [P | p] of knot point k + 1: rows g + 4r, column j
+  double dv0, dv1;   // per-lane partial sums of the expected decrease; only column 12 is meaningful, reduced at the end
+  int fail_k;        // -1, or the knot point whose Cholesky failed
+};
+// The LDS exchanges of one step are private to a wave.  A one-wave workgroup says so with __syncthreads (free there); a wave of
+// a larger workgroup must not meet the others here: in-order LDS, so its own accesses retired is all it needs.
+template <bool WAVE_ONLY>
+__device__ __forceinline__ void mfma16_bwd_sync() {
+  if constexpr (WAVE_ONLY) {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_wave_barrier();
+  } else {
+    __syncthreads();
+  }
+}
+
+// One knot point of the backward sweep from its inputs in registers: the two tile products, the LDS exchange, the Cholesky and
+// the solves, the expected decrease, the two rank-4 updates, the symmetrising transposition, and the unconditional stores of Kt
+// and [P | p] into the record `out_k` (a failed problem's go to `trash`).  `lds` and `ptile` are the wave's own MF_BWD_XCH and
+// MF_BWD_PTILE doubles.  Every kernel that runs it carries the same state, so K, d, P, p come out bit for bit the same.
+template <bool STORE_Q, bool HAS_F, bool WAVE_ONLY, typename S>
+__device__ __forceinline__ void mfma16_bwd_step(const Mfma16Knot& cur, Mfma16BwdState& st, const Mfma16BwdLane& ln,
+                                                double* __restrict__ lds, double* __restrict__ ptile, int lane, int k, double reg,
+                                                S* __restrict__ out_k, S* __restrict__ trash, S* __restrict__ qb) {
+  const int j = ln.j, g = ln.g;
+  // ---- D1 = [P'|t]^T Z : rows 0..11 = P'^T Z, row 12 = t^T Z --------------------------------
+  f64x4 D1 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) D1 = mfma_f64_16x16x4(st.Pt[c], cur.z[c], D1);
+
+  // ---- G = [Q H^T; H R] + Z^T D1 : Qxx (rows<12, cols<12), [Qux | Quu] (rows 12..15) ---------
+  // (columns 12..15 of rows 0..11 -- the Qxu block -- are never used, so the clamped Q loads of the
+  //  padding lanes need no zeroing)
+  f64x4 G = {cur.q[0], cur.q[1], cur.q[2], cur.hr};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) G = mfma_f64_16x16x4(cur.z[c], D1[c], G);
+
+  // ---- gradient [Qx; Qu] = [q; r] + Z^T t (+ Z^T P' f) : valid in lanes g == 0 -----------------
+  double gv = D1[3] + cur.qr;
+  if (HAS_F) {  // Z^T P' f = (P'^T Z)^T f : sum_i f[i] D1[i][j]
+    double s = cur.f[0] * D1[0] + cur.f[1] * D1[1] + cur.f[2] * D1[2];
+    gv += group4_allreduce(s);
+  }
+
+  // ---- LDS exchange ------------------------------------------------------------------------------
+  mfma16_bwd_sync<WAVE_ONLY>();  // previous iteration's readers are done (single-wave block: free)
+  lds[lane] = G[3];                 // [Qux | Quu], row g, col j
+  if (g == 0) lds[64 + j] = gv;     // [Qx | Qu]
+  mfma16_bwd_sync<WAVE_ONLY>();
+  // lower triangle of Quu (Eigen's LLT<Lower> reads only that), same in every lane
+  const double a00 = lds[0 * 16 + 12];
+  const double a10 = lds[1 * 16 + 12], a11 = lds[1 * 16 + 13];
+  const double a20 = lds[2 * 16 + 12], a21 = lds[2 * 16 + 13], a22 = lds[2 * 16 + 14];
+  const double a30 = lds[3 * 16 + 12], a31 = lds[3 * 16 + 13], a32 = lds[3 * 16 + 14], a33 = lds[3 * 16 + 15];
+  double rhs[4];  // column j of Qt = [Qux | Qu]
+#pragma unroll
+  for (int r = 0; r < 4; ++r) rhs[r] = lds[ln.rhs_idx[r]];
+  double quu_row[4];  // row g of the UNregularised Quu
+#pragma unroll
+  for (int c = 0; c < 4; ++c) quu_row[c] = lds[g * 16 + 12 + c];
+  f64x4 Pn;           // accumulator init: column j of [Qxx | Qx], rows g + 4r
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const double qx = lds[ln.qx_idx[r]];
+    Pn[r] = (j < 12) ? G[r] : qx;
+  }
+  Pn[3] = 0.0;
+  const double q_mine = lds[ln.qmine_idx];  // Qt[g][j] (0 in the padding columns)
+
+  // ---- Cholesky of Quu + reg I (lower; fail when a pivot is <= 0: tvlqr.cpp:159-164) -----------
+  // Only the reciprocal pivots i_k = 1/L_kk are needed by the substitutions below.
+  const double x0 = a00 + reg;
+  const double i0 = rsqrt_nr(x0);
+  const double l10 = a10 * i0, l20 = a20 * i0, l30 = a30 * i0;
+  const double x1 = (a11 + reg) - l10 * l10;
+  const double i1 = rsqrt_nr(x1);
+  const double l21 = (a21 - l20 * l10) * i1, l31 = (a31 - l30 * l10) * i1;
+  const double x2 = (a22 + reg) - l20 * l20 - l21 * l21;
+  const double i2 = rsqrt_nr(x2);
+  const double l32 = (a32 - l30 * l20 - l31 * l21) * i2;
+  const double x3 = (a33 + reg) - l30 * l30 - l31 * l31 - l32 * l32;
+  const double i3 = rsqrt_nr(x3);
+  // Failure is wave-uniform (Quu is the same in every lane).  Reference: `return k` with
+  // K_k = Qux, d_k = -Qu left unsolved and P_k, p_k untouched.  To keep the loop a plain counted
+  // loop (no mid-body exits: they wreck hipcc's s_waitcnt placement) a failed problem keeps
+  // iterating on garbage with its stores masked off; failures are rare and cost nothing extra.
+  const bool fail = !(x0 > 0.0) || !(x1 > 0.0) || !(x2 > 0.0) || !(x3 > 0.0);
+  const bool was_alive = (st.fail_k < 0);
+  if (was_alive && fail) st.fail_k = k;
+  const bool alive = (st.fail_k < 0);
+  // ---- Kt[:, j] = (L L^T)^-1 Qt[:, j]  (tvlqr.cpp:165-166; column 12 gives -d) ------------------
+  const double y0 = rhs[0] * i0;
+  const double y1 = (rhs[1] - l10 * y0) * i1;
+  const double y2 = (rhs[2] - l20 * y0 - l21 * y1) * i2;
+  const double y3 = (rhs[3] - l30 * y0 - l31 * y1 - l32 * y2) * i3;
+  const double k3 = y3 * i3;
+  const double k2 = (y2 - l32 * k3) * i2;
+  const double k1 = (y1 - l21 * k2 - l31 * k3) * i1;
+  const double k0 = (y0 - l10 * k1 - l20 * k2 - l30 * k3) * i0;
+  const double k_mine = (g == 0) ? k0 : (g == 1) ? k1 : (g == 2) ? k2 : k3;  // Kt[g][j]
+  // (Quu Kt)[g][j] with the UNregularised Quu (tvlqr.cpp:174), then W = Quu Kt - Qt
+  const double qk = quu_row[0] * k0 + quu_row[1] * k1 + quu_row[2] * k2 + quu_row[3] * k3;
+  const double w_mine = qk - q_mine;   // padding columns: rhs = 0 => Kt = 0, W = 0 without masking
+  // ---- expected decrease (tvlqr.cpp:189-191): in column 12 Kt = -d, Qt = Qu, so
+  //      d.Qu = -sum_g Kt[g] Qt[g]  and  1/2 d.Quu d = 1/2 sum_g Kt[g] (Quu Kt)[g]
+  st.dv0 = alive ? __builtin_fma(-k_mine, q_mine, st.dv0) : st.dv0;
+  st.dv1 = alive ? __builtin_fma(0.5 * k_mine, qk, st.dv1) : st.dv1;
+
+  // ---- [P | p] = [Qxx | Qx] + Kt^T W - Qt^T Kt  (tvlqr.cpp:173-186) ----------------------------
+  Pn = mfma_f64_16x16x4(k_mine, w_mine, Pn);
+  Pn = mfma_f64_16x16x4(q_mine, -k_mine, Pn);
+  // ---- the carried P is the stored P: lower triangle <- mirrored upper triangle ------------------
+#pragma unroll
+  for (int r = 0; r < 3; ++r) ptile[ln.pt_wr[r]] = Pn[r];
+  mfma16_bwd_sync<WAVE_ONLY>();
+#pragma unroll
+  for (int r = 0; r < 3; ++r) Pn[r] = ptile[ln.pt_rd[r]];
+
+  const double k_store = alive ? k_mine : q_mine;
+  // ---- store Kt and [P | p] --------------------------------------------------------------------------
+  // Unconditional, branch-free stores: lanes 13..15 duplicate column 12 onto column 12's address,
+  // and a failed problem's stores are redirected to its trash record.  With no exec-masked VMEM in
+  // the loop hipcc can count the queue exactly and wait for the prefetch with vmcnt(#younger ops)
+  // instead of draining the stores too.
+  S* __restrict__ ok_ = was_alive ? out_k : trash;
+  S* __restrict__ op_ = alive ? out_k : trash;
+  ok_[g * 13 + ln.jc] = (S)dpp_col12_dup(k_store);
+#pragma unroll
+  for (int r = 0; r < 3; ++r) op_[ln.p_off[r]] = (S)Pn[r];
+  if (STORE_Q && was_alive) {  // Qxx_, Quu_, Qux_, Qx_, Qu_ are API-visible in the reference
+#pragma unroll
+    for (int r = 0; r < 4; ++r) qb[(g + 4 * r) * 16 + j] = (S)G[r];
+    if (g == 0) qb[256 + j] = (S)gv;
+  }
+#pragma unroll
+  for (int r = 0; r < 3; ++r) st.Pt[r] = Pn[r];   // columns 13..15 are exactly 0 by construction
+}
+
+// terminal cost-to-go: P_N = Q_N, p_N = q_N (tvlqr.cpp:81-90) -> tile [P | p], and the OUTN record
+template <typename S>
+__device__ __forceinline__ void mfma16_bwd_terminal(Mfma16BwdState& st, const Mfma16BwdLane& ln, const S* __restrict__ term, S* __restrict__ on) {
+  const int j = ln.j, g = ln.g;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    double v = 0.0;
+    if (j < 12) v = (double)term[r * 48 + g * 12 + j];
+    else if (j == 12) v = (double)term[144 + g + 4 * r];
+    st.Pt[r] = v;
+    if (j <= 12) on[(g + 4 * r) * 13 + j] = (S)v;
+  }
+  st.dv0 = 0.0; st.dv1 = 0.0;
+  st.fail_k = -1;
+}
+// status and the expected decrease of problem b
+template <typename S>
+__device__ __forceinline__ void mfma16_bwd_finish(const Mfma16BwdState& st, const Mfma16BwdLane& ln, const Mfma16Args<S>& a, int b) {
+  const double t0 = group4_allreduce(st.dv0), t1 = group4_allreduce(st.dv1);
+  if (ln.j == 12 && ln.g == 0) {
+    a.status[b] = st.fail_k;   // -1 == TVLQR_SUCCESS, else the failing knot point
+    a.delta_V[2 * (size_t)b + 0] = (S)t0;
+    a.delta_V[2 * (size_t)b + 1] = (S)t1;
+  }
+}
+
 template <bool STORE_Q, bool HAS_F, typename S>
 __global__ __launch_bounds__(64, 4) void mfma16_backward_kernel(Mfma16Args<S> a) {
-  // the one and only LDS object: 4x16 tile [Qux | Quu] then [Qx | Qu]
-  // lds[0..63] = [Qux | Quu] (row g, col j), lds[64..79] = [Qx | Qu], lds[80] = 0.0 (the "zero slot" padding
-  // lanes read instead of selecting: their loop-invariant LDS addresses point here)
-  __shared__ __attribute__((aligned(16))) double lds[64 + 16 + 2];
-  __shared__ double ptile[12 * MF_PT_LD];   // the new [P | p] tile, written row-major and read back mirrored (see the symmetry note)
+  __shared__ __attribute__((aligned(16))) double lds[MF_BWD_XCH];   // the one-wave exchange area (see MF_BWD_XCH)
+  __shared__ double ptile[MF_BWD_PTILE];
   const int lane = threadIdx.x;
-  const int j = lane & 15, g = lane >> 4;
   const int b = mf_problem(blockIdx.x, a.batch);
   if (b >= a.batch) return;
   if (a.active && !a.active[b]) return;   // wave-uniform: the whole problem is skipped, its outputs stay as they are
   const int N = a.N;
   if (lane < 2) lds[80 + lane] = 0.0;
-  // loop-invariant LDS read addresses (element indices into S)
-  int rhs_idx[4];   // column j of Qt = [Qux | Qu]; zero for the padding columns 13..15
-#pragma unroll
-  for (int r = 0; r < 4; ++r) rhs_idx[r] = (j < 12) ? (r * 16 + j) : ((j == 12) ? (64 + 12 + r) : 80);
-  const int qmine_idx = (j < 12) ? lane : ((j == 12) ? (64 + 12 + g) : 80);   // Qt[g][j]
-  int qx_idx[3];    // column 12 of [Qxx | Qx]: Qx[g + 4r]; zero for columns 13..15 (unused for j < 12)
-#pragma unroll
-  for (int r = 0; r < 3; ++r) qx_idx[r] = (j == 12) ? (64 + g + 4 * r) : 80;
+  const Mfma16BwdLane ln = mfma16_bwd_lane(lane);
+  const int j = ln.j, g = ln.g;
   const S* __restrict__ in = a.in + (size_t)b * a.in_bs;
   const S* __restrict__ cin = a.cin + (size_t)b * a.cin_bs;
   S* __restrict__ out = a.out + (size_t)b * a.out_bs;
-  const bool col_ok = (j <= 12);
-  const int jc = col_ok ? j : 12;
   S* __restrict__ trash = a.trash + (size_t)b * MF_OUT;
   const Mfma16QOff qo = mfma16_q_offsets(j, g);
-  // where this lane's three [P | p] registers (rows g + 4r, column j) go inside an OUT record: the packed upper
-  // triangle, the p block, or -- for the entries below the diagonal and the padding columns -- the record's two
-  // spare slots (garbage nobody reads; same cache lines, so no extra traffic and no exec-masked store)
-  int p_off[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const int row = g + 4 * r;
-    p_off[r] = (j == 12) ? MF_OFF_p + row : ((j < 12 && j >= row) ? MF_OFF_P + mf_sym(row, j) : MF_OFF_PAD + (j > 12 ? 1 : 0));
-  }
 
-  // the tile exchange that keeps the carried P symmetric: every lane writes its three entries (row g + 4r, column j) and reads
-  // them back -- the entries BELOW the diagonal from the mirrored position above it, every other one from its own slot (no
-  // selects, no masked accesses)
-  int pt_wr[3], pt_rd[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    const int row = g + 4 * r;
-    pt_wr[r] = row * MF_PT_LD + j;
-    pt_rd[r] = (j < 12 && j < row) ? j * MF_PT_LD + row : pt_wr[r];
-  }
-
-  // terminal cost-to-go: P_N = Q_N, p_N = q_N (tvlqr.cpp:81-90) -> tile [P | p]
-  double Pt[3];
-  {
-    const S* term = a.term + (size_t)b * MF_TERM;
-    S* on = a.outn + (size_t)b * MF_TERM;
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      double v = 0.0;
-      if (j < 12) v = (double)term[r * 48 + g * 12 + j];
-      else if (j == 12) v = (double)term[144 + g + 4 * r];
-      Pt[r] = v;
-      if (col_ok) on[(g + 4 * r) * 13 + j] = (S)v;
-    }
-  }
-  // per-lane partial sums of the expected decrease; only column 12 is meaningful, reduced at the end
-  double dv0 = 0.0, dv1 = 0.0;
-  int fail_k = -1;
+  Mfma16BwdState st;
+  mfma16_bwd_terminal<S>(st, ln, a.term + (size_t)b * MF_TERM, a.outn + (size_t)b * MF_TERM);
   const double reg = a.reg_pp ? a.reg_pp[b] : a.reg;
 
   Mfma16Knot cur, nxt;
@@ -259,131 +418,12 @@ __global__ __launch_bounds__(64, 4) void mfma16_backward_kernel(Mfma16Args<S> a)
       const size_t kp = (k > 0) ? k - 1 : 0;
       mfma16_load_knot<HAS_F, S>(nxt, in + kp * a.in_ks, cin + kp * a.cin_ks, lane, j, g, qo);
     }
-
-    // ---- D1 = [P'|t]^T Z : rows 0..11 = P'^T Z, row 12 = t^T Z --------------------------------
-    f64x4 D1 = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int c = 0; c < 3; ++c) D1 = mfma_f64_16x16x4(Pt[c], cur.z[c], D1);
-
-    // ---- G = [Q H^T; H R] + Z^T D1 : Qxx (rows<12, cols<12), [Qux | Quu] (rows 12..15) ---------
-    // (columns 12..15 of rows 0..11 -- the Qxu block -- are never used, so the clamped Q loads of the
-    //  padding lanes need no zeroing)
-    f64x4 G = {cur.q[0], cur.q[1], cur.q[2], cur.hr};
-#pragma unroll
-    for (int c = 0; c < 3; ++c) G = mfma_f64_16x16x4(cur.z[c], D1[c], G);
-
-    // ---- gradient [Qx; Qu] = [q; r] + Z^T t (+ Z^T P' f) : valid in lanes g == 0 -----------------
-    double gv = D1[3] + cur.qr;
-    if (HAS_F) {  // Z^T P' f = (P'^T Z)^T f : sum_i f[i] D1[i][j]
-      double s = cur.f[0] * D1[0] + cur.f[1] * D1[1] + cur.f[2] * D1[2];
-      gv += group4_allreduce(s);
-    }
-
-    // ---- LDS exchange ------------------------------------------------------------------------------
-    __syncthreads();  // previous iteration's readers are done (single-wave block: free)
-    lds[lane] = G[3];                 // [Qux | Quu], row g, col j
-    if (g == 0) lds[64 + j] = gv;     // [Qx | Qu]
-    __syncthreads();
-    // lower triangle of Quu (Eigen's LLT<Lower> reads only that), same in every lane
-    const double a00 = lds[0 * 16 + 12];
-    const double a10 = lds[1 * 16 + 12], a11 = lds[1 * 16 + 13];
-    const double a20 = lds[2 * 16 + 12], a21 = lds[2 * 16 + 13], a22 = lds[2 * 16 + 14];
-    const double a30 = lds[3 * 16 + 12], a31 = lds[3 * 16 + 13], a32 = lds[3 * 16 + 14], a33 = lds[3 * 16 + 15];
-    double rhs[4];  // column j of Qt = [Qux | Qu]
-#pragma unroll
-    for (int r = 0; r < 4; ++r) rhs[r] = lds[rhs_idx[r]];
-    double quu_row[4];  // row g of the UNregularised Quu
-#pragma unroll
-    for (int c = 0; c < 4; ++c) quu_row[c] = lds[g * 16 + 12 + c];
-    f64x4 Pn;           // accumulator init: column j of [Qxx | Qx], rows g + 4r
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-      const double qx = lds[qx_idx[r]];
-      Pn[r] = (j < 12) ? G[r] : qx;
-    }
-    Pn[3] = 0.0;
-    const double q_mine = lds[qmine_idx];  // Qt[g][j] (0 in the padding columns)
-
-    // ---- Cholesky of Quu + reg I (lower; fail when a pivot is <= 0: tvlqr.cpp:159-164) -----------
-    // Only the reciprocal pivots i_k = 1/L_kk are needed by the substitutions below.
-    const double x0 = a00 + reg;
-    const double i0 = rsqrt_nr(x0);
-    const double l10 = a10 * i0, l20 = a20 * i0, l30 = a30 * i0;
-    const double x1 = (a11 + reg) - l10 * l10;
-    const double i1 = rsqrt_nr(x1);
-    const double l21 = (a21 - l20 * l10) * i1, l31 = (a31 - l30 * l10) * i1;
-    const double x2 = (a22 + reg) - l20 * l20 - l21 * l21;
-    const double i2 = rsqrt_nr(x2);
-    const double l32 = (a32 - l30 * l20 - l31 * l21) * i2;
-    const double x3 = (a33 + reg) - l30 * l30 - l31 * l31 - l32 * l32;
-    const double i3 = rsqrt_nr(x3);
-    // Failure is wave-uniform (Quu is the same in every lane).  Reference: `return k` with
-    // K_k = Qux, d_k = -Qu left unsolved and P_k, p_k untouched.  To keep the loop a plain counted
-    // loop (no mid-body exits: they wreck hipcc's s_waitcnt placement) a failed problem keeps
-    // iterating on garbage with its stores masked off; failures are rare and cost nothing extra.
-    const bool fail = !(x0 > 0.0) || !(x1 > 0.0) || !(x2 > 0.0) || !(x3 > 0.0);
-    const bool was_alive = (fail_k < 0);
-    if (was_alive && fail) fail_k = k;
-    const bool alive = (fail_k < 0);
-    // ---- Kt[:, j] = (L L^T)^-1 Qt[:, j]  (tvlqr.cpp:165-166; column 12 gives -d) ------------------
-    const double y0 = rhs[0] * i0;
-    const double y1 = (rhs[1] - l10 * y0) * i1;
-    const double y2 = (rhs[2] - l20 * y0 - l21 * y1) * i2;
-    const double y3 = (rhs[3] - l30 * y0 - l31 * y1 - l32 * y2) * i3;
-    const double k3 = y3 * i3;
-    const double k2 = (y2 - l32 * k3) * i2;
-    const double k1 = (y1 - l21 * k2 - l31 * k3) * i1;
-    const double k0 = (y0 - l10 * k1 - l20 * k2 - l30 * k3) * i0;
-    const double k_mine = (g == 0) ? k0 : (g == 1) ? k1 : (g == 2) ? k2 : k3;  // Kt[g][j]
-    // (Quu Kt)[g][j] with the UNregularised Quu (tvlqr.cpp:174), then W = Quu Kt - Qt
-    const double qk = quu_row[0] * k0 + quu_row[1] * k1 + quu_row[2] * k2 + quu_row[3] * k3;
-    const double w_mine = qk - q_mine;   // padding columns: rhs = 0 => Kt = 0, W = 0 without masking
-    // ---- expected decrease (tvlqr.cpp:189-191): in column 12 Kt = -d, Qt = Qu, so
-    //      d.Qu = -sum_g Kt[g] Qt[g]  and  1/2 d.Quu d = 1/2 sum_g Kt[g] (Quu Kt)[g]
-    dv0 = alive ? __builtin_fma(-k_mine, q_mine, dv0) : dv0;
-    dv1 = alive ? __builtin_fma(0.5 * k_mine, qk, dv1) : dv1;
-
-    // ---- [P | p] = [Qxx | Qx] + Kt^T W - Qt^T Kt  (tvlqr.cpp:173-186) ----------------------------
-    Pn = mfma_f64_16x16x4(k_mine, w_mine, Pn);
-    Pn = mfma_f64_16x16x4(q_mine, -k_mine, Pn);
-    // ---- the carried P is the stored P: lower triangle <- mirrored upper triangle ------------------
-#pragma unroll
-    for (int r = 0; r < 3; ++r) ptile[pt_wr[r]] = Pn[r];
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 3; ++r) Pn[r] = ptile[pt_rd[r]];
-
-    // ---- roll the prefetched knot point in BEFORE the stores are issued, so that the wait for its
-    //      loads does not also have to drain this step's stores (vmcnt retires in order) ------------
-    const double k_store = alive ? k_mine : q_mine;
+    // (the prefetch is issued before the step's stores, so the wait for it does not have to drain them: vmcnt retires in order)
+    mfma16_bwd_step<STORE_Q, HAS_F, false, S>(cur, st, ln, lds, ptile, lane, k, reg, out + (size_t)k * a.out_ks, trash,
+                                             STORE_Q ? a.qblk + ((size_t)b * N + k) * MF_QB : nullptr);
     cur = nxt;
-    // ---- store Kt and [P | p] --------------------------------------------------------------------------
-    // Unconditional, branch-free stores: lanes 13..15 duplicate column 12 onto column 12's address,
-    // and a failed problem's stores are redirected to its trash record.  With no exec-masked VMEM in
-    // the loop hipcc can count the queue exactly and wait for the prefetch with vmcnt(#younger ops)
-    // instead of draining the stores too.
-    S* __restrict__ ok_ = was_alive ? out + (size_t)k * a.out_ks : trash;
-    S* __restrict__ op_ = alive ? out + (size_t)k * a.out_ks : trash;
-    ok_[g * 13 + jc] = (S)dpp_col12_dup(k_store);
-#pragma unroll
-    for (int r = 0; r < 3; ++r) op_[p_off[r]] = (S)Pn[r];
-    if (STORE_Q && was_alive) {  // Qxx_, Quu_, Qux_, Qx_, Qu_ are API-visible in the reference
-      S* qb = a.qblk + ((size_t)b * N + k) * MF_QB;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) qb[(g + 4 * r) * 16 + j] = (S)G[r];
-      if (g == 0) qb[256 + j] = (S)gv;
-    }
-#pragma unroll
-    for (int r = 0; r < 3; ++r) Pt[r] = Pn[r];   // columns 13..15 are exactly 0 by construction
   }
-  {
-    const double t0 = group4_allreduce(dv0), t1 = group4_allreduce(dv1);
-    if (j == 12 && g == 0) {
-      a.status[b] = fail_k;   // -1 == TVLQR_SUCCESS, else the failing knot point
-      a.delta_V[2 * (size_t)b + 0] = (S)t0;
-      a.delta_V[2 * (size_t)b + 1] = (S)t1;
-    }
-  }
+  mfma16_bwd_finish<S>(st, ln, a, b);
 }
 
 // ------------------------------------------------------------------------------------------------

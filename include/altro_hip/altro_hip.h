@@ -203,6 +203,8 @@ int altro_hip_set_host_batch(altro_hip_batch* h, int host_batch);
 /* ---- the hot path ----------------------------------------------------------------------------- */
 /* tvlqr_BackwardPass over the batch: K, d, P, p, delta_V, status for every problem.             */
 int altro_hip_backward(altro_hip_batch* h, double reg);
+/* ... with a regularisation of each problem's own: reg[batch] on the host (what a solve's retry schedule runs, without its mask). */
+int altro_hip_backward_per_problem(altro_hip_batch* h, const double* reg);
 /* tvlqr_ForwardPass over the batch: x, u, y from x0 through u = d - K x, x+ = f + A x + B u.     */
 int altro_hip_forward_ltv(altro_hip_batch* h);
 /* One "sweep" of BASELINE.json's metric: backward followed by forward, no host sync in between. */
@@ -523,6 +525,8 @@ typedef struct altro_hip_solve_options { /* AltroOptions, solver_options.hpp:16-
                                                     row-layout one runs (uniform n <= 31, m <= 8, n + m <= 32: kernels/ilqr_row32.hip)        */
 #define ALTRO_HIP_FORM_FORWARD_WAVE 0x40000u     /* plan MFMA16, fp64: the wave-per-problem forward sweep also where the batch is whole groups
                                                     of 16 (kernels/tvlqr_mfma16_fwd_group.hip runs those by default; bit-identical results)  */
+#define ALTRO_HIP_FORM_BACKWARD_WAVE 0x80000u    /* plan MFMA16, fp64: the wave-per-problem backward sweep also where a launch is whole groups
+                                                    of 16 with no mask (kernels/tvlqr_mfma16_bwd_group.hip runs those by default; bit-identical results) */
 /* forms of a HANDLE: what altro_hip_merit / _expand / _sweep and every solve on it run with (a solve ORs its options' bits in) */
 int altro_hip_set_forms(altro_hip_batch* h, unsigned forms);
 unsigned altro_hip_get_forms(const altro_hip_batch* h);
@@ -652,6 +656,7 @@ int altro_hip_profile_dropped(altro_hip_batch* h, int slot);
 #define ALTRO_HIP_SWEEP_GLOBAL_WORKSPACE 0x2 /* generic_backward_kernel: per-problem work blocks in global memory instead of LDS    */
 #define ALTRO_HIP_SWEEP_MATRIX_CORES 0x4     /* generic_backward_kernel: the products on the matrix cores                           */
 #define ALTRO_HIP_SWEEP_FORWARD_STAGED 0x8   /* generic_forward_kernel: the knot point's blocks staged in LDS                       */
+#define ALTRO_HIP_SWEEP_GROUP 0x10           /* plan MFMA16, slot 0: mfma16_backward_group_kernel, one workgroup per 16 problems      */
 int altro_hip_sweep_variant(const altro_hip_batch* h, int slot, int* bits);
 /* Algorithmic bytes one launch of the slot's kernel must move.             */
 double altro_hip_algorithmic_bytes(const altro_hip_batch* h, int slot);

@@ -2,7 +2,7 @@
 // pattern reach with NO arithmetic?  (Practical roof next to the 8 TB/s datasheet number.)
 //   hipcc --offload-arch=gfx950 -O3 tools/membench.hip -o /tmp/membench && /tmp/membench
 //   /tmp/membench multi    just the problems-per-wave table (profiles/r03g_membench_multi.txt)
-//   /tmp/membench group    just the workgroup-run table: G adjacent problems' records fetched as contiguous runs (profiles/r07a_*)
+//   /tmp/membench group    just the workgroup-run table: G adjacent problems' records fetched as contiguous runs (profiles/r07a_*, r08a_*)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstring>
@@ -252,7 +252,8 @@ __global__ __launch_bounds__(64) void stream_multi(const double* __restrict__ in
 // s_barrier, so that DEPTH - 1 knot points stay in flight across the barriers.  DMA = 0: global_load_dwordx4 into a register
 // ring, ds_write_b128 into the slot at the step that consumes it.  OUTRUN = 0: every wave stores WOUT doubles itself (the
 // forward sweep's x | y | u); OUTRUN = 1: the waves put their WOUT-double records into an LDS stage and the block stores the
-// G-problem run as 16-byte chunks (the backward sweep's OUT records).  DIR = 1 walks the horizon backwards.  No arithmetic.
+// G-problem run as 16-byte chunks (the backward sweep's OUT records); OUTRUN = 2: every wave stores its whole WOUT-double record
+// itself, 8 bytes per lane.  DIR = 1 walks the horizon backwards.  No arithmetic.
 typedef double mb_f64x2 __attribute__((ext_vector_type(2)));
 template <int NCNT>
 __device__ __forceinline__ void mb_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NCNT) : "memory"); }
@@ -277,10 +278,10 @@ __global__ __launch_bounds__(64 * G) void stream_group(const double* __restrict_
   constexpr int ROUNDS = (CIN + T - 1) / T;
   constexpr int LASTW = (CIN - (ROUNDS - 1) * T + 63) / 64;   // waves that have chunks in the last round
   constexpr int SLOT = ((CIN + 63) / 64) * 64;        // slot pitch in chunks: whole wave-instructions
-  constexpr int COUT = OUTRUN ? G * WOUT / 2 : 0;     // chunks of the output run
-  constexpr int OROUNDS = OUTRUN ? (COUT + T - 1) / T : 1;
-  constexpr int OLASTW = OUTRUN ? (COUT - (OROUNDS - 1) * T) / 64 : G;
-  static_assert(RA % 2 == 0 && RB % 2 == 0 && (!OUTRUN || COUT % 64 == 0), "16-byte chunks, whole wave-instructions");
+  constexpr int COUT = OUTRUN == 1 ? G * WOUT / 2 : 0;     // chunks of the output run
+  constexpr int OROUNDS = OUTRUN == 1 ? (COUT + T - 1) / T : (OUTRUN == 2 ? (WOUT + 63) / 64 : 1);
+  constexpr int OLASTW = OUTRUN == 1 ? (COUT - (OROUNDS - 1) * T) / 64 : G;
+  static_assert(RA % 2 == 0 && RB % 2 == 0 && (OUTRUN != 1 || COUT % 64 == 0), "16-byte chunks, whole wave-instructions");
   static_assert(LASTW >= 1 && LASTW <= G && OLASTW >= 1 && OLASTW <= G, "wave classes");
   static_assert((DEPTH * SLOT + COUT) * 16 <= 160 * 1024, "LDS of one CU");
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -353,13 +354,13 @@ __global__ __launch_bounds__(64 * G) void stream_group(const double* __restrict_
 #pragma unroll
       for (int c = 0; c < (RB + 63) / 64; ++c) { const int e = c * 64 + lane; s += rb[e < RB ? e : RB - 1]; }
       acc += s;
-      if constexpr (OUTRUN) {
+      if constexpr (OUTRUN == 1) {
 #pragma unroll
         for (int c = 0; c < (WOUT + 63) / 64; ++c) { const int e = c * 64 + lane; ostage[wv * WOUT + (e < WOUT ? e : WOUT - 1)] = acc + c; }
       }
       mb_barrier();                                   // every wave has read the slot: it may be refilled
       fetch(d, k + DEPTH);
-      if constexpr (OUTRUN) {
+      if constexpr (OUTRUN == 1) {
         mb_f64x2* orun = (mb_f64x2*)(out + (kk * batch + b0) * WOUT);
 #pragma unroll
         for (int r = 0; r < OROUNDS; ++r) {
@@ -367,10 +368,113 @@ __global__ __launch_bounds__(64 * G) void stream_group(const double* __restrict_
           if constexpr (DMA) { if (r < OROUNDS - 1 || OLASTW == G || olastw) orun[c] = ((const mb_f64x2*)ostage)[c]; }
           else { const int cc = c < COUT ? c : COUT - 1; orun[cc] = ((const mb_f64x2*)ostage)[cc]; }
         }
+      } else if constexpr (OUTRUN == 2) {             // every wave stores its whole WOUT-double record itself, 8 bytes per lane
+        double* o = out + (kk * batch + b0 + wv) * WOUT;
+#pragma unroll
+        for (int c = 0; c < (WOUT + 63) / 64; ++c) { const int e = c * 64 + lane; o[e < WOUT ? e : WOUT - 1] = acc + c; }
       } else {
         out[(kk * batch + b0 + wv) * WOUT + (lane % WOUT)] = acc;
       }
     }
+  }
+}
+// The same runs behind a register stage ONE knot point deep and a two-slot LDS ring (12 staging VGPRs at G = 16 instead of
+// 24): in step s every wave first reads its own records of knot point s out of slot s % 2, then every thread writes the
+// chunks it holds (knot point s + 1, requested one step ago) into slot (s + 1) % 2, requests knot point s + 2 into the freed
+// registers and crosses ONE bare barrier.  Slot (s + 1) % 2 was last read in step s - 1, before that step's barrier.
+// Chunks are dealt to whole waves: every wave-instruction lies inside one run, so its address is a wave-uniform base
+// (stepped per trip on the scalar unit) plus one 32-bit per-thread offset.  OUTRUN = 1: the OUT run leaves through a
+// double-buffered LDS stage, one step late, as 16-byte chunks; 2: every wave stores its own record, 8 bytes per lane.
+template <int RA, int RB, int WOUT, int OUTRUN, int G>
+struct StageOne {
+  static constexpr int T = 64 * G, NA = G * RA / 2, NB = G * RB / 2, CIN = NA + NB;
+  static constexpr int FA = NA / T, REMA = NA - FA * T, WA = (REMA + 63) / 64;   // full rounds of run A; waves of the mixed round on run A
+  static constexpr int B0 = REMA ? T - 64 * WA : 0;                            // chunks of run B fetched in the mixed round
+  static constexpr int ROUNDS = FA + (REMA ? 1 : 0) + (NB - B0 + T - 1) / T;
+  static constexpr int COUT = OUTRUN == 1 ? G * WOUT / 2 : 0;
+  static constexpr size_t lds_bytes = (size_t)(2 * CIN + 2 * COUT) * 16;
+};
+template <int RA, int RB, int WOUT, int OUTRUN, int G>
+__global__ __launch_bounds__(64 * G) void stream_group_stage1(const double* __restrict__ ina, const double* __restrict__ inb,
+                                                              double* __restrict__ out, int N, int batch) {
+  using SO = StageOne<RA, RB, WOUT, OUTRUN, G>;
+  constexpr int T = SO::T, ROUNDS = SO::ROUNDS, CIN = SO::CIN, COUT = SO::COUT;
+  constexpr int OROUNDS = (COUT + T - 1) / T;
+  static_assert(SO::lds_bytes <= 160 * 1024, "LDS of one CU");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  mb_f64x2* const ring = (mb_f64x2*)smem;
+  double* const ostage = (double*)(ring + 2 * CIN);
+  const int t = threadIdx.x, lane = t & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int ngrp = batch / G, chunk = ngrp / 8;
+  const int grp = (int)((blockIdx.x & 7) * chunk + (blockIdx.x >> 3));
+  const size_t b0 = (size_t)grp * G;
+  bool isa[ROUNDS];   // wave-uniform
+  int off[ROUNDS];    // chunk inside its run (past the end: the last chunk again)
+#pragma unroll
+  for (int r = 0; r < ROUNDS; ++r) {
+    if (r < SO::FA) { isa[r] = true; off[r] = r * T + t; }
+    else if (SO::REMA && r == SO::FA) {
+      isa[r] = wv < SO::WA;
+      off[r] = isa[r] ? (r * T + t < SO::NA ? r * T + t : SO::NA - 1) : t - 64 * SO::WA;
+    } else {
+      const int c = SO::B0 + (r - SO::FA - (SO::REMA ? 1 : 0)) * T + t;
+      isa[r] = false; off[r] = c < SO::NB ? c : SO::NB - 1;
+    }
+  }
+  const mb_f64x2* pa = (const mb_f64x2*)(ina + ((size_t)(N - 1) * batch + b0) * RA);   // knot point N - 1; stepped down per request
+  const mb_f64x2* pb = (const mb_f64x2*)(inb + ((size_t)(N - 1) * batch + b0) * RB);
+  const ptrdiff_t sa = (ptrdiff_t)batch * (RA / 2), sb = (ptrdiff_t)batch * (RB / 2);
+  mb_f64x2 regs[ROUNDS];
+  auto fetch = [&]() {
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) regs[r] = (isa[r] ? pa : pb)[off[r]];
+  };
+  auto stage = [&](int slot) {
+#pragma unroll
+    for (int r = 0; r < ROUNDS; ++r) ring[slot * CIN + (isa[r] ? 0 : SO::NA) + off[r]] = regs[r];
+  };
+  fetch();
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  stage(0);
+  if (N > 1) { pa -= sa; pb -= sb; }
+  fetch();
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // drained before the loop (see stream_group)
+  mb_barrier();
+  double acc = 0.0;
+  for (int s = 0; s < N; ++s) {
+    const size_t kk = N - 1 - s;
+    const int slot = s & 1;
+    const double* ra = (const double*)(ring + slot * CIN) + wv * RA;
+    const double* rb = (const double*)(ring + slot * CIN + SO::NA) + wv * RB;
+    double sum = 0;
+#pragma unroll
+    for (int c = 0; c < (RA + 63) / 64; ++c) { const int e = c * 64 + lane; sum += ra[e < RA ? e : RA - 1]; }
+#pragma unroll
+    for (int c = 0; c < (RB + 63) / 64; ++c) { const int e = c * 64 + lane; sum += rb[e < RB ? e : RB - 1]; }
+    acc += sum;
+    stage(slot ^ 1);                       // knot point s + 1 (the last steps re-stage knot point 0: nobody reads it)
+    if (s + 2 < N) { pa -= sa; pb -= sb; }
+    fetch();
+    if constexpr (OUTRUN == 1) {
+      if (s > 0) {   // the run of step s - 1, whole since that step's barrier
+        mb_f64x2* orun = (mb_f64x2*)(out + ((kk + 1) * batch + b0) * WOUT);
+#pragma unroll
+        for (int r = 0; r < OROUNDS; ++r) { const int c = r * T + t < COUT ? r * T + t : COUT - 1; orun[c] = ((const mb_f64x2*)ostage)[(slot ^ 1) * COUT + c]; }
+      }
+#pragma unroll
+      for (int c = 0; c < (WOUT + 63) / 64; ++c) { const int e = c * 64 + lane; ostage[slot * COUT * 2 + wv * WOUT + (e < WOUT ? e : WOUT - 1)] = acc + c; }
+    } else {
+      double* o = out + (kk * batch + b0 + wv) * WOUT;
+#pragma unroll
+      for (int c = 0; c < (WOUT + 63) / 64; ++c) { const int e = c * 64 + lane; o[e < WOUT ? e : WOUT - 1] = acc + c; }
+    }
+    mb_barrier();
+  }
+  if constexpr (OUTRUN == 1) {
+    mb_f64x2* orun = (mb_f64x2*)(out + b0 * WOUT);
+#pragma unroll
+    for (int r = 0; r < OROUNDS; ++r) { const int c = r * T + t < COUT ? r * T + t : COUT - 1; orun[c] = ((const mb_f64x2*)ostage)[((N - 1) & 1) * COUT + c]; }
   }
 }
 // the two record sets it is run on: the forward sweep's (DYN 204 + OUT 144 in, x | y | u 28 out per wave) and the backward sweep's
@@ -381,7 +485,7 @@ template <int G, int DEPTH, int DMA>
 constexpr auto stream_bwd_group = stream_group<204, 160, 144, 1, 1, G, DEPTH, DMA>;
 template <int RA, int RB, int WOUT, int OUTRUN, int DIR, int G, int DEPTH, int DMA>
 static int stream_group_prepare(size_t* lds_bytes) {
-  constexpr int CIN = G * (RA / 2 + RB / 2), SLOT = ((CIN + 63) / 64) * 64, COUT = OUTRUN ? G * WOUT / 2 : 0;
+  constexpr int CIN = G * (RA / 2 + RB / 2), SLOT = ((CIN + 63) / 64) * 64, COUT = OUTRUN == 1 ? G * WOUT / 2 : 0;
   *lds_bytes = (size_t)(DEPTH * SLOT + COUT) * 16;
   CK(hipFuncSetAttribute((const void*)stream_group<RA, RB, WOUT, OUTRUN, DIR, G, DEPTH, DMA>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)*lds_bytes));
   return 0;
@@ -437,6 +541,23 @@ int main(int argc, char** argv) {
       BWD_GROUP(16, 2, 1, "backward group G = 16, depth 2, LDS-DMA")
       BWD_GROUP(16, 3, 1, "backward group G = 16, depth 3, LDS-DMA")
       BWD_GROUP(16, 2, 0, "backward group G = 16, depth 2, load + ds_write")
+      // the OUT records stored by each wave itself, 8 bytes per lane, and the register stage one knot point deep (profiles/r08a_*)
+#define BWD_GROUP_DIRECT(G, DEPTH, DMA, label)                                                                           \
+      if (stream_group_prepare<204, 160, 144, 2, 1, G, DEPTH, DMA>(&l)) return 1;                                        \
+      bwd(label, [&] { stream_group<204, 160, 144, 2, 1, G, DEPTH, DMA><<<batch / G, 64 * G, l>>>(dyn, outr, out, N, batch); });
+      BWD_GROUP_DIRECT(16, 2, 1, "backward group G = 16, depth 2, LDS-DMA, OUT per wave")
+      BWD_GROUP_DIRECT(16, 2, 0, "backward group G = 16, depth 2, load + ds_write, OUT per wave")
+#define BWD_STAGE1(OUTRUN, label)                                                                                        \
+      {                                                                                                                  \
+        const auto kernel = stream_group_stage1<204, 160, 144, OUTRUN, 16>;                                              \
+        l = StageOne<204, 160, 144, OUTRUN, 16>::lds_bytes;                                                              \
+        CK(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)l));                \
+        bwd(label, [&] { kernel<<<batch / 16, 64 * 16, l>>>(dyn, outr, out, N, batch); });                               \
+      }
+      BWD_STAGE1(1, "backward group G = 16, stage 1 deep + 2 slots")
+      BWD_STAGE1(2, "backward group G = 16, stage 1 deep + 2 slots, OUT per wave")
+#undef BWD_STAGE1
+#undef BWD_GROUP_DIRECT
 #undef BWD_GROUP
       bwd("today: stream_mapped<364, 144> 1/wave depth 1", [&] { stream_mapped<364, 144, 1, 1><<<batch, 64>>>(in, out, N, batch); });
     }
