@@ -44,6 +44,7 @@ C_ABI_SYMBOLS = [
     "altro_hip_linesearch_host",
     "altro_hip_add_linear_constraint", "altro_hip_add_user_constraint", "altro_hip_clear_constraints", "altro_hip_reset_duals",
     "altro_hip_get_duals", "altro_hip_set_duals", "altro_hip_get_penalty", "altro_hip_set_penalty", "altro_hip_shift_duals", "altro_hip_feasibility",
+    "altro_hip_add_linear_constraint_rhs", "altro_hip_set_constraint_rhs", "altro_hip_get_constraint_rhs", "altro_hip_shift_constraint_rhs",
     "altro_hip_shift_trajectory", "altro_hip_update_linear_costs", "altro_hip_get_knot",
     "altro_hip_set_pointer_mode",
 ]
@@ -52,6 +53,7 @@ CONE_EQUALITY, CONE_IDENTITY, CONE_INEQUALITY, CONE_SOC = 0, 1, 2, 3   # Constra
 # altro_hip_solve_options::forms / altro_hip_set_forms (ALTRO_HIP_FORM_*): how a solve is executed.  The C library reads no environment
 # for these any more (version 300); THIS binding still translates the variables the test-suite and the tools set (forms_from_env), so
 # that one process can alternate forms between calls.
+RHS_PER_PROBLEM, RHS_PER_KNOT = 1, 2     # altro_hip_add_linear_constraint_rhs: how g is laid out, [nb][nk][p]
 DUAL_TAIL_KEEP, DUAL_TAIL_ZERO = 0, 1   # Batch.shift_duals: what the last knot point of a block's range becomes
 FORM_NO_SPECULATION, FORM_NO_RUNAHEAD, FORM_NO_MERIT2, FORM_MERIT_LDS, FORM_MERIT_DPP_ALWAYS = 0x1, 0x2, 0x4, 0x8, 0x10
 FORM_EXPAND_LDS, FORM_ALROWS_LDS, FORM_ROLLOUT_ROUNDS, FORM_SEQUENCED, FORM_MERIT_ONE_LAUNCH = 0x20, 0x40, 0x80, 0x100, 0x200
@@ -244,6 +246,10 @@ def lib():
         L.altro_hip_get_penalty.argtypes = [vp, vp]
         L.altro_hip_set_penalty.argtypes = [vp, vp, i]
         L.altro_hip_shift_duals.argtypes = [vp, i]
+        L.altro_hip_add_linear_constraint_rhs.argtypes = [vp, i, i, i, i, vp, vp, i]
+        L.altro_hip_set_constraint_rhs.argtypes = [vp, i, i, i, vp]
+        L.altro_hip_get_constraint_rhs.argtypes = [vp, i, i, vp]
+        L.altro_hip_shift_constraint_rhs.argtypes = [vp]
         L.altro_hip_feasibility.argtypes = [vp, vp]
         L.altro_hip_set_pointer_mode.argtypes = [vp, i]
         L.altro_hip_shift_trajectory.argtypes = [vp]
@@ -300,6 +306,7 @@ class Batch:
     def __init__(self, N, n, m, batch, dtype=F64, plan=PLAN_AUTO, flags=0, device=0, stream=None):
         self.L = lib()
         self.N, self.n, self.m, self.batch = N, n, m, batch
+        self._rhs_shape = {}   # block id -> (per problem, per knot, k_first, k_last, p): the shapes get_constraint_rhs returns
         self.h = C.c_void_p()
         _check(self.L.altro_hip_batch_create(C.byref(self.h), N, n, m, batch, dtype, plan, flags,
                                              device, stream))
@@ -319,6 +326,7 @@ class Batch:
         self.L = lib()
         self.nx = np.ascontiguousarray(nx, dtype=np.int32); self.nu = np.ascontiguousarray(nu, dtype=np.int32)
         self.N, self.n, self.m, self.batch = len(self.nu), int(self.nx.max()), int(self.nu.max()), batch
+        self._rhs_shape = {}
         assert len(self.nx) == self.N + 1
         self.h = C.c_void_p()
         _check(self.L.altro_hip_batch_create_dims(C.byref(self.h), self.N, self.nx.ctypes.data_as(C.c_void_p),
@@ -594,12 +602,25 @@ class Batch:
                                          u.ctypes.data_as(C.c_void_p) if u is not None else None))
         return x, u
 
-    def add_linear_constraint(self, k_first, k_last, cone, G, g):
+    def add_linear_constraint(self, k_first, k_last, cone, G, g, per_knot=False):
         """c = G [x;u] - g in `cone` at knot points k_first..k_last (inclusive).  G: (p, n+m) numpy (row-major
-        here, sent column-major); g: (p,) shared by the batch or (batch, p) per problem.  Returns the block id."""
+        here, sent column-major); g: (p,) shared by the batch or (batch, p) per problem.  With per_knot a right-hand side of its own
+        at every knot point of the range, K = k_last - k_first + 1 of them: g is (K, p) or (batch, K, p)
+        (altro_hip_add_linear_constraint_rhs; set_constraint_rhs / shift_constraint_rhs move them later).  Returns the block id."""
         G = np.asarray(G, dtype=np.float64)
         g = np.ascontiguousarray(g, dtype=np.float64)
         Gc = np.ascontiguousarray(G.T)
+        if per_knot:
+            K = int(k_last) - int(k_first) + 1
+            per_problem = int(g.ndim == 3)
+            assert g.shape == ((self.batch, K, G.shape[0]) if per_problem else (K, G.shape[0])), "g is (K, p) or (batch, K, p)"
+            rc = self.L.altro_hip_add_linear_constraint_rhs(self.h, int(k_first), int(k_last), int(cone), int(G.shape[0]),
+                                                            Gc.ctypes.data_as(C.c_void_p), g.ctypes.data_as(C.c_void_p),
+                                                            RHS_PER_KNOT | (RHS_PER_PROBLEM if per_problem else 0))
+            if rc < 0:
+                _check(rc)
+            self._rhs_shape[rc] = (per_problem, True, int(k_first), int(k_last), int(G.shape[0]))
+            return rc
         per_problem = int(g.ndim == 2)
         if per_problem:
             assert g.shape == (self.batch, G.shape[0])
@@ -608,7 +629,37 @@ class Batch:
                                                     per_problem)
         if rc < 0:
             _check(rc)
+        self._rhs_shape[rc] = (per_problem, False, int(k_first), int(k_last), int(G.shape[0]))
         return rc
+
+    def set_constraint_rhs(self, id, g, k_first=None, k_last=None):
+        """New right-hand sides for block `id`, in place: duals, penalty and tables stay.  A per_knot block takes (K', p) or
+        (batch, K', p) for knot points k_first..k_last inside its range (default: the whole range); any other linear block (p,) or
+        (batch, p).  A host array here; under set_pointer_mode(True) pass the integer address of an fp64 device array of that layout."""
+        kf, kl = (-1 if k_first is None else int(k_first)), (-1 if k_last is None else int(k_last))
+        if g is None or isinstance(g, int):
+            ptr = g
+        else:
+            g = np.ascontiguousarray(g, dtype=np.float64)
+            if int(id) in self._rhs_shape:     # the C side reads nb * nk * p doubles: never past the end of a smaller array
+                per_problem, per_knot, k0, k1, p = self._rhs_shape[int(id)]
+                nk = (k1 - k0 + 1 if (kf, kl) == (-1, -1) else kl - kf + 1) if per_knot else 1
+                want = ((self.batch,) if per_problem else ()) + ((nk,) if per_knot else ()) + (p,)
+                assert nk < 1 or g.shape == want, "g is %s for this block and range, not %s" % (want, g.shape)
+            ptr = g.ctypes.data_as(C.c_void_p)
+        _check(self.L.altro_hip_set_constraint_rhs(self.h, int(id), kf, kl, ptr))
+
+    def get_constraint_rhs(self, id, k):
+        """What the device holds as block `id`'s right-hand side at knot point k: (p,), or (batch, p) for a per-problem block."""
+        per_problem, _, _, _, p = self._rhs_shape.get(int(id), (0, False, 0, 0, 1))
+        out = np.zeros((self.batch, p) if per_problem else (p,))
+        _check(self.L.altro_hip_get_constraint_rhs(self.h, int(id), int(k), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def shift_constraint_rhs(self):
+        """The right-hand sides' part of shift_trajectory: every per_knot block's g moves one knot point forward; the last knot point
+        of its range keeps its values until set_constraint_rhs(id, g, k_last, k_last) writes the new ones."""
+        _check(self.L.altro_hip_shift_constraint_rhs(self.h))
 
     def add_user_constraint(self, k_first, k_last, cone, p, cid):
         """Block `cid` of the constraints the run-time compiled source defines (altro_hip_add_user_constraint)."""
@@ -619,6 +670,7 @@ class Batch:
 
     def clear_constraints(self):
         _check(self.L.altro_hip_clear_constraints(self.h))
+        self._rhs_shape.clear()
 
     def reset_duals(self, penalty=1.0):
         _check(self.L.altro_hip_reset_duals(self.h, float(penalty)))

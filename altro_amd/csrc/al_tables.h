@@ -25,7 +25,7 @@ struct AlInput {
   const std::vector<AlDef>& defs;
   const std::vector<AlKnotBig>& knots;          // [N + 1]: ncon and def[] of every knot point
   const std::vector<double>& G;                 // pool of G blocks, column-major p x w as given
-  const std::vector<std::vector<double>>& g;    // per block: [p] or [batch][p]
+  const std::vector<std::vector<double>>& g;    // per block: [p] or [batch][p]; with AlDef::g_per_knot [K][p] or [batch][K][p]
 };
 
 // what the kernels' launchers and the solve loop read about the tables as a whole (AlTable's scalar members among them); the default is
@@ -51,6 +51,7 @@ struct AlTables {
   std::vector<AlKnot> knots;        // [N + 1] (plans LANE, MFMA16; empty on plan GENERIC)
   std::vector<AlKnotBig> big;       // [N + 1] completed (plan GENERIC's device table, the host's record on every plan)
   std::vector<int> gsel, guser;     // AlTable::gsel (uniform plan GENERIC), AlTable::guser (... with a block from source); else empty
+  std::vector<AlDef> defs;          // the blocks as given, g_off filled in: where each one's segment of the g pool starts
   int rows = 0;                     // dual rows of one problem
   AlSummary sum;
   int error = AL_BUILD_OK, err_k = -1;
@@ -126,21 +127,21 @@ inline AlTables al_build(const AlInput& in) {
           t.Gpad[(size_t)(gp_base[i] + r / AL_MAXP) * AL_GP_DEF + (size_t)(r % AL_MAXP) * AL_GP_LD + dev_col(e)] = in.G[(size_t)d.G_off + r + (size_t)e * d.p];
     }
   }
-  // the g pool: [p] shared, or [p][batch]
+  // the g pool: [p] shared, or [p][batch]; a block with g_per_knot has one such run per knot point of its range, [K][p] or [K][p][batch]
+  // (al_types.h: al_g_index), given as [K][p] or [batch][K][p]
   std::vector<AlDef> defs = in.defs;
   for (size_t i = 0; i < nd; ++i) {
     defs[i].g_off = (int64_t)t.g.size();
+    const AlDef& d = defs[i];
     const std::vector<double>& src = in.g[i];
-    const int p = defs[i].p;
-    if (defs[i].g_per_problem) {
-      const size_t base = t.g.size();
-      t.g.resize(base + (size_t)p * B);
-      for (int64_t b = 0; b < B; ++b)
-        for (int r = 0; r < p; ++r) t.g[base + (size_t)r * B + b] = src[(size_t)b * p + r];
-    } else {
-      t.g.insert(t.g.end(), src.begin(), src.begin() + p);
-    }
+    const int p = d.p;
+    const int K = d.g_per_knot ? (int)(src.size() / ((size_t)p * (d.g_per_problem ? B : 1))) : 1;
+    t.g.resize(t.g.size() + (size_t)K * p * (d.g_per_problem ? B : 1));
+    for (int64_t b = 0; b < (d.g_per_problem ? B : 1); ++b)
+      for (int kk = 0; kk < K; ++kk)
+        for (int r = 0; r < p; ++r) t.g[(size_t)al_g_index(d, B, b, d.k_first + kk, r)] = src[((size_t)b * K + kk) * p + r];
   }
+  t.defs = defs;
   // the knot points' records
   t.big = in.knots;
   t.knots.assign(gen ? 0 : t.big.size(), AlKnot{});
@@ -153,7 +154,7 @@ inline AlTables al_build(const AlInput& in) {
       const int s0 = slot_base[bk.def[j]];
       bk.z_off[j] = rows; rows += d.p;
       bk.cone[j] = d.cone; bk.p[j] = d.p; bk.g_per_problem[j] = d.g_per_problem; bk.G_off[j] = G_off_dev[s0];
-      bk.g_off[j] = d.g_off;
+      bk.g_off[j] = al_g_index(d, B, 0, (int)k, 0);   // this knot point's run of the block's segment
       if (gen) continue;
       AlKnot& kn = t.knots[k];
       for (int sl = 0; sl < nslots(d); ++sl, ++ns) {
@@ -163,7 +164,7 @@ inline AlTables al_build(const AlInput& in) {
         kn.z_off[ns] = bk.z_off[j] + r0;
         kn.cone[ns] = d.cone; kn.p[ns] = ps; kn.g_per_problem[ns] = d.g_per_problem;
         kn.G_off[ns] = G_off_dev[(size_t)s0 + sl];
-        kn.g_off[ns] = d.g_off + (d.g_per_problem ? (int64_t)r0 * B : (int64_t)r0);   // g is [p] or [p][batch]: row r0 on
+        kn.g_off[ns] = al_g_index(d, B, 0, (int)k, r0);   // g is [p] or [p][batch] (per knot point with g_per_knot): row r0 on
         kn.user[ns] = d.user;
         kn.Gp_off[ns] = (tile && !d.user) ? (gp_base[bk.def[j]] + sl) * AL_GP_DEF : 0;
         // bound-type slot: every row of G is +-e_idx
@@ -213,6 +214,9 @@ inline AlTables al_build(const AlInput& in) {
       uni = t.big[k].ncon == k0.ncon;
       for (int j = 0; j < k0.ncon && uni; ++j) uni = t.big[k].def[j] == k0.def[j] && t.big[k].z_off[j] == k0.z_off[j] + k * r0;
     }
+    // a block with g_per_knot on a running knot point: every knot point reads its own record, whose g_off is its own
+    for (int k = 0; k < in.N && uni; ++k)
+      for (int j = 0; j < t.big[k].ncon && uni; ++j) uni = !defs[t.big[k].def[j]].g_per_knot;
     t.sum.uniform = uni ? 1 : 0;
     t.sum.rows_per_knot = r0;
   }

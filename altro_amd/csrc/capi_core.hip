@@ -162,7 +162,8 @@ static int batch_create_impl(altro_hip_batch** out, int N, int n, int m, int bat
     ALLOC(h->m_term, B * MF_TERM * E);
     ALLOC(h->m_out, B * N * MF_OUT * E);
     ALLOC(h->m_outn, B * MF_TERM * E);
-    ALLOC(h->m_xuy, B * (N + 1) * MF_XUY * E);
+    // (zero from the start, like the other plans' candidate trajectory: altro_hip_set_input_guess alone leaves the states defined)
+    ALLOC_ZERO(h->m_xuy, B * (N + 1) * MF_XUY * E);
     ALLOC(h->m_trash, B * MF_OUT * E);
     if (flags & ALTRO_HIP_STORE_QBLOCKS) ALLOC(h->m_qblk, B * N * MF_QB * E);
     if (!rc && (n < MF_N || m < MF_M)) {   // padded shape: whatever no setter writes must read as zero

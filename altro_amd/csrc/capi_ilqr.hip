@@ -28,9 +28,44 @@ static int al_copy_pool(altro_hip_batch* h, void** dst, const std::vector<double
   const std::vector<float> f = al_pool_as<float>(pool);
   return al_copy(h, dst, f.data(), f.size() * sizeof(float));
 }
+// the knot points block `id` is registered at (one contiguous range): k0 > k1 for an id that is on none
+static void al_def_range(const altro_hip_batch* h, int id, int& k0, int& k1) {
+  k0 = 0; k1 = -1;
+  for (int k = 0; k <= h->N; ++k)
+    for (int j = 0; j < h->al_knots[k].ncon; ++j)
+      if (h->al_knots[k].def[j] == id) { if (k1 < 0) k0 = k; k1 = k; }
+}
+// The host description must not go stale: blocks whose right-hand sides the device changed without the host seeing the values
+// (al_g_stale) are read back into al_g, from the pool as it stands and where the last upload put them (AlDef::g_off)
+static int al_mirror_refresh(altro_hip_batch* h) {
+  bool any = false;
+  for (char c : h->al_g_stale) any = any || c;
+  if (!any || !h->al_d_g) { h->al_g_stale.assign(h->al_defs.size(), 0); return 0; }
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  const int64_t B = h->batch;
+  for (size_t i = 0; i < h->al_g_stale.size() && i < h->al_defs.size(); ++i) {
+    if (!h->al_g_stale[i]) continue;
+    const AlDef& d = h->al_defs[i];
+    std::vector<double>& mirror = h->al_g[i];
+    const int64_t nb = d.g_per_problem ? B : 1;
+    const int K = (int)(mirror.size() / (size_t)(d.p * nb));
+    auto fetch = [&](auto t) -> int {
+      std::vector<decltype(t)> v(mirror.size());
+      HIP_TRY(hipMemcpy(v.data(), (const decltype(t)*)h->al_d_g + d.g_off, v.size() * sizeof(t), hipMemcpyDeviceToHost));
+      for (int64_t b = 0; b < nb; ++b)
+        for (int kk = 0; kk < K; ++kk)
+          for (int r = 0; r < d.p; ++r) mirror[((size_t)b * K + kk) * d.p + r] = v[(size_t)(al_g_index(d, B, b, d.k_first + kk, r) - d.g_off)];
+      return 0;
+    };
+    if (const int rc = h->dtype == ALTRO_HIP_F64 ? fetch(double{}) : fetch(float{})) return rc;
+  }
+  h->al_g_stale.assign(h->al_defs.size(), 0);
+  return 0;
+}
 // (re)build the device tables of the constraint blocks (al_tables.h decides what they contain); duals restart from zero when the
 // structure changes
 static int al_upload_tables(altro_hip_batch* h) {
+  if (const int rc = al_mirror_refresh(h)) return rc;
   for (void** p : {(void**)&h->al_d_knots, (void**)&h->al_d_big, (void**)&h->al_d_gsel, (void**)&h->al_d_guser, &h->al_d_G, &h->al_d_Gpad, &h->al_d_g, &h->al_d_z,
                    (void**)&h->al_d_order, (void**)&h->al_d_start})
     dfree(h, p);
@@ -58,6 +93,7 @@ static int al_upload_tables(altro_hip_batch* h) {
   if ((rc = al_copy(h, (void**)&h->al_d_start, sh.start.data(), sh.start.size() * sizeof(int)))) return rc;
   h->al_nchains = (int)sh.heads.size();
   h->al_knots = t.big;
+  h->al_defs = t.defs;   // (g_off: where each block's segment of the g pool starts)
   h->al_sum = t.sum; h->al_rows = t.rows;
   return 0;
 }
@@ -879,7 +915,8 @@ int altro_hip_get_knot(altro_hip_batch* h, int k, double* x, double* u) {
 
 // One more block on the handle's host tables: altro_hip_add_linear_constraint (user = 0), or altro_hip_add_user_constraint with
 // user = id + 1 and placeholders for G and g (AlDef::user)
-static int add_block(altro_hip_batch* h, int k_first, int k_last, int cone, int p, const double* G, const double* g, int g_per_problem, int user) {
+static int add_block(altro_hip_batch* h, int k_first, int k_last, int cone, int p, const double* G, const double* g, int g_per_problem, int user,
+                     int g_per_knot = 0) {
   // ALTROSolver::SetConstraint (altro_solver.cpp:175-215) for c(x,u) = G [x;u] - g
   int rc = loop_entry(h, true);
   if (rc) return rc;
@@ -913,9 +950,10 @@ static int add_block(altro_hip_batch* h, int k_first, int k_last, int cone, int 
     default: break;   // (the limits of a block from source: altro_hip_add_user_constraint has answered them)
   }
   const int w = ad.w;
-  AlDef d{cone, p, g_per_problem ? 1 : 0, (int)h->al_G.size(), 0, user, w};
+  AlDef d{cone, p, g_per_problem ? 1 : 0, (int)h->al_G.size(), 0, user, w, g_per_knot ? 1 : 0, g_per_knot ? k_first : 0};
   h->al_G.insert(h->al_G.end(), G, G + (size_t)p * w);
-  h->al_g.emplace_back(g, g + (size_t)p * (g_per_problem ? h->batch : 1));
+  h->al_g.emplace_back(g, g + (size_t)p * (g_per_problem ? h->batch : 1) * (g_per_knot ? k_last - k_first + 1 : 1));   // [nb][nk][p]
+  h->al_g_stale.resize(h->al_g.size(), 0);
   const int id = (int)h->al_defs.size();
   h->al_defs.push_back(d);
   for (int k = k_first; k <= k_last; ++k) {
@@ -928,6 +966,12 @@ static int add_block(altro_hip_batch* h, int k_first, int k_last, int cone, int 
 int altro_hip_add_linear_constraint(altro_hip_batch* h, int k_first, int k_last, int cone, int p, const double* G,
                                     const double* g, int g_per_problem) {
   return add_block(h, k_first, k_last, cone, p, G, g, g_per_problem, 0);
+}
+int altro_hip_add_linear_constraint_rhs(altro_hip_batch* h, int k_first, int k_last, int cone, int p, const double* G, const double* g,
+                                        int rhs_layout) {
+  if (rhs_layout & ~(ALTRO_HIP_RHS_PER_PROBLEM | ALTRO_HIP_RHS_PER_KNOT))
+    return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "unknown right-hand side layout %d (ALTRO_HIP_RHS_PER_PROBLEM = 1, ALTRO_HIP_RHS_PER_KNOT = 2)", rhs_layout);
+  return add_block(h, k_first, k_last, cone, p, G, g, rhs_layout & ALTRO_HIP_RHS_PER_PROBLEM, 0, rhs_layout & ALTRO_HIP_RHS_PER_KNOT);
 }
 int altro_hip_add_user_constraint(altro_hip_batch* h, int k_first, int k_last, int cone, int p, int id) {
   // ALTROSolver::SetConstraint with a general callback pair (altro_solver.cpp:192-223): value and Jacobian of block `id` come
@@ -963,7 +1007,7 @@ int altro_hip_clear_constraints(altro_hip_batch* h) {
   int rc = loop_entry(h, true);
   if (rc) return rc;
   h->expansion_current = false;
-  h->al_defs.clear(); h->al_G.clear(); h->al_g.clear();
+  h->al_defs.clear(); h->al_G.clear(); h->al_g.clear(); h->al_g_stale.clear();
   h->al_knots.assign((size_t)h->N + 1, AlKnotBig{});
   h->al_dirty = true;
   return al_upload(h);
@@ -1070,6 +1114,103 @@ int altro_hip_shift_duals(altro_hip_batch* h, int tail) {
   if (h->al_defs.empty()) return 0;
   if (al_shift_duals_launch(h->stream, h->al_d_z, h->dtype == ALTRO_HIP_F64 ? 8 : 4, h->al_d_order, h->al_d_start, h->al_nchains, h->batch, tail))
     return fail(ALTRO_HIP_ERR_HIP, "dual shift kernel launch failed");
+  return 0;
+}
+int altro_hip_set_constraint_rhs(altro_hip_batch* h, int id, int k_first, int k_last, const double* g) {
+  // new right-hand sides for block `id`, in place (kernels/al_rhs.hip): the tables are not rebuilt, duals and penalty stay
+  int rc = loop_entry(h, true);
+  if (rc) return rc;
+  if ((rc = al_upload(h))) return rc;
+  h->expansion_current = false; h->aff_base = false;
+  if (id < 0 || id >= (int)h->al_defs.size()) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "no constraint block with id %d", id);
+  const AlDef& d = h->al_defs[id];
+  if (d.user) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "constraint block %d comes from source: it has no right-hand side g", id);
+  int r0, r1;
+  al_def_range(h, id, r0, r1);
+  int kf = r0, kl = r0;
+  if (!d.g_per_knot) {
+    if (k_first != -1 || k_last != -1)
+      return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "constraint block %d has one right-hand side for its whole range [%d, %d] (registered without "
+                                              "ALTRO_HIP_RHS_PER_KNOT): it takes k_first = k_last = -1, not [%d, %d]", id, r0, r1, k_first, k_last);
+  } else if (k_first == -1 && k_last == -1) {
+    kl = r1;
+  } else {
+    if (k_first < r0 || k_last > r1 || k_first > k_last)
+      return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "knot point range [%d, %d] outside the range [%d, %d] of constraint block %d", k_first, k_last, r0, r1, id);
+    kf = k_first; kl = k_last;
+  }
+  if (!g) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "g is required");
+  const int64_t B = h->batch, nb = d.g_per_problem ? B : 1;
+  const int nk = kl - kf + 1, C = nk * d.p;
+  const size_t count = (size_t)nb * C;
+  const double* src = g;
+  if (!h->dev_ptrs) {
+    const bool f32 = h->dtype != ALTRO_HIP_F64;
+    for (size_t i = 0; i < count; ++i)
+      if (!(f32 ? std::isfinite((float)g[i]) : std::isfinite(g[i])))
+        return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "g[%zu] = %g is not finite%s", i, g[i], f32 ? " as a float" : "");
+    if ((rc = ensure_stage(h, count * sizeof(double)))) return rc;
+    HIP_TRY(hipMemcpyAsync(h->stage, g, count * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    src = (const double*)h->stage;
+    // the host description follows: [nb][K][p], K knot points from r0 on
+    std::vector<double>& mirror = h->al_g[id];
+    const int K = d.g_per_knot ? r1 - r0 + 1 : 1;
+    for (int64_t b = 0; b < nb; ++b)
+      std::copy(g + (size_t)b * C, g + (size_t)(b + 1) * C, mirror.begin() + ((size_t)b * K + (kf - r0)) * d.p);
+  } else {
+    h->al_g_stale[id] = 1;
+  }
+  const size_t E = h->dtype == ALTRO_HIP_F64 ? 8 : 4;
+  // (the scatter writes rows of `batch` consecutive problems, knot points and rows ascending from its base: al_g_index's layout)
+  if (al_rhs_scatter_launch(h->stream, (char*)h->al_d_g + (size_t)al_g_index(d, B, 0, kf, 0) * E, (int)E, src, C, (int)nb, h->batch, 0))
+    return fail(ALTRO_HIP_ERR_HIP, "right-hand side kernel launch failed");
+  HIP_TRY(hipStreamSynchronize(h->stream));   // (the caller's array and the staging buffer are free again on return)
+  return 0;
+}
+int altro_hip_get_constraint_rhs(altro_hip_batch* h, int id, int k, double* g) {
+  // what the device holds as block `id`'s right-hand side at knot point k, [nb][p]
+  int rc = loop_entry(h, true);
+  if (rc) return rc;
+  if ((rc = al_upload(h))) return rc;
+  if (id < 0 || id >= (int)h->al_defs.size()) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "no constraint block with id %d", id);
+  const AlDef& d = h->al_defs[id];
+  if (d.user) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "constraint block %d comes from source: it has no right-hand side g", id);
+  int r0, r1;
+  al_def_range(h, id, r0, r1);
+  if (k < r0 || k > r1) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "knot point %d outside the range [%d, %d] of constraint block %d", k, r0, r1, id);
+  if (!g) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "g is required");
+  const int64_t B = h->batch, nb = d.g_per_problem ? B : 1;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  auto fetch = [&](auto t) -> int {   // knot point k's run of the segment, [p] or [p][batch] in the handle's element type -> g [nb][p]
+    std::vector<decltype(t)> v((size_t)d.p * nb);
+    const int64_t at = al_g_index(d, B, 0, k, 0);
+    HIP_TRY(hipMemcpy(v.data(), (const decltype(t)*)h->al_d_g + at, v.size() * sizeof(t), hipMemcpyDeviceToHost));
+    for (int64_t b = 0; b < nb; ++b)
+      for (int r = 0; r < d.p; ++r) g[(size_t)b * d.p + r] = v[(size_t)(al_g_index(d, B, b, k, r) - at)];
+    return 0;
+  };
+  return h->dtype == ALTRO_HIP_F64 ? fetch(double{}) : fetch(float{});
+}
+int altro_hip_shift_constraint_rhs(altro_hip_batch* h) {
+  // the right-hand sides' part of altro_hip_shift_trajectory: every ALTRO_HIP_RHS_PER_KNOT block's g moves one knot point forward
+  int rc = loop_entry(h, true);
+  if (rc) return rc;
+  if (h->ragged) return fail(ALTRO_HIP_ERR_UNSUPPORTED, "altro_hip_shift_constraint_rhs needs uniform dimensions");
+  h->expansion_current = false; h->aff_base = false;
+  if ((rc = al_upload(h))) return rc;
+  const size_t E = h->dtype == ALTRO_HIP_F64 ? 8 : 4;
+  for (size_t i = 0; i < h->al_defs.size(); ++i) {
+    const AlDef& d = h->al_defs[i];
+    if (!d.g_per_knot) continue;
+    int r0, r1;
+    al_def_range(h, (int)i, r0, r1);
+    if (r1 <= r0) continue;
+    // the segment's first element and the distance between two knot points' runs, as al_g_index has them
+    const int64_t first = al_g_index(d, h->batch, 0, r0, 0), stride = al_g_index(d, h->batch, 0, r0 + 1, 0) - first;
+    if (al_rhs_shift_launch(h->stream, (char*)h->al_d_g + (size_t)first * E, (int)E, r1 - r0 + 1, stride))
+      return fail(ALTRO_HIP_ERR_HIP, "right-hand side shift kernel launch failed");
+    h->al_g_stale[i] = 1;
+  }
   return 0;
 }
 

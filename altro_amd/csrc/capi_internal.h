@@ -147,7 +147,10 @@ struct altro_hip_batch {
   std::vector<AlDef> al_defs;
   std::vector<AlKnotBig> al_knots;       // (the device table is AlKnot for plans LANE / MFMA16, AlKnotBig for plan GENERIC)
   std::vector<double> al_G;                  // pool of G blocks, column-major p x (n+m)
-  std::vector<std::vector<double>> al_g;     // per block: [p] or [batch][p]
+  std::vector<std::vector<double>> al_g;     // per block: [p] or [batch][p]; with AlDef::g_per_knot [K][p] or [batch][K][p]
+  // per block: the device holds newer values than al_g (altro_hip_set_constraint_rhs from a device array, altro_hip_shift_constraint_rhs);
+  // the next rebuild of the tables reads those blocks' segments back first (capi_ilqr.hip: al_mirror_refresh)
+  std::vector<char> al_g_stale;
   int al_rows = 0;
   capi::AlSummary al_sum;                         // what al_upload derived from the blocks (al_tables.h), assigned as one value
   bool al_dirty = false;
@@ -672,6 +675,8 @@ bool mfma16_forward_is_x4(const altro_hip_batch* h);   // the forward sweep runs
 // al_shift_launch.hip (kernels/al_shift.hip): 0 ok, 2 launch failed
 int al_shift_duals_launch(hipStream_t stream, void* z, int esz, const int* order, const int* start, int nchains, int batch, int tail);
 int al_set_penalty_launch(hipStream_t stream, IlqrProb* prob, const double* rho, int stride, int batch);
+int al_rhs_scatter_launch(hipStream_t stream, void* dst, int esz, const double* src, int C, int nb, int batch, int form);
+int al_rhs_shift_launch(hipStream_t stream, void* g, int esz, int K, int64_t stride);
 int al_get_penalty_launch(hipStream_t stream, const IlqrProb* prob, double* rho, int batch);
 namespace capi {
 

@@ -45,7 +45,18 @@ struct AlDef {
   int64_t g_off;   // into the g pool (elements): [p] shared, or [p][batch]
   int user;        // 0: c = G [x;u] - g;  id + 1: rows and Jacobian come from the caller's run-time compiled source
   int w = 0;       // columns of G as given: n + m of the handle, or nx[k] + nu[k] of the block's knot points (per-knot-point dimensions)
+  // altro_hip_add_linear_constraint_rhs with ALTRO_HIP_RHS_PER_KNOT: the block's g pool segment holds one [p] / [p][batch] run for every
+  // knot point of its range, [K][p] shared or [K][p][batch], and k_first is the range's first knot point (al_g_index); else 0, 0
+  int g_per_knot = 0, k_first = 0;
 };
+// Where element (problem b, knot point k, row r) of block d's right-hand side lives in the g pool: al_build's g_off entries, the getter,
+// and the host mirror's read-back ask here for every element; the launches of al_rhs.hip take their base (and the shift its stride between
+// knot points) from it, and the scatter kernel itself writes what this says: rows ascending over (knot point, row), `batch` consecutive
+// problems per row.  A block without g_per_knot has one run for every k.
+__host__ __device__ inline int64_t al_g_index(const AlDef& d, int64_t batch, int64_t b, int k, int r) {
+  const int64_t row = (d.g_per_knot ? (int64_t)(k - d.k_first) * d.p : 0) + r;
+  return d.g_off + (d.g_per_problem ? row * batch + b : row);
+}
 struct AlKnot {          // everything a kernel needs about knot point k in ONE wave-uniform record
   int ncon;               // plan LANE: blocks (<= AL_MAXC); plan MFMA16: slots (<= AL_TILE_MAXC)
   int def[AL_TILE_MAXC];

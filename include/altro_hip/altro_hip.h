@@ -187,7 +187,8 @@ int altro_hip_set_cost(altro_hip_batch* h, const double* Q, const double* R, con
                        int batch_stride_zero);
 int altro_hip_set_initial_state(altro_hip_batch* h, const double* x0, int batch_stride_zero);
 /* Pointer mode of the BULK arrays: with device_pointers != 0 the A, B, f, Q, R, H, q, r, x0, u arguments of
- * altro_hip_set_dynamics / set_cost / set_initial_state / set_input_guess / update_linear_costs and the outputs of
+ * altro_hip_set_dynamics / set_cost / set_initial_state / set_input_guess / update_linear_costs, the g of
+ * altro_hip_set_constraint_rhs and the outputs of
  * altro_hip_get_K .. get_y / get_nominal / get_knot are DEVICE pointers (fp64, the same reference layout) on the
  * handle's device: kernels on the handle's stream read / write them in place, no staging copy -- for callers whose
  * linearisation already lives in HBM.  Everything else (status, delta_V, alpha / phi, results, duals, tracking-cost
@@ -434,6 +435,41 @@ int altro_hip_set_duals(altro_hip_batch* h, int k, int slot, const double* z /* 
 int altro_hip_get_penalty(altro_hip_batch* h, double* rho /* [batch] */);
 int altro_hip_set_penalty(altro_hip_batch* h, const double* rho, int batch_stride_zero);
 int altro_hip_shift_duals(altro_hip_batch* h, int tail);
+/* Right-hand sides per knot point, set in place and shifted: a bound that moves along the horizon or with the measured
+ * state -- a corridor around a moving reference, a drifting half-plane, an input limit that depends on the battery -- without
+ * altro_hip_clear_constraints, which rebuilds every table and zeroes the duals altro_hip_shift_duals has just carried over.  The reference
+ * takes a closure per knot point (ALTROSolver::SetConstraint, altro_solver.cpp:175-215).  Every plan, both element types, handles with
+ * per-knot-point dimensions included (g carries no state dimension).  No kernel of the iLQR loop differs: each reads a knot point's g
+ * where that knot point's table record says.
+ *   altro_hip_add_linear_constraint_rhs   altro_hip_add_linear_constraint with g as [nb][nk][p]: nb = batch with
+ *                          ALTRO_HIP_RHS_PER_PROBLEM, else 1; nk = k_last - k_first + 1 with ALTRO_HIP_RHS_PER_KNOT, else 1.  Layouts 0 and 1
+ *                          ARE altro_hip_add_linear_constraint: same tables, capacities and errors.  A PER_KNOT block is ONE definition
+ *                          (one of the plan's 16 / 32 slots / 64) and one chain of altro_hip_shift_duals, whatever its range.  A handle
+ *                          with such a block on a running knot point (k < N) leaves the tables' uniform path: its kernels read every
+ *                          knot point's own record (what that costs: DESIGN.md 4.35).  Unknown layout bits: ALTRO_HIP_ERR_BAD_ARGUMENT.
+ *   altro_hip_set_constraint_rhs   new values for block `id` (any linear block, one from altro_hip_add_linear_constraint included),
+ *                          written in place by one kernel: the tables are not rebuilt, duals and penalty are untouched.  On a PER_KNOT
+ *                          block k_first .. k_last must lie inside the block's own range and g is [nb][k_last - k_first + 1][p];
+ *                          k_first = k_last = -1 is the whole range.  A block without PER_KNOT takes only -1, -1 and g as [nb][p].
+ *                          g follows altro_hip_set_pointer_mode: a host array is checked -- an entry that is not finite (fp32 handles:
+ *                          not finite as a float) is ALTRO_HIP_ERR_BAD_ARGUMENT and nothing is written --; a device array (fp64, the
+ *                          same layout, on the handle's device) is read in place and its values are NOT inspected.  Errors, all
+ *                          ALTRO_HIP_ERR_BAD_ARGUMENT with nothing written: an unknown id, a block from source (it has no g), a range
+ *                          outside the block's (both are named), NULL g.  Synchronises its stream before returning.
+ *   altro_hip_get_constraint_rhs   what the device holds for block `id` at knot point k, widened to double, [nb][p].  g is always a host
+ *                          array.  k outside the block's range: ALTRO_HIP_ERR_BAD_ARGUMENT.
+ *   altro_hip_shift_constraint_rhs   the companion of altro_hip_shift_trajectory and altro_hip_shift_duals: for every PER_KNOT block, g at
+ *                          k becomes what it was at k + 1; the last knot point of the range keeps its values (the caller then writes
+ *                          the new last one: altro_hip_set_constraint_rhs(h, id, k_last, k_last, g)).  Other blocks are untouched; a
+ *                          handle without PER_KNOT blocks returns 0.  Per-knot-point dimensions: ALTRO_HIP_ERR_UNSUPPORTED, like
+ *                          altro_hip_shift_duals.
+ * Blocks added later rebuild the tables with the values the device holds at that time (and zero the duals, as ever).                  */
+enum { ALTRO_HIP_RHS_PER_PROBLEM = 1, ALTRO_HIP_RHS_PER_KNOT = 2 };
+int altro_hip_add_linear_constraint_rhs(altro_hip_batch* h, int k_first, int k_last, int cone, int p, const double* G, const double* g,
+                                        int rhs_layout);
+int altro_hip_set_constraint_rhs(altro_hip_batch* h, int id, int k_first, int k_last, const double* g);
+int altro_hip_get_constraint_rhs(altro_hip_batch* h, int id, int k, double* g /* host, [nb][p] */);
+int altro_hip_shift_constraint_rhs(altro_hip_batch* h);
 /* SolverImpl::Feasibility (solver.cpp:224-231) of the candidate trajectory, [batch].                  */
 int altro_hip_feasibility(altro_hip_batch* h, double* out);
 

@@ -125,6 +125,18 @@ class BatchSolver {
   void SetPenalty(const double* rho) { Check(altro_hip_set_penalty(h_, rho, 0)); }   // rho [batch]
   void SetPenalty(double rho) { Check(altro_hip_set_penalty(h_, &rho, 1)); }          // one value for every problem
   void ShiftDuals(int tail = ALTRO_HIP_DUAL_TAIL_KEEP) { Check(altro_hip_shift_duals(h_, tail)); }
+  // Right-hand sides per knot point (altro_hip.h: altro_hip_add_linear_constraint_rhs and its siblings): SetConstraint with g as
+  // [nb][nk][p] (rhs_layout: ALTRO_HIP_RHS_PER_PROBLEM | ALTRO_HIP_RHS_PER_KNOT), new values in place for knot points k_first .. k_last of
+  // block `id` (-1, -1: its whole range; g follows the pointer mode), what the device holds at knot point k ([nb][p], host), and the
+  // right-hand sides' part of ShiftTrajectory
+  int AddLinearConstraintRhs(int k_start, int k_stop, Cone cone, int p, const double* G, const double* g, int rhs_layout) {
+    const int id = altro_hip_add_linear_constraint_rhs(h_, k_start, k_stop, static_cast<int>(cone), p, G, g, rhs_layout);
+    if (id < 0) Check(id);
+    return id;
+  }
+  void SetConstraintRhs(int id, const double* g, int k_first = -1, int k_last = -1) { Check(altro_hip_set_constraint_rhs(h_, id, k_first, k_last, g)); }
+  void GetConstraintRhs(int id, int k, double* g) { Check(altro_hip_get_constraint_rhs(h_, id, k, g)); }
+  void ShiftConstraintRhs() { Check(altro_hip_shift_constraint_rhs(h_)); }
 
   // ---- solve ------------------------------------------------------------------------------------------------------
   altro_hip_solve_options opts;   // AltroOptions (solver_options.hpp:16-39)
