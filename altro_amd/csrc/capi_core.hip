@@ -634,12 +634,7 @@ int profile_drain(altro_hip_batch* h) {   // mode 2: turn the recorded event pai
   HIP_TRY(hipStreamSynchronize(h->stream));
   for (int i = 0; i < h->prof_n; ++i) {
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, h->prof_ev[2 * i], h->prof_ev[2 * i + 1]) != hipSuccess) continue;
-    const int slot = h->prof_slot[i];
-    h->prof_min[slot] = h->prof_launches[slot] ? std::min(h->prof_min[slot], (double)ms) : (double)ms;
-    h->prof_max[slot] = std::max(h->prof_max[slot], (double)ms);
-    h->prof_ms[slot] += ms;
-    h->prof_launches[slot] += 1;
+    if (hipEventElapsedTime(&ms, h->prof_ev[2 * i], h->prof_ev[2 * i + 1]) == hipSuccess) profile_add(h, h->prof_slot[i], ms);
   }
   h->prof_n = 0;
   return 0;
@@ -652,27 +647,13 @@ int altro_hip_profile_get(altro_hip_batch* h, int slot, int* launches, double* t
   if (rc) return rc;
   if (launches) *launches = h->prof_launches[slot];
   if (total_ms) *total_ms = h->prof_ms[slot];
-  if (kernel_name) {
-    static const char* names[3][2] = {{"generic_backward_kernel", "generic_forward_kernel"},
-                                      {"mfma16_backward_kernel", "mfma16_forward_kernel"},
-                                      {"lane_backward_kernel", "lane_forward_kernel"}};
-    *kernel_name = names[h->plan == ALTRO_HIP_PLAN_MFMA16 ? 1 : (h->plan == ALTRO_HIP_PLAN_LANE ? 2 : 0)][slot];
-    if (h->g_tile && !(slot == 0 && h->is_diag)) *kernel_name = slot == 0 ? "tile32_backward_kernel" : "tile32_forward_kernel";
-    if (slot == 0 && h->plan == ALTRO_HIP_PLAN_LANE && h->bwd_quad) *kernel_name = h->n == 4 ? "quad_backward_kernel" : "quad2_backward_kernel";
-    if (slot == 1 && h->plan == ALTRO_HIP_PLAN_LANE && h->fwd_quad) *kernel_name = "quad_forward_kernel";
-    if (slot == 1 && mfma16_forward_is_x4(h)) *kernel_name = "mfma16_forward_f32x4_kernel";
-    if (slot == 1 && mfma16_forward_is_group(h)) *kernel_name = "mfma16_forward_group_kernel";
-    if (slot == 0 && h->plan == ALTRO_HIP_PLAN_MFMA16 && h->bwd_group) *kernel_name = "mfma16_backward_group_kernel";
-    if (slot == 0 && h->plan == ALTRO_HIP_PLAN_MFMA16 && h->dtype == ALTRO_HIP_F32 && (h->flags & ALTRO_HIP_F32_PURE) &&
-        !(h->flags & ALTRO_HIP_STORE_QBLOCKS))
-      *kernel_name = (h->batch % 4 == 0) ? "mfma16_backward_f32x4_kernel"
-                                                                                    : "mfma16_backward_f32_kernel";
-  }
+  // the last launch's kernel; before any, what an unmasked launch of the handle as it stands would take
+  if (kernel_name) *kernel_name = sweep_kernel_name((h->sweep_launched[slot] ? h->last_sweep[slot] : sweep_route(sweep_shape(h), SweepCall{slot == 0, false})).id);
   return 0;
 }
 int altro_hip_sweep_variant(const altro_hip_batch* h, int slot, int* bits) {
   if (!h || !bits || slot < 0 || slot > 1) return fail(ALTRO_HIP_ERR_BAD_ARGUMENT, "bad handle, slot or result pointer");
-  *bits = h->sweep_variant[slot];
+  *bits = h->last_sweep[slot].variant;
   return 0;
 }
 int altro_hip_profile_dropped(altro_hip_batch* h, int slot) {

@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -28,6 +29,7 @@
 #include "device_ledger.h"
 #include "loop_fields.h"
 #include "loop_route.h"
+#include "sweep_route.h"
 #include "rtc_unit.h"
 
 namespace altro_hip {
@@ -43,6 +45,10 @@ int fail(int code, const char* fmt, ...);
       return ::altro_hip::capi::fail(ALTRO_HIP_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
                   __FILE__, __LINE__);                                                        \
   } while (0)
+
+// a sweep launch that carries the profiling events of the enclosing ProfScope (capi_tvlqr.hip; null events: a plain launch)
+#define PROF_LAUNCH(kernel, grid, block, lds, stream, ...) \
+  hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, h->launch_ev0, h->launch_ev1, 0, __VA_ARGS__)
 
 constexpr size_t kStageBytes = size_t(256) << 20;
 
@@ -87,7 +93,6 @@ struct altro_hip_batch {
   Mfma16Strides m_st{};
   bool fwd_group_ready = false;   // mfma16_forward_group_kernel may use its dynamic LDS on this handle's device
   bool bwd_group_ready = false;   // ... and mfma16_backward_group_kernel
-  bool bwd_group = false;         // the last MFMA16 backward sweep ran one workgroup per 16 problems (kernels/tvlqr_mfma16_bwd_group.hip)
   // plan LANE: batch structure-of-arrays ([k][element][batch])
   void *l_in = nullptr, *l_term = nullptr, *l_out = nullptr, *l_outn = nullptr, *l_xuy = nullptr,
        *l_x0 = nullptr;
@@ -123,9 +128,8 @@ struct altro_hip_batch {
   int merit_split = -1;           // -1: not decided yet (ALTRO_HIP_MERIT_SPLIT, default on)
   void *i_results = nullptr, *i_results_host = nullptr;   // per-problem solve results: device gather + pinned staging (first solve)
   void* g_ws = nullptr;           // plan GENERIC, blocks beyond 64 KB of LDS: the backward sweep's per-problem work blocks (first use)
-  bool fwd_quad = false;          // the last LANE forward sweep ran four lanes per problem
-  bool bwd_quad = false;          // the last LANE backward sweep ran four lanes per problem (kernels/tvlqr_quad_body.inc)
-  int sweep_variant[2] = {0, 0};  // ALTRO_HIP_SWEEP_* bits of the last backward / forward launch (altro_hip_sweep_variant; sweep_route.h)
+  SweepRoute last_sweep[2];       // what the last backward / forward launch was given (sweep_route.h): altro_hip_sweep_variant, altro_hip_profile_get
+  bool sweep_launched[2] = {false, false};   // ... once there has been one
   bool spec_no_memory = false;    // the spare trajectories could not be allocated: no speculation on this handle
   ModelParams model{MODEL_LINEAR, 0.0f, 0, 2.7, 1.5};
   // altro_hip_set_time_steps: the handle's float[N] on the device (allocated on first use) and its host copy; in effect while
@@ -580,6 +584,11 @@ inline int lane_get(altro_hip_batch* h, double* host, const void* base, int64_t 
 inline LoopShape loop_shape(const altro_hip_batch* h) {
   return LoopShape{h->plan, h->ragged, h->cost_dense, h->n, h->m, h->N, h->batch, h->m_st.xuy_bs, h->m_st.xuy_ks, h->nxv.data(), h->nuv.data()};
 }
+// what the route of a TVLQR sweep launch may depend on (sweep_route.h)
+inline SweepShape sweep_shape(const altro_hip_batch* h) {
+  return SweepShape{h->plan, h->dtype == ALTRO_HIP_F64, h->flags, h->forms, h->n, h->m, h->N, h->batch, h->is_diag != 0, h->has_f && !h->ilqr_linear,
+                    h->g_tile, h->g_mfma, h->m_st.in_bs, h->m_st.in_ks, h->m_st.cin_bs, h->m_st.cin_ks, h->m_st.out_bs, h->m_st.out_ks};
+}
 inline void* loop_buffer(const altro_hip_batch* h, int buf) {
   void* const p[] = {nullptr, h->g_arr[G_x], h->g_arr[G_u], h->g_xn, h->g_un, h->g_cQ, h->g_cR, h->g_cH, h->g_cq, h->g_cr, h->g_cc,
                      h->m_xuy, h->m_nom, h->m_costp, h->m_costd, h->m_costd_term, h->l_xuy, h->l_nom, h->l_cost, h->l_costq};
@@ -668,8 +677,7 @@ bool tile32_supported(int n, int m);                        // capi_tile32.hip: 
 int tile32_launch_backward(altro_hip_batch* h, double reg, const BackwardMask& pp);
 int tile32_launch_forward(altro_hip_batch* h);
 int launch_forward(altro_hip_batch* h);
-bool mfma16_forward_is_group(const altro_hip_batch* h);   // the fp64 forward sweep runs one workgroup per 16 problems
-bool mfma16_forward_is_x4(const altro_hip_batch* h);   // the forward sweep runs four problems per wave (pure fp32)
+void profile_add(altro_hip_batch* h, int slot, float ms);   // capi_tvlqr.hip: one timed launch into the slot's totals
 
 }  // namespace capi
 // al_shift_launch.hip (kernels/al_shift.hip): 0 ok, 2 launch failed

@@ -5,9 +5,6 @@
 using namespace altro_hip;
 using namespace altro_hip::capi;
 
-#define PROF_LAUNCH(kernel, grid, block, lds, stream, ...) \
-  hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, h->launch_ev0, h->launch_ev1, 0, __VA_ARGS__)
-
 namespace {
 
 Tile32Args tile32_args(altro_hip_batch* h, double reg, const BackwardMask& pp) {
@@ -66,8 +63,7 @@ int tile32_launch_forward(altro_hip_batch* h) {
   const Tile32Args a = tile32_args(h, 0.0, {});
   const int kc = (h->n + 3) / 4, mc = (h->m + 3) / 4;
 #define T32_CASE(KC_, MC_) if (kc == KC_ && mc == MC_) return forward_launch<KC_, MC_>(h, a);
-  T32_CASE(2, 2) T32_CASE(3, 2) T32_CASE(4, 1) T32_CASE(4, 2) T32_CASE(5, 1) T32_CASE(5, 2) T32_CASE(6, 1) T32_CASE(6, 2)
-  T32_CASE(7, 1) T32_CASE(7, 2) T32_CASE(8, 1)
+  TILE32_FORWARD_TILES(T32_CASE)   // (sweep_route.h)
 #undef T32_CASE
   return fail(ALTRO_HIP_ERR_UNSUPPORTED, "plan MFMA32 has no forward kernel for (n, m) = (%d, %d)", h->n, h->m);
 }

@@ -160,6 +160,7 @@ OTHER = [
     ("cost of the per-launch events", "r03zd_event_overhead_ext.txt", "tools/event_overhead.py"),
     ("HBM streaming roof of the backward sweep's traffic, no arithmetic", "r01_membench.txt", "tools/membench.hip"),
     ("run-to-run spread on one box", "r01e_bench_repeat.txt", "bench.py x 8"),
+    ("host cost of routing every sweep launch through sweep_route.h (parent / branch / parent, every config)", "sweep_route_ab.txt", "bench.py --config c1..c4, parent and branch alternately"),
 ]
 
 if __name__ == "__main__":
