@@ -25,7 +25,8 @@ TVLQR_SUCCESS = -1
 C_ABI_SYMBOLS = [
     "altro_hip_version", "altro_hip_last_error", "altro_hip_device_count", "altro_hip_device_info", "altro_hip_device_pci_bus_id",
     "altro_hip_batch_create", "altro_hip_batch_create_dims", "altro_hip_batch_destroy", "altro_hip_batch_plan",
-    "altro_hip_batch_device_bytes", "altro_hip_set_dynamics", "altro_hip_set_cost",
+    "altro_hip_batch_device_bytes", "altro_hip_set_dynamics", "altro_hip_set_dynamics_range", "altro_hip_get_dynamics_knot",
+    "altro_hip_shift_dynamics", "altro_hip_shift_linear_costs", "altro_hip_set_cost",
     "altro_hip_set_initial_state", "altro_hip_set_host_batch", "altro_hip_backward", "altro_hip_backward_per_problem", "altro_hip_forward_ltv", "altro_hip_sweep",
     "altro_hip_synchronize", "altro_hip_get_K", "altro_hip_get_d", "altro_hip_get_P",
     "altro_hip_get_p", "altro_hip_get_x", "altro_hip_get_u", "altro_hip_get_y",
@@ -189,6 +190,10 @@ def lib():
         L.altro_hip_batch_device_bytes.argtypes = [vp]
         L.altro_hip_batch_device_bytes.restype = C.c_size_t
         L.altro_hip_set_dynamics.argtypes = [vp, vp, vp, vp, i, i]
+        L.altro_hip_set_dynamics_range.argtypes = [vp, vp, vp, vp, i, i, i]
+        L.altro_hip_get_dynamics_knot.argtypes = [vp, i, vp, vp, vp]
+        L.altro_hip_shift_dynamics.argtypes = [vp]
+        L.altro_hip_shift_linear_costs.argtypes = [vp]
         L.altro_hip_set_cost.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i]
         L.altro_hip_set_initial_state.argtypes = [vp, vp, i]
         L.altro_hip_set_host_batch.argtypes = [vp, i]
@@ -343,6 +348,24 @@ class Batch:
         altro_hip.h).  The numpy-based helpers of this class always pass host arrays; use `self.L` + `self.h` with
         your own device pointers (e.g. torch tensors' data_ptr()) while the mode is on."""
         _check(self.L.altro_hip_set_pointer_mode(self.h, int(bool(device_pointers))))
+        self._device_pointers = bool(device_pointers)
+
+    def _bulk(self, a):
+        """One bulk array of a call that takes either kind: a numpy array (host; pointer mode off) or a torch device tensor (float64,
+        contiguous; pointer mode on).  -> (the object to keep alive, its address).  The kind must match the handle's pointer mode: the
+        library would read a host address on the device otherwise."""
+        if a is None:
+            return None, None
+        dev = getattr(self, "_device_pointers", False)
+        if hasattr(a, "data_ptr"):
+            if not dev:
+                raise ValueError("a device tensor needs set_pointer_mode(True)")
+            if str(a.dtype) != "torch.float64" or not a.is_contiguous() or not a.is_cuda:
+                raise ValueError("device tensors must be contiguous float64 tensors on the GPU")
+            return a, C.c_void_p(a.data_ptr())
+        if dev:
+            raise ValueError("pointer mode is on: pass device tensors, or set_pointer_mode(False) first")
+        return _in(a)
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
@@ -357,6 +380,36 @@ class Batch:
     def set_dynamics(self, A, B, f=None, k_stride_zero=False, batch_stride_zero=False):
         (a, pa), (b, pb), (c, pc) = _in(A), _in(B), _in(f)
         _check(self.L.altro_hip_set_dynamics(self.h, pa, pb, pc, int(k_stride_zero), int(batch_stride_zero)))
+
+    def set_dynamics_range(self, A, B, f, k_first, k_last, batch_stride_zero=False):
+        """altro_hip_set_dynamics_range: set_dynamics for knot points k_first .. k_last (inclusive) only, everything else keeps its
+        bits.  A [nb, nk, n*n], B [nb, nk, n*m], f [nb, nk, n] or None (zeros), column-major blocks, nk = k_last - k_first + 1, nb = 1
+        with batch_stride_zero.  numpy arrays, or -- under set_pointer_mode(True) -- float64 torch device tensors read in place."""
+        nb, nk = (1 if batch_stride_zero else self.batch), int(k_last) - int(k_first) + 1
+        keep = [self._bulk(v) for v in (A, B, f)]
+        for (a, _), blk in zip(keep, (self.n * self.n, self.n * self.m, self.n)):   # the C side reads nb * nk * block doubles
+            if a is not None and nk > 0 and int(np.prod(a.shape)) != nb * nk * blk:
+                raise ValueError("expected %d x %d x %d entries, got shape %s" % (nb, nk, blk, tuple(a.shape)))
+        _check(self.L.altro_hip_set_dynamics_range(self.h, keep[0][1], keep[1][1], keep[2][1], int(k_first), int(k_last),
+                                                   int(batch_stride_zero)))
+
+    def get_dynamics_knot(self, k):
+        """altro_hip_get_dynamics_knot: what the device holds at knot point k, as float64 numpy arrays A [batch, n*n], B [batch, n*m],
+        f [batch, n] (column-major blocks, the tile's padding stripped), in either pointer mode."""
+        A = np.zeros((self.batch, self.n * self.n)); B = np.zeros((self.batch, self.n * self.m)); f = np.zeros((self.batch, self.n))
+        _check(self.L.altro_hip_get_dynamics_knot(self.h, int(k), *[v.ctypes.data_as(C.c_void_p) for v in (A, B, f)]))
+        return A, B, f
+
+    def shift_dynamics(self):
+        """The dynamics' part of shift_trajectory (dynamics given as data): (A, B, f) of knot points 0 .. N-2 become those of k + 1,
+        in place; N-1 keeps its values until set_dynamics_range(A, B, f, N-1, N-1) writes the new ones."""
+        _check(self.L.altro_hip_shift_dynamics(self.h))
+
+    def shift_linear_costs(self):
+        """The companion of update_linear_costs for a reference that moves with the horizon: (q, r, c) of knot points 0 .. N-2 become
+        those of k + 1, in place; N-1 and N keep theirs until update_linear_costs(q, None, c, N-1, N) and
+        update_linear_costs(None, r, None, N-1, N-1) write the new ones."""
+        _check(self.L.altro_hip_shift_linear_costs(self.h))
 
     def set_cost(self, Q, R, H, q, r, is_diag=False, k_stride_zero=False, batch_stride_zero=False):
         keep = [_in(v) for v in (Q, R, H, q, r)]

@@ -1332,15 +1332,7 @@ int altro_hip_get_expansion(altro_hip_batch* h, double* A, double* B, double* lx
       raw.assign((size_t)B_ * nk * block, 0.0);
       return aos_get(h, raw.data(), src, off, bs, ks, block, nk);
     };
-    if (A || B) {
-      if ((rc = fetch(h->m_in, h->m_st.in_bs, h->m_st.in_ks, MF_OFF_Z, 192, N))) return rc;
-      for (int64_t b = 0; b < B_; ++b)
-        for (int k = 0; k < N; ++k) {
-          const double* zr = raw.data() + ((size_t)b * N + k) * 192;
-          if (A) for (int j = 0; j < n; ++j) for (int i = 0; i < n; ++i) A[((size_t)b * N + k) * n * n + i + (size_t)n * j] = zr[i * 16 + j];
-          if (B) for (int j = 0; j < m; ++j) for (int i = 0; i < n; ++i) B[((size_t)b * N + k) * n * m + i + (size_t)n * j] = zr[i * 16 + MF_N + j];
-        }
-    }
+    if ((A || B) && (rc = mfma16_get_z(h, 0, N, A, B))) return rc;
     if (lx || lu) {
       if ((rc = fetch(h->m_cin, h->m_st.cin_bs, h->m_st.cin_ks, MF_OFF_QR, 16, N))) return rc;
       for (int64_t b = 0; b < B_; ++b)

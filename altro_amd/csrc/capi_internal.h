@@ -28,6 +28,7 @@
 #include "al_shift.h"
 #include "device_ledger.h"
 #include "loop_fields.h"
+#include "shift_fields.h"
 #include "loop_route.h"
 #include "sweep_route.h"
 #include "rtc_unit.h"
@@ -471,6 +472,22 @@ inline int mfma16_get(altro_hip_batch* h, int what, double* host, int block, int
   });
 }
 
+// plan MFMA16: Z = [A B] of knot points k0 .. k0 + nk - 1 out of the DYN records, in the caller's own dimensions -- A [batch][nk][n n],
+// B [batch][nk][n m], column-major blocks; HOST arrays, either may be null (altro_hip_get_expansion, altro_hip_get_dynamics_knot)
+inline int mfma16_get_z(altro_hip_batch* h, int k0, int nk, double* A, double* B) {
+  const int n = h->n, m = h->m;
+  const int64_t B_ = h->batch;
+  std::vector<double> raw((size_t)B_ * nk * 192, 0.0);
+  if (const int rc = aos_get(h, raw.data(), h->m_in, k0 * h->m_st.in_ks + MF_OFF_Z, h->m_st.in_bs, h->m_st.in_ks, 192, nk)) return rc;
+  for (int64_t b = 0; b < B_; ++b)
+    for (int k = 0; k < nk; ++k) {
+      const double* zr = raw.data() + ((size_t)b * nk + k) * 192;
+      if (A) for (int j = 0; j < n; ++j) for (int i = 0; i < n; ++i) A[((size_t)b * nk + k) * n * n + i + (size_t)n * j] = zr[i * 16 + j];
+      if (B) for (int j = 0; j < m; ++j) for (int i = 0; i < n; ++i) B[((size_t)b * nk + k) * n * m + i + (size_t)n * j] = zr[i * 16 + MF_N + j];
+    }
+  return 0;
+}
+
 // Whole-array upload of one reference-layout source for the MFMA16 pack kernels (setup path).
 // `nk_host` = knot points per problem actually present in the host array.
 // (a device buffer that lives for one call: the call's, not the handle's -- not in the ledger, not in altro_hip_batch_device_bytes)
@@ -506,18 +523,22 @@ inline int put_src(altro_hip_batch* h, const double* src, int blk, int nk_host, 
 }
 // (cin / term: the COST and TERM records to fill -- the handle's own, or the dense cost's copies m_costd / m_costd_term, which
 //  have the same layout and strides)
+// (k0, nk: the running segments of knot points k0 .. k0 + nk - 1 only, from sources whose knot point 0 is k0 -- the kernel is handed the
+//  records from k0 on as a horizon of nk; default: the whole horizon)
 inline int mfma16_pack_launch(altro_hip_batch* h, int seg, SrcArr s0, SrcArr s1, void* cin = nullptr, void* term = nullptr,
-                              int is_diag = -1) {
-  const int64_t total = (int64_t)h->batch * h->N * 192;
+                              int is_diag = -1, int k0 = 0, int nk = -1) {
+  if (nk < 0) nk = h->N;
+  const int64_t total = (int64_t)h->batch * nk * 192;
   if (!cin) cin = h->m_cin;
   if (!term) term = h->m_term;
   if (is_diag < 0) is_diag = h->is_diag;
+  const int64_t in0 = k0 * h->m_st.in_ks, cin0 = k0 * h->m_st.cin_ks;
   if (h->dtype == ALTRO_HIP_F64)
-    hipLaunchKernelGGL(mfma16_pack_kernel<double>, dim3(grid_for(total)), dim3(256), 0, h->stream, (double*)h->m_in,
-                       (double*)cin, (double*)term, h->m_st, seg, s0, s1, is_diag, h->N, 0, h->batch, h->n, h->m);
+    hipLaunchKernelGGL(mfma16_pack_kernel<double>, dim3(grid_for(total)), dim3(256), 0, h->stream, (double*)h->m_in + in0,
+                       (double*)cin + cin0, (double*)term, h->m_st, seg, s0, s1, is_diag, nk, 0, h->batch, h->n, h->m);
   else
-    hipLaunchKernelGGL(mfma16_pack_kernel<float>, dim3(grid_for(total)), dim3(256), 0, h->stream, (float*)h->m_in,
-                       (float*)cin, (float*)term, h->m_st, seg, s0, s1, is_diag, h->N, 0, h->batch, h->n, h->m);
+    hipLaunchKernelGGL(mfma16_pack_kernel<float>, dim3(grid_for(total)), dim3(256), 0, h->stream, (float*)h->m_in + in0,
+                       (float*)cin + cin0, (float*)term, h->m_st, seg, s0, s1, is_diag, nk, 0, h->batch, h->n, h->m);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(ALTRO_HIP_ERR_HIP, "mfma16_pack launch: %s", hipGetErrorString(e));
   return 0;
@@ -584,6 +605,8 @@ inline int lane_get(altro_hip_batch* h, double* host, const void* base, int64_t 
 inline LoopShape loop_shape(const altro_hip_batch* h) {
   return LoopShape{h->plan, h->ragged, h->cost_dense, h->n, h->m, h->N, h->batch, h->m_st.xuy_bs, h->m_st.xuy_ks, h->nxv.data(), h->nuv.data()};
 }
+// where the dynamics given as data live (shift_fields.h)
+inline DynShape dyn_shape(const altro_hip_batch* h) { return DynShape{h->plan, h->n, h->m, h->N, h->batch, h->m_st.in_bs, h->m_st.in_ks}; }
 // what the route of a TVLQR sweep launch may depend on (sweep_route.h)
 inline SweepShape sweep_shape(const altro_hip_batch* h) {
   return SweepShape{h->plan, h->dtype == ALTRO_HIP_F64, h->flags, h->forms, h->n, h->m, h->N, h->batch, h->is_diag != 0, h->has_f && !h->ilqr_linear,
@@ -591,7 +614,8 @@ inline SweepShape sweep_shape(const altro_hip_batch* h) {
 }
 inline void* loop_buffer(const altro_hip_batch* h, int buf) {
   void* const p[] = {nullptr, h->g_arr[G_x], h->g_arr[G_u], h->g_xn, h->g_un, h->g_cQ, h->g_cR, h->g_cH, h->g_cq, h->g_cr, h->g_cc,
-                     h->m_xuy, h->m_nom, h->m_costp, h->m_costd, h->m_costd_term, h->l_xuy, h->l_nom, h->l_cost, h->l_costq};
+                     h->m_xuy, h->m_nom, h->m_costp, h->m_costd, h->m_costd_term, h->l_xuy, h->l_nom, h->l_cost, h->l_costq,
+                     h->m_in, h->l_in, h->g_arr[G_A], h->g_arr[G_B], h->g_arr[G_f]};
   return p[buf];
 }
 // knot points k0 .. k0 + nk - 1 of one field <- a reference-layout host array of nk_host (default: 1 with kz, else nk) knot points per
@@ -686,6 +710,8 @@ int al_set_penalty_launch(hipStream_t stream, IlqrProb* prob, const double* rho,
 int al_rhs_scatter_launch(hipStream_t stream, void* dst, int esz, const double* src, int C, int nb, int batch, int form);
 int al_rhs_shift_launch(hipStream_t stream, void* g, int esz, int K, int64_t stride);
 int al_get_penalty_launch(hipStream_t stream, const IlqrProb* prob, double* rho, int batch);
+// shift_field_launch.hip (kernels/shift_field.hip): 0 ok, 1 the description is not safe to walk in place, 2 launch failed
+int shift_field_launch(hipStream_t stream, void* buf, int esz, const capi::ShiftRun& r);
 namespace capi {
 
 }  // namespace capi

@@ -39,7 +39,8 @@ enum LoopBuf {
   LB_NONE,   // the field does not exist there: no input at k = N, no Qd on a dense cost, ...
   LB_G_X, LB_G_U, LB_G_XN, LB_G_UN, LB_G_CQ, LB_G_CR, LB_G_CH, LB_G_Cq, LB_G_Cr, LB_G_Cc,
   LB_M_XUY, LB_M_NOM, LB_M_COSTP, LB_M_COSTD, LB_M_COSTD_TERM,
-  LB_L_XUY, LB_L_NOM, LB_L_COST, LB_L_COSTQ
+  LB_L_XUY, LB_L_NOM, LB_L_COST, LB_L_COSTQ,
+  LB_M_IN, LB_L_IN, LB_G_A, LB_G_B, LB_G_F   // the dynamics given as data (shift_fields.h)
 };
 enum LoopKind { LK_AOS, LK_LANE };
 

@@ -179,6 +179,32 @@ size_t altro_hip_batch_device_bytes(const altro_hip_batch* h);
 /* ---- problem data (reference layout in, converted once to the device layout) ----------------- */
 int altro_hip_set_dynamics(altro_hip_batch* h, const double* A, const double* B, const double* f,
                            int k_stride_zero, int batch_stride_zero);
+/* Dynamics given as data that move with a receding horizon (linear time-varying MPC), in place; no record is repacked:
+ *   altro_hip_set_dynamics_range   altro_hip_set_dynamics for knot points k_first .. k_last (inclusive, inside [0, N-1]) only:
+ *                          A [nb][nk][n*n], B [nb][nk][n*m], f [nb][nk][n], column-major blocks, nk = k_last - k_first + 1, nb = 1 with
+ *                          batch_stride_zero.  Host arrays, or fp64 device arrays read in place under altro_hip_set_pointer_mode.  The
+ *                          records of every other knot point and every non-dynamics field of the same records keep their bits (plan
+ *                          LANE: A | B | f share a record with the sweep's cost blocks); shapes below the (12, 4) tile are padded as
+ *                          altro_hip_set_dynamics pads them.  f == NULL writes zeros for the range; a non-NULL f on a handle whose
+ *                          dynamics were set without f turns the affine term on -- the handle then behaves as if altro_hip_set_dynamics
+ *                          had been given an f that is zero elsewhere.  Invalidates the current expansion and synchronises the handle's
+ *                          stream before it returns.  Errors, with nothing written: a range outside [0, N-1] or k_first > k_last, a
+ *                          NULL A or B: ALTRO_HIP_ERR_BAD_ARGUMENT; no altro_hip_set_dynamics yet, or a device model (altro_hip_set_model
+ *                          / _set_model_source: the dynamics are the model's): ALTRO_HIP_ERR_NOT_SET; per-knot-point dimensions, or
+ *                          altro_hip_set_host_batch in effect (a staging aid for synthetic batches, no MPC path): ALTRO_HIP_ERR_UNSUPPORTED.
+ *   altro_hip_get_dynamics_knot    what the device holds at knot point k, widened to double, in the caller's own dimensions (the tile's
+ *                          padding stripped): A [batch][n*n], B [batch][n*m], f [batch][n]; HOST arrays in either pointer mode, any of
+ *                          them may be NULL.  Refuses the same handles as the setter.
+ *   altro_hip_shift_dynamics       the companion of altro_hip_shift_trajectory: for k = 0 .. N-2, (A_k, B_k, f_k) become what
+ *                          (A_{k+1}, B_{k+1}, f_{k+1}) were; knot point N-1 keeps its values (as ShiftTrajectory leaves its last state
+ *                          duplicated) until altro_hip_set_dynamics_range(h, A, B, f, N-1, N-1, ...) writes the new ones.  In place, one
+ *                          kernel launch per buffer on the handle's stream (kernels/shift_field.hip; what it costs: DESIGN.md 4.36);
+ *                          nothing else of any record moves.  N = 1 moves nothing and returns 0.  Invalidates the current expansion.
+ *                          Refuses the same handles as the setter.                                                                    */
+int altro_hip_set_dynamics_range(altro_hip_batch* h, const double* A, const double* B, const double* f,
+                                 int k_first, int k_last, int batch_stride_zero);
+int altro_hip_get_dynamics_knot(altro_hip_batch* h, int k, double* A, double* B, double* f);
+int altro_hip_shift_dynamics(altro_hip_batch* h);
 /* Q, R symmetric, as the reference requires (altro_solver.hpp:183).  Plan MFMA16 stores the symmetric blocks once:
  * of Q_0..Q_{N-1} only the upper triangle is read, and altro_hip_get_P returns P_0..P_{N-1} mirrored from the upper
  * triangle the sweep keeps (exactly symmetric, within rounding of the reference's P). */
@@ -481,10 +507,19 @@ int altro_hip_feasibility(altro_hip_batch* h, double* out);
  *                                   r [nb][nk][m] or NULL, c [nb][nk] or NULL for knot points
  *                                   k_first..k_last (inclusive); nk = 1 if kz, nb = 1 if bz
  *   altro_hip_get_knot              ALTROSolver::GetState / GetInput (altro_solver.cpp:323-347) for the batch
+ *   altro_hip_shift_linear_costs    the companion of altro_hip_update_linear_costs for a reference that moves with the horizon: for
+ *                                   k = 0 .. N-2, (q_k, r_k, c_k) become (q_{k+1}, r_{k+1}, c_{k+1}), in place; knot points N-1 and N
+ *                                   keep theirs.  The terminal weight generally differs from the running one, so q_N is NOT a valid
+ *                                   q_{N-1}: the caller writes both afterwards -- altro_hip_update_linear_costs(h, q, NULL, c, N-1, N, ...)
+ *                                   and, since r has no terminal knot point, a second call (h, NULL, r, NULL, N-1, N-1, ...).  Exactly the
+ *                                   fields altro_hip_update_linear_costs writes move, for the diagonal and the dense cost, on every
+ *                                   plan; the weights do not.  No loop cost set: ALTRO_HIP_ERR_NOT_SET, as altro_hip_update_linear_costs
+ *                                   answers; per-knot-point dimensions: ALTRO_HIP_ERR_UNSUPPORTED.
  * (altro_hip_set_initial_state is ALTROSolver::SetInitialState, altro_solver.cpp:177-190.)               */
 int altro_hip_shift_trajectory(altro_hip_batch* h);
 int altro_hip_update_linear_costs(altro_hip_batch* h, const double* q, const double* r, const double* c,
                                   int k_first, int k_last, int kz, int bz);
+int altro_hip_shift_linear_costs(altro_hip_batch* h);
 int altro_hip_get_knot(altro_hip_batch* h, int k, double* x /* [batch][n] */, double* u /* [batch][m] */);
 
 /* ALWAYS start from altro_hip_default_solve_options(&o) and change fields afterwards: the struct grows at its END between library

@@ -168,6 +168,16 @@ class BatchSolver {
     Check(altro_hip_update_linear_costs(h_, q, r, c, k_start, k_stop, shared_over_k, shared_over_batch));
   }
   void ShiftTrajectory() { Check(altro_hip_shift_trajectory(h_)); }
+  // The problem data's part of ShiftTrajectory for dynamics given as data and a reference that moves with the horizon (altro_hip.h:
+  // altro_hip_set_dynamics_range and its siblings): knot points k_first .. k_last of the dynamics rewritten in place (A, B, f follow the
+  // pointer mode), what the device holds at knot point k (host arrays, any may be null), and the one-knot-point shifts of (A, B, f) and
+  // of (q, r, c) -- after which the caller writes knot point N-1 (and q_N, c_N) anew
+  void SetDynamicsRange(const double* A, const double* B, const double* f, int k_first, int k_last, bool shared_over_batch = false) {
+    Check(altro_hip_set_dynamics_range(h_, A, B, f, k_first, k_last, shared_over_batch));
+  }
+  void GetDynamicsKnot(int k, double* A, double* B, double* f) { Check(altro_hip_get_dynamics_knot(h_, k, A, B, f)); }
+  void ShiftDynamics() { Check(altro_hip_shift_dynamics(h_)); }
+  void ShiftLinearCosts() { Check(altro_hip_shift_linear_costs(h_)); }
 
  private:
   static void Check(int rc) {
